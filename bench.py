@@ -8,6 +8,11 @@
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --workload c5 [--gpus N]               (BASELINE configs[4]: 4 members per GPU, 4-step
                                                             grid->mesh->grid rollout, members/s incl. the one gather)
+    python bench.py ... --full                             (also every side measurement listed below)
+    python bench.py ... --dump-outputs DIR                 (writes the last timed step's outputs as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps, writes the outputs if asked, and prints the JSON line; its
+`ms_per_step` is the wall time of one timed step.  Everything else it can measure runs only with --full.
 
 Headline workload (BASELINE.json configs[1], "c2"): synthetic ICON-CH1-scale geodesic mesh, nu = 100 ->
 N = 100 002 nodes, E = 600 000 directed edges; GNNModel(channels 64 -> hidden 64 -> 64), fp32 storage,
@@ -18,7 +23,7 @@ Inputs, weights and the prepared graph are resident in HBM before the timed regi
 members are sharded one per rank (weak scaling), there is no collective on the data path, and the
 single RCCL all-gather of the final states sits INSIDE the timed region, after the last step.
 
-Extra objects on the JSON line (DESIGN.md "Measurement"):
+Extra objects on the JSON line of a --full run (DESIGN.md "Measurement"):
   roofline      -- dominant kernel of the c2 step.  c2's working set (3 x 25.6 MB) lives in the L2s and the
                    256 MiB Infinity Cache, so the ceiling that binds is the L2 ("bound": "l2", peak 34.5
                    TB/s, MI355X_MICROARCH.md): achieved = bytes the kernel pulls through L1/L2 (SURVEY 8(d)'s
@@ -61,6 +66,32 @@ L2_PEAK_GBS = 34500.0          # same guide, "L2 (per XCD)": ~34.5 TB/s aggregat
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # same guide: "~2.5 PF dense" bf16 MFMA
 L2_GATHER_GBS = 17800.0        # same guide, "Indexed rows": rows served by the XCD's L2, 16.8-18.8 TB/s chip-wide
 MIN_SAMPLES = 10
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all .npy files together, headers included
+DUMP_SEED = 23
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32.  When they hold more than DUMP_LIMIT_BYTES
+    together, each keeps the same share of the budget as a sample of its rows (leading axes flattened, last axis
+    kept whole), drawn by a fixed seed and kept in row order, so two runs with the same arguments write the same
+    rows.  Returns {name: [shape written, shape computed]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: (v.detach().float().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32))
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(host)                     # room for the .npy headers
+    written = {}
+    for name, a in sorted(host.items()):
+        full_shape = list(a.shape)
+        if total > budget and a.ndim >= 1 and a.size:
+            rows = a.reshape(-1, a.shape[-1]) if a.ndim >= 2 else a.reshape(-1, 1)
+            keep = max(1, min(rows.shape[0], int(budget * (a.nbytes / total)) // rows[0].nbytes))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], keep, replace=False))
+            a = rows[idx] if a.ndim >= 2 else rows[idx, 0]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = [list(a.shape), full_shape]
+    return written
 
 
 def parse():
@@ -72,6 +103,13 @@ def parse():
                    help="c2: BASELINE configs[1], GNNModel forward on the nu=100 mesh, edges/s (the headline); "
                         "c5: BASELINE configs[4], InteractionNet grid->mesh->grid forecaster, 4 members per GPU, "
                         "4-step autoregressive rollout + ONE all-gather, members/s")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the side measurements: per-kernel events and the roofline, the "
+                        "live PMC traffic passes, the precision siblings, the HBM legs, the edge-MLP block and the CPU "
+                        "baseline (the --no-* options below trim a --full run); a plain run times the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step computed as DIR/<name>.npy (float32, at most "
+                        f"{DUMP_LIMIT_BYTES // 10 ** 6} MB in all: a fixed seeded sample of rows beyond that)")
     p.add_argument("--launch-dry-run", action="store_true",
                    help="with --gpus N > 1 and no WORLD_SIZE in the environment: print the N child command lines "
                         "and their rank environments as one JSON object and exit without starting them")
@@ -95,7 +133,7 @@ def parse():
                    help="auto: fused kernels, bf16x6 contraction (fp32-class, the library default); bf16x3: the same "
                         "kernels on the faster two-image split; fused_exact: fp32-input MFMA; unfused: K3 + K2 per layer")
     p.add_argument("--event-stride", type=int, default=40,
-                   help="record per-kernel hipEvents on every n-th timed step (each pair of records "
+                   help="--full: record per-kernel hipEvents on every n-th timed step (each pair of records "
                         "opens a ~10 us gap on the stream, so instrumenting every step would slow the "
                         "steps being timed); more instrumented steps follow the timed region until "
                         f"every kernel has {MIN_SAMPLES} samples")
@@ -133,6 +171,8 @@ def parse():
         a.steps = 200 if a.workload == "c2" else 10
     if a.warmup is None:
         a.warmup = 20 if a.workload == "c2" else 2
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -653,6 +693,8 @@ def run_c5(args, world, rank, dev):
         dist.all_reduce(elapsed, op=dist.ReduceOp.MAX)
     elapsed = float(elapsed.item())
     assert out.shape[0] == members and torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": out})                # every member's final state, gathered
 
     allgather = None
     if world > 1:               # the collective by itself (outside the timed region; the timed steps contain it)
@@ -685,7 +727,7 @@ def run_c5(args, world, rank, dev):
         allgather["expected"] = allgather_expectation(allgather["bytes_per_rank"], world)
         line["allgather"] = allgather
     line["library"] = library_info(args)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         # dominant kernel of the step: K6's edge kernel on the mesh->mesh blocks, by itself on the same batch
         side = edge_mlp_side_measurement(mesh, ch, dev, launches=10, members=m_local)
         t_k6 = side["us_per_launch"] * 1e-6
@@ -708,10 +750,7 @@ def run_c5(args, world, rank, dev):
         if not args.no_cpu_baseline:
             from oracle import interaction_oracle as IO
             line["cpu_baseline"] = c5_cpu_baseline(IO, model, mesh, graphs, x, out, args, members, elapsed)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    emit_line(line, rank, world)
 
 
 def c5_cpu_baseline(IO, model, mesh, graphs, x, out, args, members, elapsed):
@@ -776,8 +815,9 @@ def main():
         return pmc_child(args)
     if "WORLD_SIZE" in os.environ or args.gpus == 1:
         library_info(args)                               # refuse a variant library before any work
-    if args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.workload == "c2" and not args.no_live_traffic \
-            and not (args.no_hbm_leg and args.no_edge_mlp) and "ROCPROF_OUTPUT_PATH" not in os.environ:
+    if args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and args.workload == "c2" \
+            and not args.no_live_traffic and not (args.no_hbm_leg and args.no_edge_mlp) \
+            and "ROCPROF_OUTPUT_PATH" not in os.environ:
         collect_live_traffic(args)                       # (not when this run is itself under rocprofv3)
     world, rank, dev = init_ranks(args)
     if args.workload == "c5":
@@ -826,9 +866,9 @@ def main():
     # ---- the whole stack behind one C call; hipEvents around every kernel launch ----------------
     plan = gwen_amd.StackForward(model.stack(), graph)
     out = plan.run(x)                                                 # allocates scratch + output
-    stride = max(1, args.event_stride)                                # events on every stride-th step
+    stride = max(1, args.event_stride)                                # events on every stride-th step (--full)
     samp = Sampler(gwen_amd, 2 * layers)
-    n_sets = (args.steps + stride - 1) // stride
+    n_sets = (args.steps + stride - 1) // stride if args.full else 0
     ev_sets = [samp.new() for _ in range(n_sets)]
 
     graphed = gwen_amd.GraphedForward(plan, x) if args.graph else None
@@ -859,7 +899,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(ev_sets[i // stride] if i % stride == 0 else None)
+        step(ev_sets[i // stride] if n_sets and i % stride == 0 else None)
     final = out if out.dim() == 3 else out.unsqueeze(0)
     if world > 1:
         ag0, ag1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -878,8 +918,40 @@ def main():
     assert gathered.shape[0] == members and torch.isfinite(gathered).all()
 
     allgather = timed_allgather_object(ag0, ag1, final, world, dev) if world > 1 else None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: GNNModel.forward's output (all members once gathered)
+        dump_outputs(args.dump_outputs, {"output": gathered if world > 1 else out})
 
-    # ---- more instrumented steps (outside the timed region) until every kernel has MIN_SAMPLES ------
+    value = members * layers * e * args.steps / elapsed
+    line = {
+        "metric": "mesh edges/s (message+aggregate)", "value": value, "unit": "edges/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_ms": args.prewarm_ms,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"c2: geodesic mesh nu={args.nu} N={n} E={e}, GNNModel forward "
+                               f"C={c} H={h} (6 GCNConv layers at widths "
+                               f"{'/'.join(str(min(a, b)) for a, b in widths)} gathered), {m_local} member/GPU",
+                   "nodes": n, "edges": e, "channels": c, "hidden": h, "layers": layers,
+                   "members": members, "node_order": args.reorder, "kernel_order": args.order,
+                   "contraction": {"auto": "the library default, fp32-class on each kernel's own split -- at this "
+                                           "model's widths (<= 64) bf16x6: three bf16 images per operand, six MFMA "
+                                           "terms, fp32 accumulation (see gpu_vs_oracle_rel_err; siblings: bf16x3, "
+                                           "exact_f32; K8 runs f16x3: hbm_leg)",
+                                   "bf16x3": "bf16x3 split: two bf16 images per operand, three MFMA terms",
+                                   "fused_exact": "fp32-input MFMA (exact fp32 products)",
+                                   "unfused": "fp32-input MFMA in K3 (explicit orders contract in fp32)"}[args.order],
+                   "hip_graph": bool(args.graph), "rehearsal": "gloo, all ranks on GPU 0" if args.rehearse_gloo else None,
+                   "parallelism": f"ensemble members sharded 1 rank = {m_local} member(s); one all-gather at end"},
+        "members_per_s": members * args.steps / elapsed,
+    }
+    if allgather is not None:
+        allgather["expected"] = allgather_expectation(allgather["bytes_per_rank"], world)
+        line["allgather"] = allgather
+    line["library"] = library_info(args)
+    if not args.full:
+        return emit_line(line, rank, world)
+
+    # ---- --full: more instrumented steps (outside the timed region) until every kernel has MIN_SAMPLES ------
     while samp.min_samples() < MIN_SAMPLES:
         step(samp.new())
         torch.cuda.synchronize()
@@ -919,40 +991,14 @@ def main():
                   "bound this kernel; the HBM-bound measurement of the same path is hbm_leg",
     }
 
-    value = members * layers * e * args.steps / elapsed
     # one 64 -> 64 message+aggregate pass by itself (the last layer: a whole-layer kernel at 64 channels)
     last_key = [k for k in summ if k[1] == h and k[2] == c and k[0] in ("layer", "wide")]
     pass64 = None
     if last_key:
         cnt_, tot_ = summ[last_key[0]]
         pass64 = round(m_local * e / (tot_ / cnt_))
-    line = {
-        "metric": "mesh edges/s (message+aggregate)", "value": value, "unit": "edges/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "prewarm_ms": args.prewarm_ms,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"c2: geodesic mesh nu={args.nu} N={n} E={e}, GNNModel forward "
-                               f"C={c} H={h} (6 GCNConv layers at widths "
-                               f"{'/'.join(str(min(a, b)) for a, b in widths)} gathered), {m_local} member/GPU",
-                   "nodes": n, "edges": e, "channels": c, "hidden": h, "layers": layers,
-                   "members": members, "node_order": args.reorder, "kernel_order": args.order,
-                   "contraction": {"auto": "the library default, fp32-class on each kernel's own split -- at this "
-                                           "model's widths (<= 64) bf16x6: three bf16 images per operand, six MFMA "
-                                           "terms, fp32 accumulation (see gpu_vs_oracle_rel_err; siblings: bf16x3, "
-                                           "exact_f32; K8 runs f16x3: hbm_leg)",
-                                   "bf16x3": "bf16x3 split: two bf16 images per operand, three MFMA terms",
-                                   "fused_exact": "fp32-input MFMA (exact fp32 products)",
-                                   "unfused": "fp32-input MFMA in K3 (explicit orders contract in fp32)"}[args.order],
-                   "hip_graph": bool(args.graph), "rehearsal": "gloo, all ranks on GPU 0" if args.rehearse_gloo else None,
-                   "parallelism": f"ensemble members sharded 1 rank = {m_local} member(s); one all-gather at end"},
-        "members_per_s": members * args.steps / elapsed,
-        "edges_per_s_64ch_pass": pass64,
-        "roofline": roofline,
-    }
-    if allgather is not None:
-        allgather["expected"] = allgather_expectation(allgather["bytes_per_rank"], world)
-        line["allgather"] = allgather
-    line["library"] = library_info(args)
+    line["edges_per_s_64ch_pass"] = pass64
+    line["roofline"] = roofline
 
     single = rank == 0 and world == 1
     # ---- siblings of the headline on the other contractions (outside the timed region) ----------------------
@@ -1032,6 +1078,11 @@ def main():
                                        "passes": v[1]} for th, v in sorted(sweep.items())},
             "gpu_vs_oracle_rel_err": err,
         }
+    emit_line(line, rank, world)
+
+
+def emit_line(line, rank, world):
+    """Print the one JSON result line (rank 0) and, with N > 1 ranks, destroy the process group."""
     if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:

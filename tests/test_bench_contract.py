@@ -35,11 +35,82 @@ def test_default_flags_are_the_contract(monkeypatch):
     assert a.prewarm_ms > 0
 
 
+def test_plain_run_flags(monkeypatch):
+    """`--gpus 1 --steps K --warmup W` alone is the plain run: no --full measurements, no output files; K >= 1."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs) == (True, "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_dump_outputs_whole_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; within the budget every array whole, beyond it the same seeded sample of rows
+    (in row order) on every call, all files together within the budget."""
+    import numpy as np
+    import torch
+    import bench
+    a = torch.arange(3 * 200 * 64, dtype=torch.float32).reshape(3, 200, 64)
+    b = np.linspace(0.0, 1.0, 500)
+    bench.dump_outputs(str(tmp_path / "whole"), {"a": a, "b": b})
+    assert np.array_equal(np.load(tmp_path / "whole" / "a.npy"), a.numpy())
+    wb = np.load(tmp_path / "whole" / "b.npy")
+    assert wb.dtype == np.float32 and np.array_equal(wb, b.astype(np.float32))
+    limit = 2 * 4096 + 50_000
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    shapes = [bench.dump_outputs(str(tmp_path / k), {"a": a, "b": b}) for k in ("s1", "s2")]
+    assert shapes[0] == shapes[1] and shapes[0]["a"][1] == [3, 200, 64]
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").iterdir()) <= limit
+    for name in ("a", "b"):
+        s1, s2 = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert s1.dtype == np.float32 and np.array_equal(s1, s2) and 0 < s1.shape[0]
+    rows = np.load(tmp_path / "s1" / "a.npy")
+    assert rows.shape[1] == 64 and rows.shape[0] < 600
+    first = rows[:, 0] / 64                                   # row r of a.reshape(-1, 64) starts at 64 r
+    assert np.array_equal(rows, a.reshape(-1, 64).numpy()[first.astype(int)]) and (np.diff(first) > 0).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(hip_lib, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline only: the contract keys, `steps` = K, `ms_per_step`
+    behind `value`, none of the --full measurements; --dump-outputs writes the last step's GNNModel output, bit for
+    bit the same on a second run with the same arguments."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    got = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup",
+                    "config", "library"):
+            assert key in d, key
+        assert (d["steps"], d["warmup"], d["unit"], d["dtype"], d["higher_is_better"]) == (7, 2, "edges/s", "f32", True)
+        assert abs(d["value"] - 6 * 600_000 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+        for key in ("roofline", "cpu_baseline", "hbm_leg", "hbm_leg_64ch", "exact_f32", "bf16x3", "edge_mlp_block",
+                    "edge_mlp_block_8_members", "edges_per_s_64ch_pass"):
+            assert key not in d, key
+        assert [f.name for f in (tmp_path / run).iterdir()] == ["output.npy"]
+        y = np.load(tmp_path / run / "output.npy")
+        assert y.dtype == np.float32 and y.shape == (100_002, 64) and np.isfinite(y).all() and np.abs(y).max() > 0
+        got.append(y)
+    assert np.array_equal(got[0], got[1])
+
+
 @pytest.mark.gpu
 def test_bench_line_contract_on_a_tiny_run(hip_lib):
     """One JSON line with the fields the driver parses, `roofline` (frac <= 1, >= 10 samples) and `cpu_baseline`."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "2", "--no-hbm-leg", "--no-exact",
-           "--cpu-seconds", "1", "--edge-mlp-members", "0", "--prewarm-ms", "20"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "2", "--no-hbm-leg",
+           "--no-exact", "--cpu-seconds", "1", "--edge-mlp-members", "0", "--prewarm-ms", "20"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
@@ -133,10 +204,11 @@ def test_c5_workload_defaults(monkeypatch):
 
 
 @pytest.mark.gpu
-def test_c5_bench_line_on_a_small_run(hip_lib):
-    """--workload c5 at 64 channels: members/s line with the roofline of K6 and the oracle-checked CPU baseline."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--c5-channels", "64", "--steps", "2",
-           "--warmup", "1", "--cpu-seconds", "2", "--prewarm-ms", "20"]
+def test_c5_bench_line_on_a_small_run(hip_lib, tmp_path):
+    """--workload c5 at 64 channels: members/s line with the roofline of K6 and the oracle-checked CPU baseline; the
+    rollout's final states (4 x 200 000 x 64, beyond the dump budget) come out as a sample of rows."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "c5", "--c5-channels", "64",
+           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--prewarm-ms", "20", "--dump-outputs", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")][-1])
@@ -144,6 +216,13 @@ def test_c5_bench_line_on_a_small_run(hip_lib):
     assert abs(d["value"] - 4 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] <= 1
     assert d["cpu_baseline"]["gpu_vs_oracle_rel_err_one_step"] <= 1e-4
+    import numpy as np
+    import bench
+    assert [f.name for f in tmp_path.iterdir()] == ["output.npy"]
+    assert (tmp_path / "output.npy").stat().st_size <= bench.DUMP_LIMIT_BYTES
+    got = np.load(tmp_path / "output.npy")
+    assert got.dtype == np.float32 and got.ndim == 2 and got.shape[1] == 64 and 0 < got.shape[0] < 4 * 200_000
+    assert np.isfinite(got).all()
 
 
 @pytest.mark.gpu
@@ -175,7 +254,7 @@ def test_default_line_carries_live_pmc_traffic_and_the_library_stamp():
     """One short default-shaped run (N = 1): the contract keys, the library stamp, and `roofline.traffic` collected by
     this very run (two rocprofv3 --pmc child passes) -- within 1.0 .. 1.25 x the compulsory bytes for the HBM-bound legs
     (wasted re-reads would show here first); `ag["expected"]` on the N > 1 line is covered by the rehearsal test."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--hbm-steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "2", "--hbm-steps", "3",
            "--no-cpu-baseline", "--no-exact"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
