@@ -167,6 +167,10 @@ SIGNATURES = {
     "gwen_mlp2_f32": (_int, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 5 + [_i64, _i64, _int, _vp, _vp, _i64,
                               _vp, _i64, _int, _vp, C.c_size_t, _vp]),
     "gwen_mlp2_workspace_bytes": (_i64, [_i64]),
+    "gwen_mlp2_contract_supported": (_int, [_i64, _int]),
+    "gwen_mlp2_contract_workspace_bytes": (_i64, [_i64, _int]),
+    "gwen_mlp2_contract_f32": (_int, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 5 + [_i64, _i64, _int, _vp, _vp,
+                               _i64, _vp, _i64, _int, _int, _vp, C.c_size_t, _vp]),
     "gwen_mlp2_rows": (_int, [_i64]),
     "gwen_act_pair_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _int, _vp]),
     "gwen_act_pair_seg_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),
@@ -175,6 +179,7 @@ SIGNATURES = {
     "gwen_mlp2_bwd_supported": (_int, [_i64]),
     "gwen_mlp2_bwd_rows": (_i64, [_i64]),
     "gwen_mlp2_bwd_f32": (_int, [_vp] * 5 + [_i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, C.c_size_t, _vp]),
+    "gwen_mlp2_bwd_contract_f32": (_int, [_vp] * 5 + [_i64, _i64, _vp, _vp, _vp, _i64, _i64, _int, _vp, C.c_size_t, _vp]),
     "gwen_masked_l1_workspace_floats": (_i64, []),
     "gwen_masked_l1_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
 }

@@ -26,11 +26,19 @@
 //   phase 3  y = MFMA + b2; out = res + y stored from registers;
 //   phase 4  (aggregation) y -> LDS fp32 tile (aliases the A tile); one thread per (target row, 4
 //            columns) adds its rows' entries in stored order -- no atomics, bitwise reproducible.
+// fp32-class tier (GWEN_CONTRACT_F16X3, gwen_mlp2_contract_f32): f16x3 -- two power-of-two-scaled fp16 images per
+//   operand (split.h) in the very registers and LDS tiles of the hi/lo bf16 images, three v_mfma_f32_16x16x32_f16 per
+//   k-step: no more MFMAs, no more weight registers (bf16x6 would add a third image: ~32 VGPRs more at 128 channels and
+//   a third LDS image per tile).  Its cost: 8 VGPRs of column exponents, the per-row scales (TPW each), the hidden rows
+//   held across one more barrier, and NJW x ROWS x 4 B of LDS for the partial row maxima (512 B at 32 channels, 2 KB at
+//   128) -- a row's F values are spread over the NJW column-group waves, so its scale takes one LDS round and barrier per
+//   contraction.  Zero spills at both widths (the 128-channel instantiations use 214-242 of 256 VGPRs).
 // Tiles are ROW-ALIGNED (gwen_edge_tiles): tile c owns the target rows whose first edge lies in
 //   [cT, (c+1)T), so every target row is summed by exactly one block; T = 64 - (max degree - 1) makes a
 //   tile one pass of 64 edges on bounded-degree graphs, and a row longer than a pass is carried
 //   through the block's own earlier partial sum (same thread, program order).
 #include "common.h"
+#include "split.h"
 
 namespace {
 
@@ -63,6 +71,8 @@ struct MCfg {
   // two hi/lo images: the A tile (reused as the fp32 y tile of phase 4) and the hidden tile
   static constexpr size_t a_bytes = split_bytes > y_bytes ? split_bytes : y_bytes;
   static constexpr size_t lds_bytes = a_bytes + split_bytes;
+  // f16x3: partial row maxima, one per (column group, row) -- a row's F values are spread over NJW waves
+  static constexpr size_t lds_f16 = lds_bytes + (size_t)NJW * ROWS * 4;
   static constexpr int Q = F / 4;                                // 16-B pieces per row
   static constexpr int SLOTS = NWB * 64 / Q;                     // target rows reduced at a time
   static_assert(NT % TSTEP == 0 && NJ % NC == 0, "tiles must divide over the waves");
@@ -94,9 +104,57 @@ __device__ inline void load_w(const float *__restrict__ W, int jt, int mi, int m
   }
 }
 
+// ---- f16x3 (GWEN_CONTRACT_F16X3, see split.h): two scaled fp16 images per operand in the same registers and tiles ----
+__device__ inline int abs_bits(float x) { return __builtin_bit_cast(int, x) & 0x7fffffff; }
+__device__ inline int f16_scale_of(int m) {            // 2^k brings a maximum magnitude (as abs_bits) to [2^14, 2^15)
+  const int e = m >> 23;
+  return gwen::kF16Top - (e > gwen::kF16Floor ? e : gwen::kF16Floor);
+}
+// v * 2^-(s + c[i]): one exact ldexp per element, nothing in between that could leave fp32's range
+__device__ inline float4_t unscale4(float4_t v, int s, const int (&c)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = __builtin_ldexpf(v[i], -(s + c[i]));
+  return v;
+}
+// load_w for f16x3: the lane's W row (output column jt 16 + mi) is scaled by 2^s, s from the row's maximum over this
+// lane's 8 KS values and those of the three other lanes holding the row (mh = 0..3); returns s
+template <int F>
+__device__ inline int load_w_f16(const float *__restrict__ W, int jt, int mi, int mh,
+                                 bf16x8 (&whi)[MCfg<F>::KS], bf16x8 (&wlo)[MCfg<F>::KS]) {
+  const float *wrow = W + (int64_t)(jt * 16 + mi) * F;
+  float x[MCfg<F>::KS][8];
+  int m = 0;
+#pragma unroll
+  for (int ks = 0; ks < MCfg<F>::KS; ++ks)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float4_t a = *reinterpret_cast<const float4_t *>(wrow + 8 * (4 * ks + mh) + 4 * h);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x[ks][4 * h + i] = a[i];
+        m = max(m, abs_bits(a[i]));
+      }
+    }
+  m = max(m, __shfl_xor(m, 16));
+  m = max(m, __shfl_xor(m, 32));
+  const int s = f16_scale_of(m);
+#pragma unroll
+  for (int ks = 0; ks < MCfg<F>::KS; ++ks) gwen::split_f16<8>(x[ks], s, whi[ks], wlo[ks]);
+  return s;
+}
+
 // One k-step of TPW row tiles x NC column tiles: the operand pairs are read once, the products of
 // one kind go to all TPW * NC independent accumulators before the next kind touches them again.
-template <int F>
+// (F16: the same three products on v_mfma_f32_16x16x32_f16 -- the images carry fp16 bits)
+template <int F, bool F16>
+__device__ inline f32x4 mma1(const bf16x8 &w, const bf16x8 &a, const f32x4 &d) {
+  if constexpr (F16)
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(gwen::f16x8, w), __builtin_bit_cast(gwen::f16x8, a),
+                                                  d, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, a, d, 0, 0, 0);
+}
+template <int F, bool F16>
 __device__ inline void mma_step(const bf16x8 (&ahi)[MCfg<F>::TPW], const bf16x8 (&alo)[MCfg<F>::TPW],
                                 const bf16x8 (&whi)[MCfg<F>::NC], const bf16x8 (&wlo)[MCfg<F>::NC],
                                 f32x4 (&d)[MCfg<F>::TPW][MCfg<F>::NC]) {
@@ -105,17 +163,17 @@ __device__ inline void mma_step(const bf16x8 (&ahi)[MCfg<F>::TPW], const bf16x8 
   for (int n = 0; n < C::NC; ++n)
 #pragma unroll
     for (int k = 0; k < C::TPW; ++k)
-      d[k][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi[n], alo[k], d[k][n], 0, 0, 0);
+      d[k][n] = mma1<F, F16>(whi[n], alo[k], d[k][n]);
 #pragma unroll
   for (int n = 0; n < C::NC; ++n)
 #pragma unroll
     for (int k = 0; k < C::TPW; ++k)
-      d[k][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo[n], ahi[k], d[k][n], 0, 0, 0);
+      d[k][n] = mma1<F, F16>(wlo[n], ahi[k], d[k][n]);
 #pragma unroll
   for (int n = 0; n < C::NC; ++n)
 #pragma unroll
     for (int k = 0; k < C::TPW; ++k)
-      d[k][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi[n], ahi[k], d[k][n], 0, 0, 0);
+      d[k][n] = mma1<F, F16>(whi[n], ahi[k], d[k][n]);
 }
 
 template <int F>
@@ -131,7 +189,7 @@ __device__ inline void read_tiles(const __bf16 *thi, const __bf16 *tlo, int tt0,
 }
 
 // weights resident in registers
-template <int F>
+template <int F, bool F16>
 __device__ inline void tiles_mma(const __bf16 *thi, const __bf16 *tlo, int tt0, int mi, int mh,
                                  const bf16x8 (&whi)[MCfg<F>::NC][MCfg<F>::KS],
                                  const bf16x8 (&wlo)[MCfg<F>::NC][MCfg<F>::KS],
@@ -150,7 +208,7 @@ __device__ inline void tiles_mma(const __bf16 *thi, const __bf16 *tlo, int tt0, 
       wh[n] = whi[n][ks];
       wl[n] = wlo[n][ks];
     }
-    mma_step<F>(ahi, alo, wh, wl, d);
+    mma_step<F, F16>(ahi, alo, wh, wl, d);
   }
 }
 
@@ -176,7 +234,13 @@ struct Pass {
   int32_t w0, e0, e1;
 };
 
-template <int F, int M1, int M2, bool SEG>
+// F16 (GWEN_CONTRACT_F16X3): two fp16 images per operand (split.h) in the registers and tiles the hi/lo bf16 images
+// use -- the same MFMA count, registers and LDS, plus NJW x ROWS partial row maxima (2 KB at 128 channels).  W is
+// scaled per output column (load_w_f16); the A rows and the activated hidden rows per ROW: a row's values are spread
+// over the NJW column-group waves, so each wave posts its 16 columns' maximum to LDS and, after a barrier, every lane
+// takes the maximum of the NJW posts (one more barrier per contraction).  Both contractions accumulate from zero and
+// are un-scaled by one ldexp per element before the gathered addends / biases are added.
+template <int F, int M1, int M2, bool SEG, bool F16 = false>
 __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
     const float *__restrict__ A, const float *__restrict__ W1, const float *__restrict__ G1,
     const int32_t *__restrict__ idx1, const float *__restrict__ G2,
@@ -186,7 +250,8 @@ __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
     const int32_t *__restrict__ tile_row, int32_t n_tiles, float *__restrict__ agg, int mean,
     uint32_t ldb1, uint32_t ldb2) {                     // row strides of G1 / G2 in bytes
   using C = MCfg<F>;
-  __shared__ __attribute__((aligned(16))) char lds_raw[C::lds_bytes];
+  __shared__ __attribute__((aligned(16))) char lds_raw[F16 ? C::lds_f16 : C::lds_bytes];
+  int *emax = reinterpret_cast<int *>(lds_raw + C::lds_bytes);          // F16: [NJW][ROWS] partial row maxima
   __bf16 *thi = reinterpret_cast<__bf16 *>(lds_raw);                    // A tile, hi / lo
   __bf16 *tlo = thi + C::ROWS * C::PB;
   float *ytile = reinterpret_cast<float *>(lds_raw);                     // aliases the A tile (phase 4)
@@ -200,11 +265,46 @@ __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
 
   // resident: this wave's hi/lo fragments of both matrices
   bf16x8 w1hi[C::NC][C::KS], w1lo[C::NC][C::KS], w2hi[C::NC][C::KS], w2lo[C::NC][C::KS];
+  int c1[C::NC][4], c2[C::NC][4];         // F16: the exponents of this lane's output columns col(n) .. + 3
 #pragma unroll
   for (int n = 0; n < C::NC; ++n) {
-    load_w<F>(W1, jw * C::NC + n, mi, mh, w1hi[n], w1lo[n]);
-    load_w<F>(W2, jw * C::NC + n, mi, mh, w2hi[n], w2lo[n]);
+    if constexpr (F16) {
+      const int s1 = load_w_f16<F>(W1, jw * C::NC + n, mi, mh, w1hi[n], w1lo[n]);
+      const int s2 = load_w_f16<F>(W2, jw * C::NC + n, mi, mh, w2hi[n], w2lo[n]);
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {                      // column 4 mh + v of the tile is W row mi = 4 mh + v
+        c1[n][v] = __shfl(s1, 4 * mh + v);
+        c2[n][v] = __shfl(s2, 4 * mh + v);
+      }
+    } else {
+      load_w<F>(W1, jw * C::NC + n, mi, mh, w1hi[n], w1lo[n]);
+      load_w<F>(W2, jw * C::NC + n, mi, mh, w2hi[n], w2lo[n]);
+    }
   }
+  // F16: the scale exponent of each of this lane's rows from the row maxima of X over this wave's columns, posted to
+  // LDS by every column group (the caller has made the previous reads of emax safe to overwrite: a barrier lies between)
+  int sa[C::TPW], sh[C::TPW];
+  auto row_scale = [&](const float4_t (&X)[C::TPW][C::NC], int (&s)[C::TPW]) {
+#pragma unroll
+    for (int k = 0; k < C::TPW; ++k) {
+      int m = 0;
+#pragma unroll
+      for (int n = 0; n < C::NC; ++n)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = max(m, abs_bits(X[k][n][e]));
+      m = max(m, __shfl_xor(m, 16));
+      m = max(m, __shfl_xor(m, 32));
+      if (mh == 0) emax[jw * C::ROWS + (tt0 + k * C::TSTEP) * 16 + mi] = m;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < C::TPW; ++k) {
+      int m = 0;
+#pragma unroll
+      for (int q = 0; q < C::NJW; ++q) m = max(m, emax[q * C::ROWS + (tt0 + k * C::TSTEP) * 16 + mi]);
+      s[k] = f16_scale_of(m);
+    }
+  };
   float4_t b1v[C::NC], b2v[C::NC];
 #pragma unroll
   for (int n = 0; n < C::NC; ++n) {
@@ -304,8 +404,22 @@ __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
         float4_t v = areg[k][n];
         if (row >= n_rows) v = float4_t{0.f, 0.f, 0.f, 0.f};
         rv[k][n] = v;
+      }
+    }
+    if constexpr (F16) row_scale(rv, sa);
+#pragma unroll
+    for (int k = 0; k < C::TPW; ++k) {
+      const int row = (tt0 + k * C::TSTEP) * 16 + mi;
+#pragma unroll
+      for (int n = 0; n < C::NC; ++n) {
+        const float4_t v = rv[k][n];
         bf16x4 h4, l4;
-        split4(v, h4, l4);
+        if constexpr (F16) {
+          const float x[4] = {v[0], v[1], v[2], v[3]};
+          gwen::split_f16<4>(x, sa[k], h4, l4);
+        } else {
+          split4(v, h4, l4);
+        }
         *reinterpret_cast<bf16x4 *>(thi + row * C::PB + col(n)) = h4;
         *reinterpret_cast<bf16x4 *>(tlo + row * C::PB + col(n)) = l4;
       }
@@ -326,7 +440,29 @@ __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
     // (the hidden tile has its own LDS image: the previous pass's second contraction, which read it,
     //  lies before the barrier above for every wave)
     f32x4 d[C::TPW][C::NC];
-    tiles_mma<F>(thi, tlo, tt0, mi, mh, w1hi, w1lo, d);
+    tiles_mma<F, F16>(thi, tlo, tt0, mi, mh, w1hi, w1lo, d);
+    if constexpr (F16) {                                 // un-scale, then the addends; the hidden rows' own scales
+      float4_t hk[C::TPW][C::NC];
+#pragma unroll
+      for (int k = 0; k < C::TPW; ++k)
+#pragma unroll
+        for (int n = 0; n < C::NC; ++n)
+          hk[k][n] = activate(unscale4(float4_t{d[k][n][0], d[k][n][1], d[k][n][2], d[k][n][3]}, sa[k], c1[n]) +
+                              add[k][n], act);
+      row_scale(hk, sh);
+#pragma unroll
+      for (int k = 0; k < C::TPW; ++k) {
+        const int row = (tt0 + k * C::TSTEP) * 16 + mi;
+#pragma unroll
+        for (int n = 0; n < C::NC; ++n) {
+          const float x[4] = {hk[k][n][0], hk[k][n][1], hk[k][n][2], hk[k][n][3]};
+          bf16x4 h4, l4;
+          gwen::split_f16<4>(x, sh[k], h4, l4);
+          *reinterpret_cast<bf16x4 *>(hhi + row * C::PB + col(n)) = h4;
+          *reinterpret_cast<bf16x4 *>(hlo + row * C::PB + col(n)) = l4;
+        }
+      }
+    } else {
 #pragma unroll
     for (int k = 0; k < C::TPW; ++k) {
       const int row = (tt0 + k * C::TSTEP) * 16 + mi;
@@ -339,6 +475,7 @@ __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
         *reinterpret_cast<bf16x4 *>(hhi + row * C::PB + col(n)) = h4;
         *reinterpret_cast<bf16x4 *>(hlo + row * C::PB + col(n)) = l4;
       }
+    }
     }
     // residual rows other than A: requested before the second contraction, used after it
     const int64_t pass_off = (int64_t)cur.w0 * F;
@@ -356,13 +493,15 @@ __global__ __launch_bounds__(MCfg<F>::NWB * 64, MCfg<F>::MINW) void k_mlp2(
     __syncthreads();
     // ---- phase 3: second contraction, residual, store ---------------------------------------------
     float4_t y[C::TPW][C::NC];
-    tiles_mma<F>(hhi, hlo, tt0, mi, mh, w2hi, w2lo, d);
+    tiles_mma<F, F16>(hhi, hlo, tt0, mi, mh, w2hi, w2lo, d);
 #pragma unroll
     for (int k = 0; k < C::TPW; ++k) {
       const int row = (tt0 + k * C::TSTEP) * 16 + mi;
 #pragma unroll
       for (int n = 0; n < C::NC; ++n) {
-        y[k][n] = float4_t{d[k][n][0], d[k][n][1], d[k][n][2], d[k][n][3]} + b2v[n];
+        y[k][n] = float4_t{d[k][n][0], d[k][n][1], d[k][n][2], d[k][n][3]};
+        if constexpr (F16) y[k][n] = unscale4(y[k][n], sh[k], c2[n]);
+        y[k][n] += b2v[n];
         if (out && row < n_rows) {
           float4_t o = y[k][n];
           if (res) o += rv[k][n];
@@ -437,7 +576,7 @@ __global__ void k_edge_tiles(const int32_t *__restrict__ rowptr, int32_t N, int3
   for (int32_t c = s / T + 1; c < n_tiles && (int64_t)c * T <= en; ++c) tile_row[c] = r + 1;
 }
 
-template <int F, int M1, int M2>
+template <int F, int M1, int M2, bool F16>
 int launch(const float *A, const float *W1, const float *G1, const int32_t *idx1, const float *G2,
            const int32_t *idx2, const float *b1, const float *W2, const float *b2, const float *res,
            float *out, int64_t R, int act, const int32_t *rowptr, const int32_t *tile_row,
@@ -453,17 +592,17 @@ int launch(const float *A, const float *W1, const float *G1, const int32_t *idx1
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_mlp2<F, M1, M2, true>), C::NWB * 64, 0));
+        &nbk, reinterpret_cast<const void *>(&k_mlp2<F, M1, M2, true, F16>), C::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
   int64_t blocks = (int64_t)256 * per_cu;
   if (blocks > tiles) blocks = tiles;
   if (seg)
-    k_mlp2<F, M1, M2, true><<<(unsigned)blocks, C::NWB * 64, 0, st>>>(
+    k_mlp2<F, M1, M2, true, F16><<<(unsigned)blocks, C::NWB * 64, 0, st>>>(
         A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, (int32_t)R, act, rowptr, tile_row,
         (int32_t)tiles, agg, mean, ldb1, ldb2);
   else
-    k_mlp2<F, M1, M2, false><<<(unsigned)blocks, C::NWB * 64, 0, st>>>(
+    k_mlp2<F, M1, M2, false, F16><<<(unsigned)blocks, C::NWB * 64, 0, st>>>(
         A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, (int32_t)R, act, nullptr, nullptr,
         (int32_t)tiles, nullptr, 0, ldb1, ldb2);
   GWEN_LAUNCH_CHECK();
@@ -471,16 +610,18 @@ int launch(const float *A, const float *W1, const float *G1, const int32_t *idx1
 }
 
 template <int F>
-int launch_mode(int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
+int launch_mode(int f16, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
                 const float *G2, const int32_t *idx2, const float *b1, const float *W2,
                 const float *b2, const float *res, float *out, int64_t R, int act,
                 const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg, int mean,
                 void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st) {
-#define GWEN_MODE(A1, A2)                                                                        \
-  if (m1 == A1 && m2 == A2)                                                                      \
-    return launch<F, A1, A2>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr,    \
-                             tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st)
-  GWEN_MODE(kNone, kNone); GWEN_MODE(kSelf, kNone); GWEN_MODE(kIdx, kNone); GWEN_MODE(kIdx, kIdx);
+#define GWEN_MODE(A1, A2, H)                                                                     \
+  if (m1 == A1 && m2 == A2 && (f16 != 0) == H)                                                   \
+    return launch<F, A1, A2, H>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
+                                tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st)
+  GWEN_MODE(kNone, kNone, false); GWEN_MODE(kSelf, kNone, false); GWEN_MODE(kIdx, kNone, false);
+  GWEN_MODE(kIdx, kIdx, false);
+  GWEN_MODE(kNone, kNone, true); GWEN_MODE(kSelf, kNone, true); GWEN_MODE(kIdx, kNone, true); GWEN_MODE(kIdx, kIdx, true);
 #undef GWEN_MODE
   return GWEN_EINVAL;
 }
@@ -489,7 +630,8 @@ int launch_mode(int m1, int m2, const float *A, const float *W1, const float *G1
 
 // interact_rows.hip: the row-stationary kernel 256 channels run on
 int gwen_mlp2_rows_f();
-int gwen_mlp2_rows_launch(int F, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
+int64_t gwen_mlp2_rows_ws_bytes(int F, int f16);
+int gwen_mlp2_rows_launch(int F, int f16, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
                           const float *G2, const int32_t *idx2, const float *b1, const float *W2,
                           const float *b2, const float *res, float *out, int64_t R, int act,
                           const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg,
@@ -504,9 +646,18 @@ extern "C" int gwen_mlp2_rows(int64_t F) {
        : F == 256 ? gwen_mlp2_rows_f() : GWEN_EINVAL;
 }
 
+extern "C" int gwen_mlp2_contract_supported(int64_t F, int contract) {
+  return gwen_mlp2_supported(F) && (contract == GWEN_CONTRACT_BF16X3 || contract == GWEN_CONTRACT_F16X3) ? 1 : 0;
+}
+
+extern "C" int64_t gwen_mlp2_contract_workspace_bytes(int64_t F, int contract) {
+  if (!gwen_mlp2_contract_supported(F, contract)) return GWEN_EINVAL;
+  // 256 channels: two matrices x (hi, lo) x bf16-sized images (+ f16x3: 2 F column exponents); others: none
+  return gwen_mlp2_rows_ws_bytes((int)F, contract == GWEN_CONTRACT_F16X3);
+}
+
 extern "C" int64_t gwen_mlp2_workspace_bytes(int64_t F) {
-  if (!gwen_mlp2_supported(F)) return GWEN_EINVAL;
-  return F > 128 ? 2 * 2 * F * F * 2 : 0;      // two matrices x (hi, lo) x bf16
+  return gwen_mlp2_contract_workspace_bytes(F, GWEN_CONTRACT_BF16X3);
 }
 
 extern "C" int64_t gwen_edge_tiles_count(int64_t E, int64_t T) {
@@ -533,7 +684,7 @@ extern "C" int gwen_edge_tiles(const int32_t *rowptr, int64_t N, int64_t E, int6
 //     g_e    = ge + g_pre1 We
 // W2t = W2^T and Wet = We^T, [F, F] row-major (row = output column of the contraction); d1 = act'(pre1) [R, F];
 // g_pre1 has gwen_mlp2_bwd_rows(R) rows (whole passes: the kernel stores every lane), g_e has R.  F in {64, 256}.
-int gwen_mlp2_rows_bwd_launch(int F, const float *ge, const float *W2t, const float *d1, const float *T,
+int gwen_mlp2_rows_bwd_launch(int F, int f16, const float *ge, const float *W2t, const float *d1, const float *T,
                               const int32_t *dst, const float *Wet, float *hid, float *out, int64_t R, void *workspace,
                               uint32_t ldbT, hipStream_t st);
 extern "C" int64_t gwen_mlp2_bwd_rows(int64_t R) {
@@ -541,34 +692,44 @@ extern "C" int64_t gwen_mlp2_bwd_rows(int64_t R) {
   return R <= 0 ? 0 : (R + rows - 1) / rows * rows;
 }
 extern "C" int gwen_mlp2_bwd_supported(int64_t F) { return F == 64 || F == 256 ? 1 : 0; }
-extern "C" int gwen_mlp2_bwd_f32(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
-                                 int64_t T_rows, int64_t ldT, const float *Wet, float *g_pre1, float *g_e, int64_t R,
-                                 int64_t F, void *workspace, size_t workspace_bytes, gwen_stream_t stream_) {
-  if (R < 0 || T_rows < 0 || !gwen_mlp2_bwd_supported(F)) return GWEN_EINVAL;
+extern "C" int gwen_mlp2_bwd_contract_f32(const float *ge, const float *W2t, const float *d1, const float *T,
+                                          const int32_t *dst, int64_t T_rows, int64_t ldT, const float *Wet, float *g_pre1,
+                                          float *g_e, int64_t R, int64_t F, int contract, void *workspace,
+                                          size_t workspace_bytes, gwen_stream_t stream_) {
+  if (R < 0 || T_rows < 0 || !gwen_mlp2_bwd_supported(F) || !gwen_mlp2_contract_supported(F, contract))
+    return GWEN_EINVAL;
   if (R == 0) return GWEN_OK;
   if (!ge || !W2t || !d1 || !T || !dst || !Wet || !g_pre1 || !g_e || ldT < F || ldT % 4) return GWEN_EINVAL;
   if (g_pre1 == ge || g_pre1 == d1 || g_pre1 == g_e || g_e == d1) return GWEN_EINVAL;      // g_e may alias ge row for row
   if (R >= (int64_t(1) << 31) - kMaxRows || T_rows * ldT * 4 >= (int64_t(1) << 32) || R * F * 4 >= (int64_t(1) << 32))
     return GWEN_ERANGE;              // 32-bit byte offsets into the tables (d1 is read as a table, row for row)
-  const int64_t need = gwen_mlp2_workspace_bytes(F);
+  const int64_t need = gwen_mlp2_contract_workspace_bytes(F, contract);
   if (need > 0 && (!workspace || (int64_t)workspace_bytes < need)) return GWEN_ENOSPACE;
   const void *al[] = {ge, W2t, d1, T, Wet, g_pre1, g_e, need > 0 ? workspace : nullptr};
   for (const void *p : al)
     if (p && !gwen_aligned(p, 16)) return GWEN_EINVAL;
-  return gwen_mlp2_rows_bwd_launch((int)F, ge, W2t, d1, T, dst, Wet, g_pre1, g_e, R, workspace, (uint32_t)(ldT * 4),
-                                   gwen_stream(stream_));
+  return gwen_mlp2_rows_bwd_launch((int)F, contract == GWEN_CONTRACT_F16X3, ge, W2t, d1, T, dst, Wet, g_pre1, g_e, R,
+                                   workspace, (uint32_t)(ldT * 4), gwen_stream(stream_));
 }
 
-extern "C" int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                             int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
-                             int64_t G2_rows, int64_t ldg2,
-                             const float *b1, const float *W2, const float *b2, const float *res,
-                             float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
-                             const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
-                             int mean, void *workspace, size_t workspace_bytes,
-                             gwen_stream_t stream_) {
+extern "C" int gwen_mlp2_bwd_f32(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
+                                 int64_t T_rows, int64_t ldT, const float *Wet, float *g_pre1, float *g_e, int64_t R,
+                                 int64_t F, void *workspace, size_t workspace_bytes, gwen_stream_t stream_) {
+  return gwen_mlp2_bwd_contract_f32(ge, W2t, d1, T, dst, T_rows, ldT, Wet, g_pre1, g_e, R, F, GWEN_CONTRACT_BF16X3,
+                                    workspace, workspace_bytes, stream_);
+}
+
+extern "C" int gwen_mlp2_contract_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+                                      int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
+                                      int64_t G2_rows, int64_t ldg2,
+                                      const float *b1, const float *W2, const float *b2, const float *res,
+                                      float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
+                                      const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
+                                      int mean, int contract, void *workspace, size_t workspace_bytes,
+                                      gwen_stream_t stream_) {
   if (R < 0 || N_agg < 0 || n_tiles < 0 || G1_rows < 0 || G2_rows < 0) return GWEN_EINVAL;
-  if (!gwen_mlp2_supported(F)) return GWEN_EINVAL;
+  if (!gwen_mlp2_contract_supported(F, contract)) return GWEN_EINVAL;
+  const int f16 = contract == GWEN_CONTRACT_F16X3;
   if (act != GWEN_ACT_NONE && act != GWEN_ACT_RELU && act != GWEN_ACT_SILU) return GWEN_EINVAL;
   if (agg && (!rowptr || !tile_row || n_tiles < 1)) return GWEN_EINVAL;
   if (!agg && !out) return R == 0 ? GWEN_OK : GWEN_EINVAL;
@@ -586,20 +747,33 @@ extern "C" int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, c
   if ((G1 && G1_rows * ldg1 * 4 >= (int64_t(1) << 32)) || (G2 && G2_rows * ldg2 * 4 >= (int64_t(1) << 32)))
     return GWEN_ERANGE;              // 32-bit byte offsets into the tables
   if (out && (out == G1 || out == G2)) return GWEN_EINVAL;      // out may alias A / res row for row
-  const int64_t need = gwen_mlp2_workspace_bytes(F);
+  const int64_t need = gwen_mlp2_contract_workspace_bytes(F, contract);
   if (need > 0 && (!workspace || (int64_t)workspace_bytes < need)) return GWEN_ENOSPACE;
   const void *al[] = {A, W1, G1, G2, b1, W2, b2, res, out, agg, need > 0 ? workspace : nullptr};
   for (const void *p : al)
     if (p && !gwen_aligned(p, 16)) return GWEN_EINVAL;
 #define GWEN_M(FF)                                                                                \
   if (F == FF)                                                                                    \
-    return launch_mode<FF>(m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
+    return launch_mode<FF>(f16, m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
                            tile_row, n_tiles, agg, mean, workspace, (uint32_t)(ldg1 * 4),       \
                            (uint32_t)(ldg2 * 4), st)
   if (F == 256 || F == 64)
-    return gwen_mlp2_rows_launch((int)F, m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, tile_row,
+    return gwen_mlp2_rows_launch((int)F, f16, m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, tile_row,
                                  n_tiles, agg, mean, workspace, (uint32_t)(ldg1 * 4), (uint32_t)(ldg2 * 4), st);
   GWEN_M(32); GWEN_M(128);
 #undef GWEN_M
   return GWEN_EINVAL;
+}
+
+extern "C" int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+                             int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
+                             int64_t G2_rows, int64_t ldg2,
+                             const float *b1, const float *W2, const float *b2, const float *res,
+                             float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
+                             const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
+                             int mean, void *workspace, size_t workspace_bytes,
+                             gwen_stream_t stream_) {
+  return gwen_mlp2_contract_f32(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act,
+                                rowptr, tile_row, n_tiles, agg, N_agg, mean, GWEN_CONTRACT_BF16X3, workspace,
+                                workspace_bytes, stream_);
 }

@@ -35,6 +35,7 @@
 // (the first contraction accumulates onto them), so the pass body exists twice with the two sets swapped.
 #include "common.h"
 #include "rows_common.h"
+#include "split.h"
 // (the lab version of this file -- timing ablations -DABL=1..7, per-phase s_memtime stamps -DGWEN_K6R_STAMPS, two row
 //  tiles per wave -DK6R_RT=2 -- is tools/experiments/interact_rows_lab.patch; DESIGN.md section 4 / 7.3 has their numbers)
 constexpr int K6R_RT = 1;      // 16-row tiles per wave (see RCfg)
@@ -72,11 +73,13 @@ struct RCfg {
   static constexpr int kOffY = NSLOT * STEP;
   static constexpr int kOffB = kOffY + ROWS * PY * 4;
   static constexpr int lds_bytes = kOffB + 2 * F * 4;
+  static constexpr int kOffS = lds_bytes;           // f16x3: the exponents of W1's | W2's output columns, a byte each
+  static constexpr int lds_f16 = kOffS + 2 * F;
   static constexpr int Q = YC / 4;                  // 16-B pieces per chunk row
   static constexpr int SLOTS = NW * 64 / Q;         // target rows reduced at a time
   static constexpr int JG = 2 / RT;                 // column tiles per MFMA group (two accumulators a group)
   static_assert(RT == 1 || RT == 2, "one or two row tiles per wave");
-  static_assert(STEP % (1024 * NW) == 0 && lds_bytes <= 160 * 1024, "ring must tile over the waves and fit");
+  static_assert(STEP % (1024 * NW) == 0 && lds_f16 <= 160 * 1024, "ring must tile over the waves and fit");
 };
 
 __device__ inline float4_t activate(float4_t v, int act) {
@@ -108,6 +111,59 @@ __global__ __launch_bounds__(64) void k_split_wr(const float *__restrict__ W1, c
   dst[64] = lo;
 }
 
+// ---- f16x3 (GWEN_CONTRACT_F16X3): two scaled fp16 images per operand (split.h), scales per W column and per ROW --------
+// |x| as a non-negative int: its order is that of the magnitudes (+Inf above every finite value, NaN above +Inf)
+__device__ inline int abs_bits(float x) { return __builtin_bit_cast(int, x) & 0x7fffffff; }
+// the exponent k of the scale 2^k that brings a maximum magnitude (as abs_bits) to [2^14, 2^15)
+__device__ inline int f16_scale_of(int m) {
+  const int e = m >> 23;
+  return gwen::kF16Top - (e > gwen::kF16Floor ? e : gwen::kF16Floor);
+}
+// v * 2^-(s + c_i): the product of the two scales undone by ONE exact ldexp per element (one rounding, and only where
+// the result is subnormal) -- no intermediate that could leave fp32's range.  c: the 4 columns' exponents + 128 as the
+// bytes of one LDS word (one register a column tile instead of four: the 256-channel epilogues are register-bound)
+__device__ inline float4_t unscale4(float4_t v, int s, const uint8_t *c) {
+  const uint32_t c4 = *reinterpret_cast<const uint32_t *>(c);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) v[i] = __builtin_ldexpf(v[i], 128 - s - (int)__builtin_amdgcn_ubfe(c4, 8 * i, 8));
+  return v;
+}
+__device__ inline void split8_f16(const float4_t a, const float4_t b, int s, bf16x8 &hi, bf16x8 &lo) {
+  const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  gwen::split_f16<8>(x, s, hi, lo);
+}
+
+// k_split_wr for f16x3: one block per (column tile jo, matrix); lane (i, g) holds 8 KS values of W row 16 jo + i (an
+// output column), the four lanes of a row combine their maxima, and the row's scale exponent goes to wexp[m F + o]
+template <int F>
+__global__ __launch_bounds__(64) void k_split_wr_f16(const float *__restrict__ W1, const float *__restrict__ W2,
+                                                     bf16x8 *__restrict__ img, int32_t *__restrict__ wexp) {
+  using C = RCfg<F>;
+  const int lane = threadIdx.x, i = lane & 15, g = lane >> 4, jo = blockIdx.x;
+  const float *wp = (blockIdx.y ? W2 : W1) + (int64_t)(jo * 16 + i) * F + 4 * g;
+  float4_t a[C::KS], b[C::KS];
+  int m = 0;
+#pragma unroll
+  for (int ks = 0; ks < C::KS; ++ks) {
+    a[ks] = *reinterpret_cast<const float4_t *>(wp + 32 * ks);
+    b[ks] = *reinterpret_cast<const float4_t *>(wp + 32 * ks + 16);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m = max(m, max(abs_bits(a[ks][e]), abs_bits(b[ks][e])));
+  }
+  m = max(m, __shfl_xor(m, 16));
+  m = max(m, __shfl_xor(m, 32));
+  const int s = f16_scale_of(m);
+#pragma unroll
+  for (int ks = 0; ks < C::KS; ++ks) {
+    bf16x8 hi, lo;
+    split8_f16(a[ks], b[ks], s, hi, lo);
+    bf16x8 *dst = img + (int64_t)(blockIdx.y * C::KS + ks) * (C::STEP / 16) + (jo * 2) * 64 + lane;
+    dst[0] = hi;
+    dst[64] = lo;
+  }
+  if (g == 0) wexp[blockIdx.y * F + jo * 16 + i] = s;
+}
+
 struct Pass {
   int32_t tile, r0, r1;
   int32_t w0, e0, e1;
@@ -118,11 +174,13 @@ struct Pass {
 // the second one's load the next pass's A rows (2 tiles a step) and, in its first step, the next indices
 // (HID: the activation step also stores the hidden layer, one store per column tile -- every lane, every time: the
 //  counts must be exact)
-template <int F, int RT, int M1, int M2, int RES, bool HID = false>
+// (F16: the first contraction's steps load no residual rows; G2R, f16x3 with a G2 table: they load the G2 rows)
+template <int F, int RT, int M1, int M2, int RES, bool HID = false, bool F16 = false, bool G2R = false>
 struct Vis {
   static constexpr int of(int si) {
     using C = RCfg<F, RT>;
-    if (si < C::KS) return RT * (((M1 != kNone && si < C::GS) ? C::NJ / C::GS : 0) + (RES == kResOther ? 2 : 0));
+    if (si < C::KS)
+      return RT * (((M1 != kNone && si < C::GS) ? C::NJ / C::GS : 0) + ((G2R || (RES == kResOther && !F16)) ? 2 : 0));
     return RT * (2 + (si == C::KS ? (M1 == kIdx ? 1 : 0) + (M2 == kIdx ? 1 : 0) + (HID ? C::NJ : 0) : 0));
   }
 };
@@ -131,7 +189,20 @@ struct Vis {
 // act(acc + G1 + b1), and it is stored as well (`hid`, rows padded to whole passes: the stores are unconditional) --
 //     g_pre1 = (ge W2 + T[dst]) * act'(pre1)  ->  hid ;   g_e = ge + g_pre1 We  ->  out
 // with A = res = ge, "W1" = W2^T, G1 = act'(pre1) row for row, G2 = T gathered by target, "W2" = We^T.
-template <int F, int RT, int M1, int M2, bool SEG, int RES, bool HID = false>
+//
+// F16 (GWEN_CONTRACT_F16X3): the same passes on v_mfma_f32_16x16x32_f16 with two fp16 images per operand (split.h) --
+// three MFMAs and two images per k-step as 3xbf16, so the ring keeps its size.  Scales are powers of two: W per
+// output column (k_split_wr_f16, or the RESIDENT split; exponents in LDS at kOffS), the B operand per ROW -- the
+// A row before the first contraction, the activated hidden row before the second -- from the row's maximum over
+// the lane's F / 4 values and the three other lanes of the row (two cross-lane steps).  Both contractions
+// accumulate from ZERO in the scaled domain and are un-scaled by one ldexp per element (unscale4) before anything
+// else touches them: the gathered addends and the biases are added AFTER it, in fp32's own range, so an addend
+// far above or below A W1^T can not push an intermediate out of range.  Nothing is pre-loaded into the first
+// accumulators then: with a G2 table (G2R) its rows ride along in the first contraction's steps, two column tiles a
+// step into the E registers that step has just split.  The residual is read again from memory in the store (row
+// layout, 256 contiguous bytes per 16 lanes), so E is free after the first contraction: the un-scaling epilogues
+// need those registers at 256 channels (held to the end of the pass, as 3xbf16 does, they spill).
+template <int F, int RT, int M1, int M2, bool SEG, int RES, bool HID = false, bool F16 = false>
 __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k_mlp2r(
     const float *__restrict__ A, const char *__restrict__ img, const float *__restrict__ W1f,
     const float *__restrict__ W2f, const float *__restrict__ G1,
@@ -139,13 +210,17 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
     const float *__restrict__ b1, const float *__restrict__ b2, const float *__restrict__ res,
     float *__restrict__ out, int32_t R, int act, const int32_t *__restrict__ rowptr,
     const int32_t *__restrict__ tile_row, int32_t n_tiles, float *__restrict__ agg, int mean,
-    uint32_t ldb1, uint32_t ldb2, float *__restrict__ hid = nullptr) {
+    uint32_t ldb1, uint32_t ldb2, float *__restrict__ hid = nullptr, const int32_t *__restrict__ wexp = nullptr) {
   using C = RCfg<F, RT>;
   constexpr int NR = RT * C::NJ;                                     // float4 registers per set
-  __shared__ __attribute__((aligned(1024))) char lds[C::lds_bytes];
+  constexpr bool G2R = F16 && M2 != kNone;
+  // (F16 at 64 channels keeps the MFMA-layout A loads and stores of 256 channels: no ROWIO turn through the y tile)
+  constexpr bool ROWIO = C::ROWIO && !F16;
+  __shared__ __attribute__((aligned(1024))) char lds[F16 ? C::lds_f16 : C::lds_bytes];
   const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
   float *ytile = reinterpret_cast<float *>(lds + C::kOffY);
   float *bl = reinterpret_cast<float *>(lds + C::kOffB);           // b1 | b2
+  uint8_t *sx = reinterpret_cast<uint8_t *>(lds + C::kOffS);        // F16: W1's | W2's column exponents + 128
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int mi = lane & 15, g = lane >> 4;
@@ -155,6 +230,10 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
   for (int f = t; f < F; f += C::NW * 64) {
     bl[f] = b1 ? b1[f] : 0.0f;
     bl[F + f] = b2 ? b2[f] : 0.0f;
+    if constexpr (F16 && !C::RESIDENT) {
+      sx[f] = (uint8_t)(wexp[f] + 128);
+      sx[F + f] = (uint8_t)(wexp[F + f] + 128);
+    }
   }
 
   // tiles are dealt so that the blocks of one XCD (blockIdx % 8) walk ONE contiguous eighth of them
@@ -227,7 +306,7 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
     i1n[rt] = i2n[rt] = 0;
 #pragma unroll
     for (int j = 0; j < C::NJ; ++j) {
-      if constexpr (C::ROWIO) {                                      // A rows: the row layout (see pass_body)
+      if constexpr (ROWIO) {                                      // A rows: the row layout (see pass_body)
         int32_t last = (cur.e1 < R ? cur.e1 : R) - 1;
         last = last < 0 ? 0 : last;
         int32_t row = cur.w0 + (wave * RT + rt) * 16 + 4 * (j % 4) + g;
@@ -236,7 +315,7 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
       } else {
         ra[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(A + (int64_t)rr * F + col(j));
       }
-      if constexpr (M2 != kNone)
+      if constexpr (M2 != kNone && !F16)
         rb[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(reinterpret_cast<const char *>(G2) +
                                                                  ((uint32_t)i2[rt] * ldb2 + col(j) * 4u));
       else
@@ -246,11 +325,27 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
   if constexpr (C::RESIDENT) {
     // every block splits the two fp32 matrices into its own LDS image itself (32 KB of L2-resident reads): no
     // pre-split pass, no workspace traffic -- two tiny launches in front of a 100 us kernel cost 4-5 % of it
+    if constexpr (F16) {                                             // f16x3: one thread per W row (output column)
+      for (int r = t; r < 2 * F; r += C::NW * 64) {
+        const float *wr = r < F ? W1f + (int64_t)r * F : W2f + (int64_t)(r - F) * F;
+        int m = 0;
+        for (int k = 0; k < F; k += 4) {
+          const float4_t v = *reinterpret_cast<const float4_t *>(wr + k);
+          m = max(max(m, max(abs_bits(v[0]), abs_bits(v[1]))), max(abs_bits(v[2]), abs_bits(v[3])));
+        }
+        sx[r] = (uint8_t)(f16_scale_of(m) + 128);
+      }
+      __syncthreads();
+    }
     for (int p = wave; p < 2 * C::KS * C::NJ; p += C::NW) {          // fragment pairs (matrix, ks, jo)
       const int m = p / (C::KS * C::NJ), ks = (p / C::NJ) % C::KS, jo = p % C::NJ;
       const float *wp = (m ? W2f : W1f) + (int64_t)(jo * 16 + mi) * F + 32 * ks + 4 * g;
       bf16x8 hi, lo;
-      split8(*reinterpret_cast<const float4_t *>(wp), *reinterpret_cast<const float4_t *>(wp + 16), hi, lo);
+      if constexpr (F16)
+        split8_f16(*reinterpret_cast<const float4_t *>(wp), *reinterpret_cast<const float4_t *>(wp + 16),
+                   (int)sx[m * F + jo * 16 + mi] - 128, hi, lo);
+      else
+        split8(*reinterpret_cast<const float4_t *>(wp), *reinterpret_cast<const float4_t *>(wp + 16), hi, lo);
       char *dst = lds + (m * C::KS + ks) * C::STEP + (jo * 2) * 1024 + lane * 16;
       *reinterpret_cast<bf16x8 *>(dst) = hi;
       *reinterpret_cast<bf16x8 *>(dst + 1024) = lo;
@@ -261,7 +356,22 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
     dma(1, 1);
   }
 
-  using V = Vis<F, RT, M1, M2, RES, HID>;
+  using V = Vis<F, RT, M1, M2, RES, HID, F16, G2R>;
+  // F16: the scale exponent of each of this lane's rows, from the row's F values in X (this lane's F / 4 and the
+  // three other lanes of the row: lanes l, l ^ 16, l ^ 32, l ^ 48)
+  auto row_scale = [&](const float4_t (&X)[NR], int (&s)[RT]) {
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      int m = 0;
+#pragma unroll
+      for (int j = 0; j < C::NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = max(m, abs_bits(X[rt * C::NJ + j][e]));
+      m = max(m, __shfl_xor(m, 16));
+      m = max(m, __shfl_xor(m, 32));
+      s[rt] = f16_scale_of(m);
+    }
+  };
 
   bool last_pass = false;
   // One pass.  E: this pass's A rows (later the residual).  H: pre-loaded with the G2 rows (or zero) -- the first
@@ -310,7 +420,9 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
         }
       }
     };
-    if constexpr (C::ROWIO) to_mfma(E);
+    if constexpr (ROWIO) to_mfma(E);
+    int sa[RT], sh[RT];                                              // F16: the rows' scales (A rows, hidden rows)
+    if constexpr (F16) row_scale(E, sa);
 
     static_for<2 * C::KS>([&](auto ss) {
       constexpr int si = decltype(ss)::value;
@@ -338,7 +450,13 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
         for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
           for (int j = 0; j < C::NJ; ++j) {
-            float4_t v = H[rt * C::NJ + j] + *reinterpret_cast<const float4_t *>(bl + col(j));
+            float4_t v;
+            if constexpr (F16) {                                     // un-scaled first, then the addends
+              v = unscale4(H[rt * C::NJ + j], sa[rt], sx + col(j)) + *reinterpret_cast<const float4_t *>(bl + col(j));
+              if constexpr (G2R) v += E[rt * C::NJ + j];
+            } else {
+              v = H[rt * C::NJ + j] + *reinterpret_cast<const float4_t *>(bl + col(j));
+            }
             if constexpr (HID) {
               v = v * rc[rt * C::NJ + j];
               H[rt * C::NJ + j] = v;
@@ -348,8 +466,11 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
               if constexpr (M1 != kNone) v += rc[rt * C::NJ + j];
               H[rt * C::NJ + j] = activate(v, act);
             }
-            rc[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(bl + F + col(j));
+            if constexpr (F16) asm volatile("" ::: "memory");       // (one column tile's LDS reads at a time)
+            if constexpr (F16) rc[rt * C::NJ + j] = float4_t{0.f, 0.f, 0.f, 0.f};
+            else rc[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(bl + F + col(j));
           }
+        if constexpr (F16) row_scale(H, sh);
       }
       if constexpr (!C::RESIDENT) {
         const int into = slot >= 1 ? slot - 1 : C::NSLOT - 1;        // (slot + 2) % 3
@@ -359,7 +480,10 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
       bf16x8 bh[RT], bo[RT];
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
-        if constexpr (first) {
+        if constexpr (F16) {
+          if constexpr (first) split8_f16(E[rt * C::NJ + 2 * ks], E[rt * C::NJ + 2 * ks + 1], sa[rt], bh[rt], bo[rt]);
+          else split8_f16(H[rt * C::NJ + 2 * ks], H[rt * C::NJ + 2 * ks + 1], sh[rt], bh[rt], bo[rt]);
+        } else if constexpr (first) {
           split8(E[rt * C::NJ + 2 * ks], E[rt * C::NJ + 2 * ks + 1], bh[rt], bo[rt]);
         } else {
           split8(H[rt * C::NJ + 2 * ks], H[rt * C::NJ + 2 * ks + 1], bh[rt], bo[rt]);
@@ -375,7 +499,12 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
             for (int j = si * (C::NJ / C::GS); j < (si + 1) * (C::NJ / C::GS); ++j)
               rc[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(p1 + 64 * j);
           }
-          if constexpr (RES == kResOther) {                          // E's registers are free: the residual rows
+          if constexpr (G2R) {                                       // E's registers are free: the G2 rows
+            const char *p2 = reinterpret_cast<const char *>(G2) + ((uint32_t)i2[rt] * ldb2 + 16u * gs);
+#pragma unroll
+            for (int j = 2 * ks; j < 2 * ks + 2; ++j)
+              E[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(p2 + 64 * j);
+          } else if constexpr (RES == kResOther && !F16) {           // E's registers are free: the residual rows
             int row = prow(rt) < n_rows ? prow(rt) : (n_rows > 0 ? n_rows - 1 : 0);
             const char *pr = reinterpret_cast<const char *>(res + pass_off) + (uint32_t)(row * F * 4 + 16 * gs);
 #pragma unroll
@@ -391,7 +520,7 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
           }
           // the next pass's A rows in the ROW layout (register 4 c + k: row 4 k + lane / 16, columns 64 c + 4 (lane
           // % 16) ..+3 -- 16 lanes read 256 contiguous bytes); the pass turns them into the MFMA layout at its top
-          if constexpr (C::ROWIO) {
+          if constexpr (ROWIO) {
 #pragma unroll
             for (int j = 2 * ks; j < 2 * ks + 2; ++j) {
               int32_t row = fol.w0 + (wave * RT + rt) * 16 + 4 * (j % 4) + gs;
@@ -426,12 +555,37 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
               const bf16x8 wa = kind == 1 ? wl[d] : wh[d];
               const bf16x8 xb = kind == 0 ? bo[rt] : bh[rt];
               const int ix = rt * C::NJ + jo + d;
-              if constexpr (first) H[ix] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, H[ix], 0, 0, 0);
-              else rc[ix] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, rc[ix], 0, 0, 0);
+              if constexpr (F16) {
+                const gwen::f16x8 wf = __builtin_bit_cast(gwen::f16x8, wa), xf = __builtin_bit_cast(gwen::f16x8, xb);
+                if constexpr (first) H[ix] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xf, H[ix], 0, 0, 0);
+                else rc[ix] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, xf, rc[ix], 0, 0, 0);
+              } else if constexpr (first) {
+                H[ix] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, H[ix], 0, 0, 0);
+              } else {
+                rc[ix] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, rc[ix], 0, 0, 0);
+              }
             }
       }
       slot = slot + 1 == C::NSLOT ? 0 : slot + 1;
     });
+    // F16: y = the second contraction un-scaled, + b2 -- column tile by column tile as the store below reaches it (all
+    // at once, with the residual and the next pass's A rows live, the 256-channel kernel spills)
+    auto finish_y = [&](int rt, int j) {
+      if constexpr (F16)
+        rc[rt * C::NJ + j] = unscale4(rc[rt * C::NJ + j], sh[rt], sx + F + col(j)) +
+                             *reinterpret_cast<const float4_t *>(bl + F + col(j));
+    };
+    if constexpr (F16) {
+      if (!out) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+          for (int j = 0; j < C::NJ; ++j) {
+            finish_y(rt, j);
+            asm volatile("" ::: "memory");
+          }
+      }
+    }
 
     // ---- out = res + y stored from registers; E's registers then take the next pass's G2 rows (its first
     // contraction accumulates onto them).  (Issued in four parts inside the aggregation's chunks instead:
@@ -445,8 +599,12 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
           char *po = reinterpret_cast<char *>(out + pass_off) + (uint32_t)(prow(rt) * F * 4 + 16 * gs) + 0 * ps;
 #pragma unroll
           for (int j = 0; j < C::NJ; ++j) {
+            finish_y(rt, j);
             float4_t o = rc[rt * C::NJ + j];
-            if constexpr (RES != kResNone) o += E[rt * C::NJ + j];
+            if constexpr (RES != kResNone && !F16) o += E[rt * C::NJ + j];
+            if constexpr (RES != kResNone && F16)
+              o += *reinterpret_cast<const float4_t *>(reinterpret_cast<const char *>(res + pass_off) +
+                                                       (uint32_t)(prow(rt) * F * 4 + 16 * gs) + 64 * j);
             *reinterpret_cast<float4_t *>(po + 64 * j) = o;
           }
         }
@@ -455,18 +613,31 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
         float *yown = ytile + (wave * RT + rt) * 16 * C::PY;
         const int wrow = (wave * RT + rt) * 16;
         float *po = out + pass_off + (int64_t)(wrow + gs) * F + 4 * ps;       // ps: lane % 16 here
+        // (F16) row `row` of the pass in `res`, clamped to the pass's last valid row (a pass without rows: the launch's
+        // last row -- never past the array)
+        auto res_row = [&](int row) {
+          int32_t rr = cur.w0 + row;
+          const int32_t last = (cur.e1 < R ? cur.e1 : R) - 1;
+          rr = rr < last ? rr : last;
+          return res + (int64_t)(rr < 0 ? 0 : rr) * F;
+        };
 #pragma unroll
         for (int c = 0; c < C::NCH; ++c) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
+            finish_y(rt, 4 * c + j);
             float4_t o = rc[rt * C::NJ + 4 * c + j];
-            if constexpr (RES != kResNone) o += E[rt * C::NJ + 4 * c + j];
+            if constexpr (RES != kResNone && !F16) o += E[rt * C::NJ + 4 * c + j];
             *reinterpret_cast<float4_t *>(yown + ps * C::PY + 16 * j + 4 * gs) = o;
           }
-          if constexpr (C::ROWIO) {
+          if constexpr (ROWIO) {
             float4_t v[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4_t *>(yown + (4 * k + gs) * C::PY + 4 * ps);
+            if constexpr (RES != kResNone && F16) {                  // the residual, read again in the row layout
+#pragma unroll
+              for (int k = 0; k < 4; ++k) v[k] += *reinterpret_cast<const float4_t *>(res_row(wrow + 4 * k + gs) + 64 * c + 4 * ps);
+            }
             if (wrow + 16 <= n_rows) {                                 // the wave's 16 rows all exist: no per-row test
 #pragma unroll
               for (int k = 0; k < 4; ++k) *reinterpret_cast<float4_t *>(po + (int64_t)(4 * k) * F + 64 * c) = v[k];
@@ -478,7 +649,9 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
           } else {                                                     // 256 channels: one piece at a time
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-              const float4_t v = *reinterpret_cast<const float4_t *>(yown + (4 * k + gs) * C::PY + 4 * ps);
+              float4_t v = *reinterpret_cast<const float4_t *>(yown + (4 * k + gs) * C::PY + 4 * ps);
+              if constexpr (RES != kResNone && F16)
+                v += *reinterpret_cast<const float4_t *>(res_row(wrow + 4 * k + gs) + 64 * c + 4 * ps);
               if (wrow + 4 * k + gs < n_rows) *reinterpret_cast<float4_t *>(po + (int64_t)(4 * k) * F + 64 * c) = v;
               asm volatile("" ::: "memory");
             }
@@ -488,7 +661,7 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
       const char *p2 = reinterpret_cast<const char *>(G2) + ((uint32_t)i2n[rt] * ldb2 + 16u * gs);
 #pragma unroll
       for (int j = 0; j < C::NJ; ++j) {
-        if constexpr (M2 != kNone)
+        if constexpr (M2 != kNone && !F16)
           E[rt * C::NJ + j] = *reinterpret_cast<const float4_t *>(p2 + 64 * j);
         else
           E[rt * C::NJ + j] = float4_t{0.f, 0.f, 0.f, 0.f};
@@ -557,7 +730,23 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
   if constexpr (!C::RESIDENT) wait_vm<0>();                          // the DMAs issued past the last chunk used
 }
 
-template <int F, int M1, int M2>
+// the workspace at 256 channels: the fragment images of both matrices (2 x (hi, lo) x F^2 bf16), then -- f16x3 -- the
+// exponents of their output columns (2 F int32)
+template <int F>
+constexpr int64_t rows_ws_bytes(bool f16) { return (int64_t)2 * 2 * F * F * 2 + (f16 ? 2 * F * 4 : 0); }
+
+template <int F, bool F16>
+const int32_t *split_weights(const float *W1, const float *W2, void *workspace, hipStream_t st) {
+  using C = RCfg<F, K6R_RT>;
+  bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);               // W1's k-steps, then W2's
+  int32_t *wexp = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + rows_ws_bytes<F>(false));
+  if constexpr (C::RESIDENT) return nullptr;                         // 64 channels: split inside the kernel
+  if constexpr (F16) k_split_wr_f16<F><<<dim3(C::NJ, 2), 64, 0, st>>>(W1, W2, img, wexp);
+  else k_split_wr<F><<<dim3(C::NJ * C::KS, 2), 64, 0, st>>>(W1, W2, img);
+  return F16 ? wexp : nullptr;
+}
+
+template <int F, int M1, int M2, bool F16>
 int launch_rows(const float *A, const float *W1, const float *G1, const int32_t *idx1, const float *G2,
                 const int32_t *idx2, const float *b1, const float *W2, const float *b2, const float *res,
                 float *out, int64_t R, int act, const int32_t *rowptr, const int32_t *tile_row,
@@ -565,11 +754,9 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
                 hipStream_t st) {
   using C = RCfg<F, K6R_RT>;
   const bool seg = agg != nullptr;
-  bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);               // W1's k-steps, then W2's
-  if constexpr (!C::RESIDENT) {                                      // 64 channels: split inside the kernel
-    k_split_wr<F><<<dim3(C::NJ * C::KS, 2), 64, 0, st>>>(W1, W2, img);
-    GWEN_LAUNCH_CHECK();
-  }
+  bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);
+  const int32_t *wexp = split_weights<F, F16>(W1, W2, workspace, st);
+  if constexpr (!C::RESIDENT) GWEN_LAUNCH_CHECK();
   const int64_t tiles = seg ? n_tiles : (R + C::ROWS - 1) / C::ROWS;
   static int cus = 0;
   if (cus == 0) {
@@ -583,9 +770,9 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
   const int r = !res ? kResNone : (res == A ? kResA : kResOther);
   const char *im = reinterpret_cast<const char *>(img);
 #define GWEN_R(SEGV, RV)                                                                              \
-  k_mlp2r<F, K6R_RT, M1, M2, SEGV, RV><<<(unsigned)blocks, C::NW * 64, 0, st>>>(                              \
+  k_mlp2r<F, K6R_RT, M1, M2, SEGV, RV, false, F16><<<(unsigned)blocks, C::NW * 64, 0, st>>>(                 \
       A, im, W1, W2, G1, idx1, G2, idx2, b1, b2, res, out, (int32_t)R, act, SEGV ? rowptr : nullptr,  \
-      SEGV ? tile_row : nullptr, (int32_t)tiles, SEGV ? agg : nullptr, SEGV ? mean : 0, ldb1, ldb2)
+      SEGV ? tile_row : nullptr, (int32_t)tiles, SEGV ? agg : nullptr, SEGV ? mean : 0, ldb1, ldb2, nullptr, wexp)
   if (seg) {
     if (r == kResNone) GWEN_R(true, kResNone); else if (r == kResA) GWEN_R(true, kResA); else GWEN_R(true, kResOther);
   } else {
@@ -597,15 +784,13 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
 }
 
 // the block's edge-level backward (see k_mlp2r, HID): hid = (ge W2t^T + T[dst]) * d1 ; out = ge + hid Wet^T
-template <int F>
+template <int F, bool F16>
 int launch_rows_bwd(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
                     const float *Wet, float *hid, float *out, int64_t R, void *workspace, uint32_t ldbT, hipStream_t st) {
   using C = RCfg<F, K6R_RT>;
   bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);
-  if constexpr (!C::RESIDENT) {
-    k_split_wr<F><<<dim3(C::NJ * C::KS, 2), 64, 0, st>>>(W2t, Wet, img);
-    GWEN_LAUNCH_CHECK();
-  }
+  const int32_t *wexp = split_weights<F, F16>(W2t, Wet, workspace, st);
+  if constexpr (!C::RESIDENT) GWEN_LAUNCH_CHECK();
   const int64_t tiles = (R + C::ROWS - 1) / C::ROWS;
   static int cus = 0;
   if (cus == 0) {
@@ -616,9 +801,9 @@ int launch_rows_bwd(const float *ge, const float *W2t, const float *d1, const fl
   }
   int64_t blocks = (int64_t)cus * (C::RESIDENT ? 2 : 1);
   if (blocks > tiles) blocks = tiles;
-  k_mlp2r<F, K6R_RT, kSelf, kIdx, false, kResA, true><<<(unsigned)blocks, C::NW * 64, 0, st>>>(
+  k_mlp2r<F, K6R_RT, kSelf, kIdx, false, kResA, true, F16><<<(unsigned)blocks, C::NW * 64, 0, st>>>(
       ge, reinterpret_cast<const char *>(img), W2t, Wet, d1, nullptr, T, dst, nullptr, nullptr, ge, out, (int32_t)R,
-      GWEN_ACT_NONE, nullptr, nullptr, (int32_t)tiles, nullptr, 0, (uint32_t)(F * 4), ldbT, hid);
+      GWEN_ACT_NONE, nullptr, nullptr, (int32_t)tiles, nullptr, 0, (uint32_t)(F * 4), ldbT, hid, wexp);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
 }
@@ -626,27 +811,38 @@ int launch_rows_bwd(const float *ge, const float *W2t, const float *d1, const fl
 }  // namespace
 
 int gwen_mlp2_rows_f() { return RCfg<256, K6R_RT>::ROWS; }   // the same at every width this kernel takes
+int64_t gwen_mlp2_rows_ws_bytes(int F, int f16) {
+  return F == 256 ? rows_ws_bytes<256>(f16 != 0) : 0;
+}
 
-int gwen_mlp2_rows_bwd_launch(int F, const float *ge, const float *W2t, const float *d1, const float *T,
+int gwen_mlp2_rows_bwd_launch(int F, int f16, const float *ge, const float *W2t, const float *d1, const float *T,
                               const int32_t *dst, const float *Wet, float *hid, float *out, int64_t R, void *workspace,
                               uint32_t ldbT, hipStream_t st) {
-  if (F == 64) return launch_rows_bwd<64>(ge, W2t, d1, T, dst, Wet, hid, out, R, workspace, ldbT, st);
-  if (F == 256) return launch_rows_bwd<256>(ge, W2t, d1, T, dst, Wet, hid, out, R, workspace, ldbT, st);
+#define GWEN_B(FF, H)                                                                                        \
+  if (F == FF && (f16 != 0) == H) return launch_rows_bwd<FF, H>(ge, W2t, d1, T, dst, Wet, hid, out, R, workspace, ldbT, st)
+  GWEN_B(64, false); GWEN_B(256, false); GWEN_B(64, true); GWEN_B(256, true);
+#undef GWEN_B
   return GWEN_EINVAL;
 }
 
 // interact.hip's dispatch for F = 256 (pointers validated there); m1 / m2 as interact.hip's kNone / kSelf / kIdx
-int gwen_mlp2_rows_launch(int F, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
+int gwen_mlp2_rows_launch(int F, int f16, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
                           const float *G2, const int32_t *idx2, const float *b1, const float *W2,
                           const float *b2, const float *res, float *out, int64_t R, int act,
                           const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg,
                           int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st) {
-#define GWEN_MODE(FF, A1, A2)                                                                         \
-  if (F == FF && m1 == A1 && m2 == A2)                                                                \
-    return launch_rows<FF, A1, A2>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr,   \
-                                   tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st)
-  GWEN_MODE(256, kNone, kNone); GWEN_MODE(256, kSelf, kNone); GWEN_MODE(256, kIdx, kNone); GWEN_MODE(256, kIdx, kIdx);
-  GWEN_MODE(64, kNone, kNone); GWEN_MODE(64, kSelf, kNone); GWEN_MODE(64, kIdx, kNone); GWEN_MODE(64, kIdx, kIdx);
+#define GWEN_MODE(FF, A1, A2, H)                                                                      \
+  if (F == FF && m1 == A1 && m2 == A2 && (f16 != 0) == H)                                             \
+    return launch_rows<FF, A1, A2, H>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
+                                      tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st)
+  GWEN_MODE(256, kNone, kNone, false); GWEN_MODE(256, kSelf, kNone, false); GWEN_MODE(256, kIdx, kNone, false);
+  GWEN_MODE(256, kIdx, kIdx, false);
+  GWEN_MODE(64, kNone, kNone, false); GWEN_MODE(64, kSelf, kNone, false); GWEN_MODE(64, kIdx, kNone, false);
+  GWEN_MODE(64, kIdx, kIdx, false);
+  GWEN_MODE(256, kNone, kNone, true); GWEN_MODE(256, kSelf, kNone, true); GWEN_MODE(256, kIdx, kNone, true);
+  GWEN_MODE(256, kIdx, kIdx, true);
+  GWEN_MODE(64, kNone, kNone, true); GWEN_MODE(64, kSelf, kNone, true); GWEN_MODE(64, kIdx, kNone, true);
+  GWEN_MODE(64, kIdx, kIdx, true);
 #undef GWEN_MODE
   return GWEN_EINVAL;
 }

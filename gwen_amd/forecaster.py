@@ -67,8 +67,13 @@ class ForecastGraphs:
 
 
 class InteractionForecaster(nn.Module):
+    """``precision`` ("3xbf16", the default, or "f16x3": fp32-class) applies to every contraction of the model -- the
+    blocks (``InteractionNet.precision``) and the embedding / read-out ``Linear``s; ``set_precision`` changes it.  Not
+    part of ``state_dict()``.  A captured step (``GraphedStep``, ``ensemble_forecast``) keeps the precision it was
+    captured with."""
+
     def __init__(self, grid_channels: int, hidden: int, steps: int = 4, activation: str = "silu",
-                 aggr: str = "sum"):
+                 aggr: str = "sum", precision: str = "3xbf16"):
         super().__init__()
         self.grid_channels, self.hidden, self.steps = grid_channels, hidden, steps
         self.grid_embed = nn.Linear(grid_channels, hidden)
@@ -80,6 +85,14 @@ class InteractionForecaster(nn.Module):
         self.processor = nn.ModuleList([InteractionNet(hidden, activation, aggr) for _ in range(steps)])
         self.decoder = InteractionNet(hidden, activation, aggr)
         self.readout = nn.Linear(hidden, grid_channels)
+        self.set_precision(precision)
+
+    def set_precision(self, p: str) -> "InteractionForecaster":
+        """The contraction of the encoder, the processors, the decoder and the six embedding / read-out layers."""
+        for net in (self.encoder, *self.processor, self.decoder):
+            net.precision = p                                # (validates p: "3xbf16" or "f16x3")
+        self.precision = p
+        return self
 
     @staticmethod
     def prepare(mesh: Mesh, device) -> ForecastGraphs:
@@ -95,13 +108,16 @@ class InteractionForecaster(nn.Module):
         fs = [g.sort_edges(torch.from_numpy(f).to(device)) for g, f in zip(gs, feats)]
         return ForecastGraphs(*gs, torch.from_numpy(mesh.pos.astype(np.float32)).to(device), *fs)
 
-    @staticmethod
-    def _lin(x: Tensor, m: nn.Linear) -> Tensor:
-        """K3 (bf16x3, as the blocks around it); with autograd when gradients are needed (ops.LinearFunction:
-        the backward runs on K3 and the gradient reductions too)."""
+    def _lin(self, x: Tensor, m: nn.Linear) -> Tensor:
+        """K3 on the model's precision, as the blocks around it ("3xbf16": bf16x3; "f16x3": K3's fp32-class split);
+        with autograd when gradients are needed (ops.LinearFunction: the backward runs on K3 and the gradient
+        reductions too)."""
+        prec = self.__dict__.get("precision", "3xbf16")        # (a model pickled before the setting existed)
         if torch.is_grad_enabled() and (x.requires_grad or m.weight.requires_grad):
-            return ops.linear_autograd(x, m.weight, m.bias, contract="3xbf16")
-        return ops.linear(x, m.weight, m.bias, exact=False)
+            return ops.linear_autograd(x, m.weight, m.bias, contract=prec)
+        if prec == "3xbf16":
+            return ops.linear(x, m.weight, m.bias, exact=False)
+        return ops.linear(x, m.weight, m.bias, contract=prec)
 
     def _static(self, graphs: ForecastGraphs):
         lin = self._lin

@@ -151,12 +151,25 @@ def mlp2_supported(channels: int) -> bool:
     return bool(_lib.lib().gwen_mlp2_supported(channels))
 
 
+# K6's precision tiers (include/gwen_hip.h, gwen_mlp2_contract_f32): "3xbf16" -- two bf16 images, ~17 bits per product
+# (the default); "f16x3" -- fp32-class, two power-of-two-scaled fp16 images (W per output column, rows per row)
+MLP2_CONTRACTS = {"3xbf16": _lib.CONTRACT_BF16X3, "f16x3": _lib.CONTRACT_F16X3}
+
+
+def _mlp2_contract(contract: str) -> int:
+    if contract not in MLP2_CONTRACTS:
+        raise ValueError(f"K6 contract must be one of {sorted(MLP2_CONTRACTS)}; got {contract!r}")
+    return MLP2_CONTRACTS[contract]
+
+
 def mlp2(a: Tensor, w1: Tensor, w2: Tensor, b2: Optional[Tensor] = None, *,
          g1: Optional[Tensor] = None, idx1: Optional[Tensor] = None, g2: Optional[Tensor] = None,
          idx2: Optional[Tensor] = None, b1: Optional[Tensor] = None, res: Optional[Tensor] = None,
          act: str = "silu", graph: Optional[EdgeGraph] = None, mean: bool = False,
-         want_out: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
-    """K6 (gwen_mlp2_f32): returns (out, agg); ``agg`` only with ``graph`` (rows = its stored edges)."""
+         want_out: bool = True, contract: str = "3xbf16") -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """K6 (gwen_mlp2_contract_f32): returns (out, agg); ``agg`` only with ``graph`` (rows = its stored edges).
+    ``contract``: "3xbf16" (gwen_mlp2_f32's split, the default) or "f16x3" (fp32-class)."""
+    code = _mlp2_contract(contract)
     f = a.size(-1)
     if a.dim() != 2 or not mlp2_supported(f):
         raise ValueError(f"K6 needs [rows, F] with F in (32, 64, 128, 256); got {tuple(a.shape)}")
@@ -191,18 +204,18 @@ def mlp2(a: Tensor, w1: Tensor, w2: Tensor, b2: Optional[Tensor] = None, *,
             raise ValueError("A must hold one row per stored edge of the graph")
         agg = torch.empty(graph.num_dst, f, dtype=torch.float32, device=dev)
         tile_row, n_tiles = graph.tiles(int(_lib.lib().gwen_mlp2_rows(f)))
-    nws = int(_lib.lib().gwen_mlp2_workspace_bytes(f))
+    nws = int(_lib.lib().gwen_mlp2_contract_workspace_bytes(f, code))
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws > 0 else None
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_mlp2_f32(
+        rc = _lib.lib().gwen_mlp2_contract_f32(
             _ptr(a), _ptr(w1), _ptr(g1), _ptr(idx1), 0 if g1 is None else g1.size(0),
             0 if g1 is None else g1.stride(0), _ptr(g2), _ptr(idx2), 0 if g2 is None else g2.size(0),
             0 if g2 is None else g2.stride(0), _ptr(b1), _ptr(w2), _ptr(b2),
             _ptr(res), _ptr(out), rows, f, _ACT[act],
             _ptr(graph.rowptr) if graph else None, _ptr(tile_row), n_tiles, _ptr(agg),
-            graph.num_dst if graph else 0, int(mean),
+            graph.num_dst if graph else 0, int(mean), code,
             _ptr(ws), nws, _stream(dev))
-    _lib.check(rc, "gwen_mlp2_f32")
+    _lib.check(rc, "gwen_mlp2_contract_f32")
     return out, agg
 
 
@@ -214,13 +227,18 @@ def _mlp(fin: int, f: int, act: str) -> nn.Sequential:
 class InteractionNet(nn.Module):
     """``forward(x_src, x_dst, e, graph) -> (x_dst', e')``; parameters ``edge_mlp.{0,2}.{weight,bias}``
     ([F,3F] / [F,F]) and ``node_mlp.{0,2}.{weight,bias}`` ([F,2F] / [F,F]).  Forward on K6; when gradients are
-    needed the backward runs on libgwen_hip.so as well (``_InteractionNetFunction``: atomic-free, reproducible)."""
+    needed the backward runs on libgwen_hip.so as well (``_InteractionNetFunction``: atomic-free, reproducible).
 
-    def __init__(self, channels: int, activation: str = "silu", aggr: str = "sum"):
+    ``precision`` ("3xbf16", the default, or "f16x3": fp32-class) governs everything the block contracts: the node
+    projections (K3: "f16x3" runs its fp32-class split, bf16x6), both K6 launches, and every product and weight
+    gradient of the backward.  A setting, not a parameter: it is not in ``state_dict()`` (pickling keeps it)."""
+
+    def __init__(self, channels: int, activation: str = "silu", aggr: str = "sum", precision: str = "3xbf16"):
         super().__init__()
         if activation not in _ACT or aggr not in ("sum", "mean"):
             raise ValueError("activation in (none, relu, silu), aggr in (sum, mean)")
         self.channels, self.activation, self.aggr = channels, activation, aggr
+        self.precision = precision
         self.edge_mlp = _mlp(3 * channels, channels, activation)
         self.node_mlp = _mlp(2 * channels, channels, activation)
         self._blocks = None          # contiguous [F,F] blocks of the two first layers + their versions
@@ -240,6 +258,15 @@ class InteractionNet(nn.Module):
                 bn = torch.cat([torch.zeros_like(l1.bias), l1.bias, l3.bias]).contiguous()
             self._blocks = (key, (we, wa, wn, bn))
         return self._blocks[1]
+
+    @property
+    def precision(self) -> str:
+        return self.__dict__.get("_precision", "3xbf16")          # (a module pickled before the setting existed)
+
+    @precision.setter
+    def precision(self, p: str) -> None:
+        _mlp2_contract(p)
+        self._precision = p
 
     def __getstate__(self):          # the cache is derived data: keep modules picklable and small
         state = self.__dict__.copy()
@@ -261,24 +288,29 @@ class InteractionNet(nn.Module):
                     update_edges: bool = True, return_agg: bool = False):
         f = self.channels
         we, wa, wn, bn = self._weight_blocks()
+        prec = self.precision
+        # (the default keeps exact=False: the launch it has always been; "f16x3" -> K3's fp32-class split)
+        lin = (lambda x, w, b: ops.linear(x, w, b, exact=False)) if prec == "3xbf16" else \
+            (lambda x, w, b: ops.linear(x, w, b, contract=prec))                                # noqa: E731
         if x_src is x_dst:                                   # mesh -> mesh: one launch, [N, 3F]
-            p = ops.linear(x_dst, wn, bn, exact=False)
+            p = lin(x_dst, wn, bn)
             ps, pd, q = p[:, :f], p[:, f:2 * f], p[:, 2 * f:]
         else:                                                # bipartite: sources apart
-            ps = ops.linear(x_src, wn[:f], None, exact=False)
-            p = ops.linear(x_dst, wn[f:], bn[f:], exact=False)
+            ps = lin(x_src, wn[:f], None)
+            p = lin(x_dst, wn[f:], bn[f:])
             pd, q = p[:, :f], p[:, f:]
         e_new, agg = mlp2(e, we, self.edge_mlp[2].weight, self.edge_mlp[2].bias,
                           g1=ps, idx1=graph.src, g2=pd, idx2=graph.dst, res=e, act=self.activation,
-                          graph=graph, mean=self.aggr == "mean", want_out=update_edges)
+                          graph=graph, mean=self.aggr == "mean", want_out=update_edges, contract=prec)
         x_new, _ = mlp2(agg, wa, self.node_mlp[2].weight, self.node_mlp[2].bias, g1=q,
-                        res=x_dst, act=self.activation)
+                        res=x_dst, act=self.activation, contract=prec)
         # (training keeps the aggregate and the node projections: node-sized arrays this pass makes anyway)
         return (x_new, e_new, agg, p, None if x_src is x_dst else ps) if return_agg else (x_new, e_new)
 
 
 # ---- pieces of the backward (csrc/interact_bwd.hip + K2 / K3 / the gradient reductions) -------------------------
-_BWD_CONTRACT = "3xbf16"          # the block's forward (K6) contracts on the bf16x3 split; so does its backward
+# (the backward contracts on the block's own precision, InteractionNet.precision: "3xbf16" or "f16x3" -- the latter is
+#  K6's scaled fp16 split in the fused edge launch and the fp32-class split, bf16x6, of K3 and the weight gradients)
 
 
 def _act_pair(a: Tensor, act: str, g1: Optional[Tensor] = None, idx1: Optional[Tensor] = None,
@@ -328,20 +360,22 @@ def _ew(op: int, a: Tensor, b: Tensor) -> Tensor:
     return a
 
 
-def _edge_backward(ge: Tensor, w2t: Tensor, d1: Tensor, t: Tensor, dst: Tensor, wet: Tensor) -> Tuple[Tensor, Tensor]:
-    """gwen_mlp2_bwd_f32: (g_pre1, g_e) = ((ge W2 + T[dst]) * d1, ge + g_pre1 We) in one launch of K6's kernel."""
+def _edge_backward(ge: Tensor, w2t: Tensor, d1: Tensor, t: Tensor, dst: Tensor, wet: Tensor,
+                   contract: str = "3xbf16") -> Tuple[Tensor, Tensor]:
+    """gwen_mlp2_bwd_contract_f32: (g_pre1, g_e) = ((ge W2 + T[dst]) * d1, ge + g_pre1 We) in one launch of K6's kernel."""
+    code = _mlp2_contract(contract)
     rows, f = ge.shape
     L = _lib.lib()
     dev = ge.device
     padded = int(L.gwen_mlp2_bwd_rows(rows))
     g_pre1 = torch.empty(padded, f, dtype=torch.float32, device=dev)        # whole passes: the kernel stores every lane
     g_e = torch.empty_like(ge)
-    nws = int(L.gwen_mlp2_workspace_bytes(f))
+    nws = int(L.gwen_mlp2_contract_workspace_bytes(f, code))
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws > 0 else None
     with torch.cuda.device(dev):
-        rc = L.gwen_mlp2_bwd_f32(_ptr(ge), _ptr(w2t), _ptr(d1), _ptr(t), _ptr(dst), t.size(0), t.stride(0), _ptr(wet),
-                                 _ptr(g_pre1), _ptr(g_e), rows, f, _ptr(ws), nws, _stream(dev))
-    _lib.check(rc, "gwen_mlp2_bwd_f32")
+        rc = L.gwen_mlp2_bwd_contract_f32(_ptr(ge), _ptr(w2t), _ptr(d1), _ptr(t), _ptr(dst), t.size(0), t.stride(0),
+                                          _ptr(wet), _ptr(g_pre1), _ptr(g_e), rows, f, code, _ptr(ws), nws, _stream(dev))
+    _lib.check(rc, "gwen_mlp2_bwd_contract_f32")
     return g_pre1[:rows], g_e
 
 
@@ -390,8 +424,9 @@ class _InteractionNetFunction(torch.autograd.Function):
         net, g, same = ctx.net, ctx.graph, ctx.same
         f, act, mean = net.channels, net.activation, net.aggr == "mean"
         n_src, n_dst = g.num_src, g.num_dst
+        prec = net.precision
         with torch.no_grad():
-            lin = lambda x, w, b=None: ops.linear(x, w, b, contract=_BWD_CONTRACT)          # noqa: E731
+            lin = lambda x, w, b=None: ops.linear(x, w, b, contract=prec)                   # noqa: E731
             x_src, x_dst, e = x_src.detach().contiguous(), x_dst.detach().contiguous(), e.detach().contiguous()
             gx = gx.contiguous()
             has_ge = bool(ctx.update_edges and ge is not None and ge.numel() > 0)
@@ -421,8 +456,8 @@ class _InteractionNetFunction(torch.autograd.Function):
             # (every weight / bias gradient: stage 1 launched where its operands are live, the fixed-order finishes of
             #  all of them in ONE launch at the end -- ops.GradBatch)
             gb = ops.GradBatch()
-            gw = lambda a, b_: gb.grad_weight(a, b_, _BWD_CONTRACT)                          # noqa: E731
-            gwb = lambda a, b_: gb.grad_weight_bias(a, b_, _BWD_CONTRACT)                    # noqa: E731
+            gw = lambda a, b_: gb.grad_weight(a, b_, prec)                                   # noqa: E731
+            gwb = lambda a, b_: gb.grad_weight_bias(a, b_, prec)                             # noqa: E731
             g_w4, g_b4 = gwb(gx, h3)                                   # (weight gradient + column sums of the same rows)
             g_pre3 = _ew(_lib.EW_MUL, lin(gx, w4t), d3)
             del h3, d3
@@ -441,7 +476,7 @@ class _InteractionNetFunction(torch.autograd.Function):
                 #  zero array still replaces four launches and nine passes, and ge's own gradient terms drop out)
                 g_agg_s = g_agg * g.inv_degree().view(-1, 1) if mean else g_agg
                 g_pre1, g_e = _edge_backward(ge if has_ge else torch.zeros_like(e), w2t, d1,
-                                             lin(g_agg_s, w2t), g.dst, wet)
+                                             lin(g_agg_s, w2t), g.dst, wet, prec)
                 del d1
                 g_b2 = gb.grad_bias(g_agg_s * g.degree())
                 g_w2 = gw(g_agg_s, hagg)

@@ -493,6 +493,23 @@ int gwen_gnn_backward_f32(const struct gwen_graph *graph_t, const struct gwen_la
  *   workspace: gwen_mlp2_workspace_bytes(F) bytes, 16-byte aligned (GWEN_ENOSPACE if smaller): only F = 256
  *   needs one -- its weights are streamed from pre-split bf16 fragment images (F = 64 splits them in-kernel).
  *
+ * gwen_mlp2_contract_f32 / gwen_mlp2_bwd_contract_f32: the same launches with a choice of contraction (contract, a
+ *   GWEN_CONTRACT_* code; gwen_mlp2_contract_supported(F, contract)): GWEN_CONTRACT_BF16X3 is gwen_mlp2_f32 /
+ *   gwen_mlp2_bwd_f32 bit for bit (they forward to it); GWEN_CONTRACT_F16X3 is "fp32-class on the kernel's own split",
+ *   as on gwen_layer_desc: two fp16 images per operand at the same three MFMAs per k-step, both operands scaled by
+ *   exact powers of two -- W per OUTPUT COLUMN, the A rows and the activated hidden rows per ROW (a row's result never
+ *   depends on the other rows of a launch: a member of a block-diagonal batched launch is bitwise the member alone).
+ *   Each contraction accumulates from zero and is un-scaled by ONE ldexp per element (the two exponents summed) before
+ *   G1 / G2 / b1 / b2 / res are added, so an addend far larger or smaller than A W1^T puts no intermediate out of
+ *   range.  Accuracy: ~2^-24 relative per product, like bf16x6; elements more than 2^17 below their row's (or W
+ *   column's) maximum fall into fp16's subnormal range and keep an ABSOLUTE accuracy of ~2^-40 of that maximum, and
+ *   maxima below 2^-107 are scaled as 2^-107 (rows of magnitude 2^-107 .. 2^127 keep full precision; an all-zero
+ *   row contributes an exact 0 to A W1^T).  A row holding +-Inf or NaN gets NaN / Inf in every column of that row's outputs (the lo
+ *   image of an infinite value is Inf - Inf) and, with agg, in its target's sum; every other row is untouched.  A
+ *   non-finite W entry spoils its output column for every row, as in fp32.  Supported: BF16X3 and F16X3 at every F
+ *   of gwen_mlp2_supported (the backward: F in {64, 256}); GWEN_CONTRACT_F32 / BF16X6 return GWEN_EINVAL.
+ *   workspace: gwen_mlp2_contract_workspace_bytes(F, contract) (F = 256: the images + 2 F int32 column exponents).
+ *
  * gwen_edge_tiles: row-aligned tiling of a CSR's entries.  tile c owns the target rows whose first
  *   entry lies in [cT, (c+1)T); n_tiles = gwen_edge_tiles_count(E, T) = max(1, ceil(E/T)); T <= 128.
  *   T = gwen_mlp2_rows(F) - (max row length - 1) (at least 1) keeps each tile a single pass of the
@@ -515,6 +532,15 @@ int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_
                   int64_t R, int64_t F, int act, const int32_t *rowptr, const int32_t *tile_row,
                   int64_t n_tiles, float *agg, int64_t N_agg, int mean, void *workspace,
                   size_t workspace_bytes, gwen_stream_t stream);
+int gwen_mlp2_contract_supported(int64_t F, int contract);   /* BF16X3 and F16X3 at F in {32, 64, 128, 256} */
+int64_t gwen_mlp2_contract_workspace_bytes(int64_t F, int contract);
+int gwen_mlp2_contract_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+                           int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
+                           int64_t G2_rows, int64_t ldg2,
+                           const float *b1, const float *W2, const float *b2, const float *res, float *out,
+                           int64_t R, int64_t F, int act, const int32_t *rowptr, const int32_t *tile_row,
+                           int64_t n_tiles, float *agg, int64_t N_agg, int mean, int contract, void *workspace,
+                           size_t workspace_bytes, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K6^T  pieces of the InteractionNet block's BACKWARD (build-defined like K6; serves the training step of the
@@ -539,6 +565,9 @@ int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_
  *                        output column); d1 = act'(pre1) [R, F]; T [T_rows, F] with row stride ldT.  g_pre1 has
  *                        gwen_mlp2_bwd_rows(R) rows (R rounded up to whole passes: the kernel stores every lane), g_e
  *                        [R, F] may be ge itself.  workspace as gwen_mlp2_f32.  3xbf16 contractions, as K6.
+ *   gwen_mlp2_bwd_contract_f32: the same with a contract (BF16X3 = gwen_mlp2_bwd_f32 bit for bit; F16X3 as
+ *                        gwen_mlp2_contract_f32 -- T[dst] is added after the first contraction is un-scaled);
+ *                        workspace: gwen_mlp2_contract_workspace_bytes(F, contract).
  * ------------------------------------------------------------------------------------------- */
 #define GWEN_EW_MUL 0
 #define GWEN_EW_ADD 1
@@ -556,6 +585,9 @@ int64_t gwen_mlp2_bwd_rows(int64_t R);
 int gwen_mlp2_bwd_f32(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
                       int64_t T_rows, int64_t ldT, const float *Wet, float *g_pre1, float *g_e, int64_t R, int64_t F,
                       void *workspace, size_t workspace_bytes, gwen_stream_t stream);
+int gwen_mlp2_bwd_contract_f32(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
+                               int64_t T_rows, int64_t ldT, const float *Wet, float *g_pre1, float *g_e, int64_t R,
+                               int64_t F, int contract, void *workspace, size_t workspace_bytes, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Masked L1 loss, value and gradient in one pass -- the reference's training objective
