@@ -182,6 +182,8 @@ SIGNATURES = {
     "gwen_mlp2_bwd_contract_f32": (_int, [_vp] * 5 + [_i64, _i64, _vp, _vp, _vp, _i64, _i64, _int, _vp, C.c_size_t, _vp]),
     "gwen_masked_l1_workspace_floats": (_i64, []),
     "gwen_masked_l1_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "gwen_ens_crps_workspace_floats": (_i64, [_i64, _i64, _i64]),
+    "gwen_ens_crps_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 

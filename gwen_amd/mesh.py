@@ -48,6 +48,16 @@ class Mesh:
     def num_edges(self) -> int:
         return int(self.edge_index.shape[1])
 
+    def face_areas(self) -> np.ndarray:
+        """Spherical-triangle area of every face, float64 ``[F]`` (they sum to 4 pi).  The faces are the forecaster's
+        grid cells (``InteractionForecaster.prepare``), so these are the natural node weights of grid scores
+        (``gwen_amd.losses``).  Van Oosterom--Strackee: tan(E/2) = |a.(b x c)| / (1 + a.b + b.c + c.a)."""
+        p = self.pos / np.linalg.norm(self.pos, axis=1, keepdims=True)
+        a, b, c = p[self.faces[:, 0]], p[self.faces[:, 1]], p[self.faces[:, 2]]
+        num = np.abs(np.einsum("ij,ij->i", a, np.cross(b, c)))
+        den = 1.0 + np.einsum("ij,ij->i", a, b) + np.einsum("ij,ij->i", b, c) + np.einsum("ij,ij->i", c, a)
+        return 2.0 * np.arctan2(num, den)
+
 
 def _morton3(pos: np.ndarray, bits: int = 10) -> np.ndarray:
     q = np.clip(((pos + 1.0) * 0.5 * ((1 << bits) - 1)).round().astype(np.uint64), 0, (1 << bits) - 1)

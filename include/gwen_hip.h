@@ -603,6 +603,29 @@ int gwen_masked_l1_f32(const float *out, const float *target, const uint8_t *mas
                        int64_t C, float *grad, float *loss, float *workspace, int64_t workspace_floats,
                        gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ensemble CRPS over the members axis, scores and gradient in one pass over the ensemble.
+ * pred fp32 [M, N, C] (members first), target fp32 [N, C], both contiguous; node_w [N] >= 0 and chan_w [C] >= 0
+ * or NULL (ones).  For a point with members x_1..x_M and truth y, k = pair_coef (alpha / (2M(M-1)) +
+ * (1 - alpha) / (2M^2): alpha = 1 fair, 0 the ensemble's own CRPS):
+ *     CRPS = (1/M) sum_i |x_i - y| - k sum_i sum_j |x_i - x_j|
+ *     scores[0][c] = sum_n w_n CRPS(n,c) / sum w                      (per-channel CRPS)
+ *     scores[1][c] = sum_n w_n (mean_i x_i - y)^2 / sum w             (RMSE^2 of the ensemble mean)
+ *     scores[2][c] = sum_n w_n var_i(x_i) / sum w                     (spread^2; unbiased variance, NaN for M = 1)
+ *     loss[0]      = sum_c v_c scores[0][c] / sum v
+ *     grad_pred[i,n,c] = w_n v_c / (sum w sum v) * (sign(x_i - y) / M - 2k (#{x_j < x_i} - #{x_j > x_i}))
+ *     grad_target[n,c] = -w_n v_c / (sum w sum v) / M * sum_i sign(x_i - y)              (sign(0) = 0)
+ * grad_pred, grad_target and scores may be NULL; loss may not.  1 <= M <= 64, N >= 1, C >= 1, every pointer
+ * 4-byte aligned, else GWEN_EINVAL before any HIP call (also for a workspace shorter than
+ * gwen_ens_crps_workspace_floats(M, N, C) floats).  C % 4 == 0 with 16-byte aligned pred / target / grads reads
+ * 16 bytes per lane.  Four launches, sums in a fixed order, no atomics (bitwise reproducible); zero weights give
+ * NaN, as the expression does.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gwen_ens_crps_workspace_floats(int64_t M, int64_t N, int64_t C);
+int gwen_ens_crps_f32(const float *pred, const float *target, const float *node_w, const float *chan_w, int64_t M,
+                      int64_t N, int64_t C, float pair_coef, float *grad_pred, float *grad_target, float *loss,
+                      float *scores, float *workspace, int64_t workspace_floats, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
