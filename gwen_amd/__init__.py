@@ -5,12 +5,13 @@ UpConvLayers, GCNConvLayers, GNNModel, loss_func) plus the ``GCNConv`` layer it 
 torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); build it with
 ``python -m gwen_amd.build``.
 """
-from . import forecaster, g2m, interaction, losses, ops
+from . import forecaster, g2m, interaction, losses, noise, ops
 from .forward import GraphedForward, KernelEvents, StackForward, event_bracket_overhead
 from .gcn_conv import GCNConv, Linear
 from .forecaster import InteractionForecaster
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
 from .losses import EnsembleCRPSLoss, ensemble_crps, ensemble_scores
+from .noise import NoiseStream
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
 from .models_gnn import (DownConvLayers, GCNConvLayers, GNNConfig, GNNModel, UpConvLayers,
@@ -20,6 +21,6 @@ __all__ = [
     "GCNConv", "Linear", "GraphedForward", "KernelEvents", "StackForward", "event_bracket_overhead", "GraphCSR", "GraphCache", "default_cache", "prepare_graph", "Mesh",
     "complete_graph", "geodesic_mesh", "DownConvLayers", "GCNConvLayers", "GNNConfig", "GNNModel",
     "UpConvLayers", "loss_func", "InteractionNet", "InteractionForecaster", "EdgeGraph", "interaction_graph",
-    "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores",
+    "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream",
 ]
 __version__ = "0.1.0"

@@ -69,6 +69,24 @@ def gather_members(local: Tensor, num_members: int, group: Optional[dist.Process
     return torch.cat([buf[r, : counts[r]] for r in range(world)], 0)
 
 
+def perturbed_members(x0: Tensor, num_members: int, sigma, seed: int,
+                      group: Optional[dist.ProcessGroup] = None) -> Tensor:
+    """This rank's block (``member_range``) of the initial ensemble ``x0 + sigma z``: x0 [N, C] on a HIP device, sigma a
+    float or a [C] tensor, z[m, n, c] = z(seed, tag 1, draw 0, m, n, c) of gwen_amd.noise (the initial-condition
+    stream: never the latent noise's).  A pure function of the global member index, so the blocks of all ranks
+    concatenate to the one-process ensemble without any exchange."""
+    from . import noise
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    lo, hi = member_range(num_members, rank, world)
+    if x0.dim() != 2:
+        raise ValueError(f"perturbed_members: x0 [N, C] expected, got {tuple(x0.shape)}")
+    z = noise.normal(noise.NoiseStream(seed, x0.device), hi - lo, x0.size(0), x0.size(1), member0=lo,
+                     tag=noise.TAG_INITIAL)
+    s = torch.as_tensor(sigma, dtype=x0.dtype, device=x0.device)
+    return x0.unsqueeze(0) + s * z
+
+
 def ensemble_rollout(step: Callable[[Tensor], Tensor], x_members: Tensor, num_steps: int,
                      num_members: int, group: Optional[dist.ProcessGroup] = None) -> Tensor:
     """Apply ``step`` ``num_steps`` times to this rank's members ``[members_local, N, C]`` (each output

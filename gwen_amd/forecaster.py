@@ -28,6 +28,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
+from . import noise as noise_mod
 from . import ops
 from .g2m import grid_mesh_edges
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
@@ -50,6 +51,7 @@ class ForecastGraphs:
     f_mesh: Tensor
     f_m2g: Tensor
     _batched: dict = None   # members -> ForecastGraphs of the block-diagonal graphs
+    members: int = 1        # copies of the graphs these are (mesh latent row r = node r % Nm of member r // Nm)
 
     def batched(self, members: int) -> "ForecastGraphs":
         """Graphs and static inputs of ``members`` independent copies (EdgeGraph.batched): the c5 path rolls
@@ -62,18 +64,30 @@ class ForecastGraphs:
             rep = lambda t: t.repeat(members, 1)                                   # noqa: E731
             self._batched[members] = ForecastGraphs(
                 self.g2m.batched(members), self.mesh.batched(members), self.m2g.batched(members),
-                rep(self.mesh_pos), rep(self.f_g2m), rep(self.f_mesh), rep(self.f_m2g))
+                rep(self.mesh_pos), rep(self.f_g2m), rep(self.f_mesh), rep(self.f_m2g), members=members)
         return self._batched[members]
+
+    @property
+    def mesh_nodes(self) -> int:
+        """Mesh nodes of ONE member."""
+        return self.mesh_pos.size(0) // self.__dict__.get("members", 1)
 
 
 class InteractionForecaster(nn.Module):
     """``precision`` ("3xbf16", the default, or "f16x3": fp32-class) applies to every contraction of the model -- the
     blocks (``InteractionNet.precision``) and the embedding / read-out ``Linear``s; ``set_precision`` changes it.  Not
     part of ``state_dict()``.  A captured step (``GraphedStep``, ``ensemble_forecast``) keeps the precision it was
-    captured with."""
+    captured with.
+
+    ``noise_channels`` K > 0 (8, 16, 32 or 64) adds latent noise: once per step, between the encoder and the
+    processor, ``vm += z Wz^T`` with z drawn per member, node and step from a ``noise.NoiseStream`` passed as ``noise=``
+    (``noise_embed`` = Wz, an ``nn.Linear(K, hidden, bias=False)``, zero-initialised: a fresh noisy model computes what
+    its deterministic self computes).  Without ``noise=`` the step is deterministic (z = 0).  Every call that takes a
+    stream leaves it ``n_steps`` draws further on; member m at step t of a call that starts at draw d gets
+    z(seed, 0, d + t, m, node, k), whichever path runs it."""
 
     def __init__(self, grid_channels: int, hidden: int, steps: int = 4, activation: str = "silu",
-                 aggr: str = "sum", precision: str = "3xbf16"):
+                 aggr: str = "sum", precision: str = "3xbf16", noise_channels: int = 0):
         super().__init__()
         self.grid_channels, self.hidden, self.steps = grid_channels, hidden, steps
         self.grid_embed = nn.Linear(grid_channels, hidden)
@@ -86,6 +100,12 @@ class InteractionForecaster(nn.Module):
         self.decoder = InteractionNet(hidden, activation, aggr)
         self.readout = nn.Linear(hidden, grid_channels)
         self.set_precision(precision)
+        if noise_channels not in (0,) + noise_mod.INJECT_CHANNELS:
+            raise ValueError(f"noise_channels must be 0 or one of {noise_mod.INJECT_CHANNELS}, got {noise_channels}")
+        self.noise_channels = noise_channels
+        if noise_channels:
+            self.noise_embed = nn.Linear(noise_channels, hidden, bias=False)
+            nn.init.zeros_(self.noise_embed.weight)
 
     def set_precision(self, p: str) -> "InteractionForecaster":
         """The contraction of the encoder, the processors, the decoder and the six embedding / read-out layers."""
@@ -124,27 +144,39 @@ class InteractionForecaster(nn.Module):
         return (lin(graphs.mesh_pos, self.mesh_embed), lin(graphs.f_g2m, self.g2m_edge_embed),
                 lin(graphs.f_mesh, self.mesh_edge_embed), lin(graphs.f_m2g, self.m2g_edge_embed))
 
-    def _step(self, grid_x: Tensor, graphs: ForecastGraphs, static, out: Optional[Tensor] = None) -> Tensor:
+    def _step(self, grid_x: Tensor, graphs: ForecastGraphs, static, out: Optional[Tensor] = None,
+              noise: Optional["noise_mod.NoiseStream"] = None, member0: int = 0) -> Tensor:
+        """One step; with ``noise``: the latent noise of members ``member0 ..`` at the stream's draw, which the step
+        then advances by one (in stream order: captured with the step)."""
         vm, e_g2m, e_m, e_m2g = static
         vg = self._lin(grid_x, self.grid_embed)
         vm, _ = self.encoder(vg, vm, e_g2m, graphs.g2m, update_edges=False)
+        if noise is not None:
+            if self.__dict__.get("noise_channels", 0):             # (a model pickled before the setting existed: 0)
+                wz = self.noise_embed.weight
+                grad = torch.is_grad_enabled() and (vm.requires_grad or wz.requires_grad)
+                vm = noise_mod.inject(vm, wz, noise, graphs.mesh_nodes, member0, out=None if grad else vm)
+            noise.advance(1)
         for net in self.processor:
             vm, e_m = net(vm, vm, e_m, graphs.mesh)
         vg, _ = self.decoder(vm, vg, e_m2g, graphs.m2g, update_edges=False)
         delta = self._lin(vg, self.readout)
         return grid_x + delta if out is None else torch.add(grid_x, delta, out=out)      # (out: GraphedStep's buffers)
 
-    def forward(self, grid_x: Tensor, graphs: ForecastGraphs) -> Tensor:
+    def forward(self, grid_x: Tensor, graphs: ForecastGraphs, noise: Optional["noise_mod.NoiseStream"] = None,
+                member0: int = 0) -> Tensor:
         """``grid_x`` [N_grid, C] or [members, N_grid, C] (members share graphs and weights: one launch set
-        over the block-diagonal graph)."""
+        over the block-diagonal graph).  ``noise``: latent noise of members ``member0 ..`` (advances the stream by 1)."""
         if grid_x.dim() == 3:
             m = grid_x.size(0)
             gb = graphs.batched(m)
-            return self._step(grid_x.reshape(-1, grid_x.size(-1)), gb, self._static(gb)).view_as(grid_x)
-        return self._step(grid_x, graphs, self._static(graphs))
+            return self._step(grid_x.reshape(-1, grid_x.size(-1)), gb, self._static(gb), noise=noise,
+                              member0=member0).view_as(grid_x)
+        return self._step(grid_x, graphs, self._static(graphs), noise=noise, member0=member0)
 
     def rollout(self, grid_x: Tensor, graphs: ForecastGraphs, n_steps: int,
-                graphed: bool = False) -> List[Tensor]:
+                graphed: bool = False, noise: Optional["noise_mod.NoiseStream"] = None,
+                member0: int = 0) -> List[Tensor]:
         """Autoregressive: state_{t+1} = forward(state_t); returns the n_steps states.
         ``graphed``: capture ONE step (its ~26 launches) into a hipGraph and replay it per step -- the
         launchers allocate and synchronise nothing, so the step is capturable as is; worth it when the
@@ -152,21 +184,23 @@ class InteractionForecaster(nn.Module):
         states, cur = [], grid_x
         with torch.no_grad():
             if graphed:
-                step = GraphedStep(self, graphs, grid_x)
+                step = GraphedStep(self, graphs, grid_x, noise=noise, member0=member0)
                 for _ in range(n_steps):
                     cur = step(cur)                          # (one of the step's two buffers: the next call reads it in place)
                     states.append(cur.clone())
                 return states
             static = self._static(graphs)
             for _ in range(n_steps):
-                cur = self._step(cur, graphs, static)
+                cur = self._step(cur, graphs, static) if noise is None else \
+                    self._step(cur, graphs, static, noise=noise, member0=member0)
                 states.append(cur)
         return states
 
 
 def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,
                       n_steps: int, num_members: int, group=None, graphed: bool = True,
-                      batched: bool = True, step_cache: dict = None, gather: bool = True) -> Tensor:
+                      batched: bool = True, step_cache: dict = None, gather: bool = True,
+                      noise=None, member0: Optional[int] = None) -> Tensor:
     """BASELINE config c5: this rank's members ``[members_local, N_grid, C]`` are rolled out ``n_steps``
     steps (independent members, replicated graph and weights), then every rank's final states are gathered
     ONCE (``ensemble.gather_members``: RCCL all-gather over xGMI under the "nccl" backend).  Returns
@@ -178,42 +212,66 @@ def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,
     ``step_cache``: a dict the captured step lives in between calls (capture costs one eager step plus the
     capture itself; the static embeddings inside it are those of the weights at capture time).
     ``gather=False`` returns this rank's final states ``[members_local, N_grid, C]`` without the collective.
-    ``model`` needs ``_static(graphs)`` and ``_step(x, graphs, static)`` (InteractionForecaster)."""
+    ``noise`` (a ``noise.NoiseStream``): latent noise.  This rank's first member is ``member0``, by default
+    ``ensemble.member_range(num_members, rank, world)[0]``; every rank holds the same seed and the same draw, so member m
+    gets the same noise on any rank and in any path.  The stream ends ``n_steps`` draws further on, on every rank, also
+    on one that holds no member (the member-by-member path rewinds it between members).  Cost: ``member0`` is a kernel
+    argument, so the graphed member-by-member path with ``noise`` captures one step per member (an eager warm-up step
+    and two graph captures each) -- on every call unless ``step_cache`` keeps them; the batched path captures once.
+    ``model`` needs ``_static(graphs)`` and ``_step(x, graphs, static)`` (InteractionForecaster; with ``noise``, also the
+    ``noise=`` and ``member0=`` keywords of its ``_step``)."""
     from . import ensemble
     m_local = x_members.size(0)
+    if noise is not None and member0 is None:
+        dist = torch.distributed
+        on = dist.is_available() and dist.is_initialized()
+        rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+        member0 = ensemble.member_range(num_members, rank, world)[0]
+    kw = {} if noise is None else {"noise": noise}
 
-    def captured(g, x0):
+    def captured(g, x0, m0):
         if step_cache is None:
-            return GraphedStep(model, g, x0)
-        key = (id(model), id(g), tuple(x0.shape))
+            return GraphedStep(model, g, x0, **kw, **({} if noise is None else {"member0": m0}))
+        key = (id(model), id(g), tuple(x0.shape)) + (() if noise is None else (id(noise), m0))
         if key not in step_cache:
-            step_cache[key] = GraphedStep(model, g, x0)
+            step_cache[key] = GraphedStep(model, g, x0, **kw, **({} if noise is None else {"member0": m0}))
         return step_cache[key]
+
+    def one_step(x, g, static, m0):
+        return model._step(x, g, static) if noise is None else model._step(x, g, static, noise=noise, member0=m0)
 
     with torch.no_grad():
         if m_local == 0:
             local = x_members.new_empty((0,) + tuple(x_members.shape[1:]))
+            if noise is not None:
+                noise.advance(n_steps)                       # a rank without members keeps the others' draw
         elif batched:
             gb = graphs.batched(m_local)
             cur = x_members.reshape(-1, x_members.size(-1))
             if graphed:
-                step = captured(gb, cur)
+                step = captured(gb, cur, member0)
                 for _ in range(n_steps):             # (the step alternates between its two state buffers: no copies)
                     cur = step(cur)
                 cur = cur.clone()
             else:
                 static = model._static(gb)
                 for _ in range(n_steps):
-                    cur = model._step(cur, gb, static)
+                    cur = one_step(cur, gb, static, member0)
             local = cur.view_as(x_members)
         else:
             finals = []
-            step = captured(graphs, x_members[0]) if graphed else None
-            static = None if step is not None else model._static(graphs)
+            static = None if graphed else model._static(graphs)
+            step = captured(graphs, x_members[0], None) if graphed and noise is None else None
             for m in range(m_local):
+                m0 = None if noise is None else member0 + m
+                if noise is not None:
+                    if m > 0:
+                        noise.advance(-n_steps)              # every member starts at the call's draw
+                    if graphed:                              # (member0 is a kernel argument: one capture per member)
+                        step = captured(graphs, x_members[0], m0)
                 cur = x_members[m]
                 for _ in range(n_steps):
-                    cur = step(cur) if step is not None else model._step(cur, graphs, static)
+                    cur = step(cur) if step is not None else one_step(cur, graphs, static, m0)
                 finals.append(cur.clone() if step is not None else cur)
             local = torch.stack(finals)
     if not gather:
@@ -226,21 +284,29 @@ class GraphedStep:
     and the graph B -> A -- so that an autoregressive rollout replays them alternately without copying the state (one
     capture over a fixed input / output pair cost two state-sized copies per step: 2 % of the c5 rollout).  ``step(x)``
     copies ``x`` into the next input buffer unless it IS that buffer (the previous call's result), replays, and returns the
-    output buffer -- valid until the call AFTER the next one (clone it to keep it longer)."""
+    output buffer -- valid until the call AFTER the next one (clone it to keep it longer).
 
-    def __init__(self, model: InteractionForecaster, graphs: ForecastGraphs, grid_x: Tensor):
+    ``noise``: the captured step injects the latent noise of members ``member0 ..`` at the stream's draw and advances it,
+    so every replay draws fresh noise (the warm-up step's advance is taken back)."""
+
+    def __init__(self, model: InteractionForecaster, graphs: ForecastGraphs, grid_x: Tensor, noise=None,
+                 member0: int = 0):
         self.bufs = [grid_x.detach().clone(), torch.empty_like(grid_x)]
         self.graphs = graphs                                 # the captured graphs hold raw pointers into these:
+        self.noise = noise                                   # (and into the noise state)
         self.cur = 0                                         # the buffer the next call reads
+        kw = {} if noise is None else {"noise": noise, "member0": member0}
         with torch.no_grad():                                # keep every tensor they read alive
             static = self._static = model._static(graphs)
-            model._step(self.bufs[0], graphs, static, out=self.bufs[1])       # warm-up: occupancy queries, tilings, caches
+            model._step(self.bufs[0], graphs, static, out=self.bufs[1], **kw)  # warm-up: occupancy queries, tilings, caches
+            if noise is not None:
+                noise.advance(-1)
             torch.cuda.synchronize(grid_x.device)
             self.replays = []
             for i in (0, 1):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    model._step(self.bufs[i], graphs, static, out=self.bufs[1 - i])
+                    model._step(self.bufs[i], graphs, static, out=self.bufs[1 - i], **kw)
                 self.replays.append(g)
 
     def __call__(self, x: Tensor) -> Tensor:

@@ -626,6 +626,34 @@ int gwen_ens_crps_f32(const float *pred, const float *target, const float *node_
                       int64_t N, int64_t C, float pair_coef, float *grad_pred, float *grad_target, float *loss,
                       float *scores, float *workspace, int64_t workspace_floats, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Latent noise: reproducible Gaussian noise per ensemble member, a pure function of
+ *     z(seed, tag, draw, member, node, k),   k = channel of a noise vector.
+ * Philox4x64-10 (numpy.random.Philox) with key = (seed, tag) and counter = (node, member, draw, k / 8), 64-bit words,
+ * word 0 least significant.  The block's words w_0..w_3 split into h[2i] = lo32(w_i), h[2i+1] = hi32(w_i);
+ * u_j = ((h_j >> 8) + 1/2) 2^-24 in (0, 1); Box-Muller on (u_2p, u_2p+1), p = 0..3:
+ *     z[8 (k / 8) + 2p] = sqrt(-2 ln u_2p) cos(2 pi u_2p+1),    z[8 (k / 8) + 2p + 1] = sqrt(-2 ln u_2p) sin(2 pi u_2p+1).
+ * (u needs 25 bits from 1/2 up: ln u is evaluated from 1 - u there, and the angle through sincospi of 2u or 2u - 2,
+ * so that no argument is rounded.)  tag 0: latent noise; tag 1: initial-condition perturbation.
+ * state: DEVICE uint64 [2] = {seed, draw}, 8-byte aligned, read by every launch (a captured hipGraph sees the current
+ * draw on every replay).  No allocation, no synchronisation, no atomics.
+ *
+ *   gwen_noise_normal_f32: out[m, n, k] = z(state[0], tag, state[1], member0 + m, n, k), fp32 [members, nodes, K]
+ *                          contiguous, any K >= 1.
+ *   gwen_noise_inject_f32: out[r, :] = x[r, :] + sum_k z(state[0], 0, state[1], member0 + r / nodes, r % nodes, k) wz[:, k]
+ *                          x, out fp32 [rows, H] (out may be x), wz fp32 [H, K] (an nn.Linear(K, H) weight); K in
+ *                          {8, 16, 32, 64}, H % 4 == 0, x / out / wz 16-byte aligned.  The noise term is accumulated from
+ *                          zero by fmaf in increasing k, then added to x: it does not depend on x or on any contraction
+ *                          tier, and two launches are bitwise equal.
+ *   gwen_noise_advance:    state[1] += n (n may be negative), one thread, in stream order.
+ * Bad arguments give GWEN_EINVAL before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+int gwen_noise_normal_f32(const uint64_t *state, uint64_t tag, int64_t member0, int64_t members, int64_t nodes,
+                          int64_t K, float *out, gwen_stream_t stream);
+int gwen_noise_inject_f32(const uint64_t *state, int64_t member0, int64_t rows, int64_t nodes, const float *x,
+                          const float *wz, int64_t H, int64_t K, float *out, gwen_stream_t stream);
+int gwen_noise_advance(uint64_t *state, int64_t n, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
