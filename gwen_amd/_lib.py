@@ -86,6 +86,7 @@ def wide_contract(fin: int, fout: int, code: int) -> int:
 KIND_PROPAGATE, KIND_LINEAR, KIND_LAYER, KIND_CHAIN, KIND_SMALL, KIND_WIDE = 2, 3, 4, 5, 6, 8
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
 EW_MUL, EW_ADD = 0, 1
+MLP2_LN_EDGE, MLP2_LN_NODE = 0, 1                    # GWEN_MLP2_LN_* (include/gwen_hip.h)
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
 
@@ -171,6 +172,13 @@ SIGNATURES = {
     "gwen_mlp2_contract_workspace_bytes": (_i64, [_i64, _int]),
     "gwen_mlp2_contract_f32": (_int, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 5 + [_i64, _i64, _int, _vp, _vp,
                                _i64, _vp, _i64, _int, _int, _vp, C.c_size_t, _vp]),
+    "gwen_mlp2_ln_supported": (_int, [_i64, _int, _int]),
+    "gwen_mlp2_ln_f32": (_int, [_vp] * 4 + [_i64, _i64, _vp, _vp, _i64, _i64] + [_vp] * 5 + [_i64, _i64, _int, _vp, _vp,
+                         _i64, _vp, _i64, _int, _int, _vp, _vp, _f32, _vp, C.c_size_t, _vp]),
+    "gwen_layer_norm_supported": (_int, [_i64]),
+    "gwen_layer_norm_f32": (_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _vp]),
+    "gwen_layer_norm_bwd_chunks": (_i64, [_i64]),
+    "gwen_layer_norm_bwd_f32": (_int, [_vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _vp]),
     "gwen_mlp2_rows": (_int, [_i64]),
     "gwen_act_pair_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _int, _vp]),
     "gwen_act_pair_seg_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp]),

@@ -635,7 +635,8 @@ int gwen_mlp2_rows_launch(int F, int f16, int m1, int m2, const float *A, const 
                           const float *G2, const int32_t *idx2, const float *b1, const float *W2,
                           const float *b2, const float *res, float *out, int64_t R, int act,
                           const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg,
-                          int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st);
+                          int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st, const float *ln_g,
+                          const float *ln_b, float ln_eps);
 
 extern "C" int gwen_mlp2_supported(int64_t F) {
   return F == 32 || F == 64 || F == 128 || F == 256 ? 1 : 0;
@@ -719,16 +720,32 @@ extern "C" int gwen_mlp2_bwd_f32(const float *ge, const float *W2t, const float 
                                     workspace, workspace_bytes, stream_);
 }
 
-extern "C" int gwen_mlp2_contract_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+// K6 with LayerNorm: which launch shapes have a fused instantiation of the row-stationary kernel (interact_rows.hip, LN)
+extern "C" int gwen_mlp2_ln_supported(int64_t F, int contract, int shape) {
+  if (!gwen_mlp2_contract_supported(F, contract)) return 0;
+  // (256 channels: the LN instantiations spill -- interact_rows.hip, launch_rows -- so that width runs unfused)
+  return F == 64 && (shape == GWEN_MLP2_LN_EDGE || shape == GWEN_MLP2_LN_NODE) ? 1 : 0;
+}
+
+// gwen_mlp2_contract_f32 and gwen_mlp2_ln_f32 (ln_gamma / ln_beta NULL: the former, the same launch bit for bit)
+static int mlp2_run(const float *A, const float *W1, const float *G1, const int32_t *idx1,
                                       int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
                                       int64_t G2_rows, int64_t ldg2,
                                       const float *b1, const float *W2, const float *b2, const float *res,
                                       float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
                                       const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
                                       int mean, int contract, void *workspace, size_t workspace_bytes,
-                                      gwen_stream_t stream_) {
+                                      gwen_stream_t stream_, const float *ln_g, const float *ln_b, float ln_eps) {
   if (R < 0 || N_agg < 0 || n_tiles < 0 || G1_rows < 0 || G2_rows < 0) return GWEN_EINVAL;
   if (!gwen_mlp2_contract_supported(F, contract)) return GWEN_EINVAL;
+  if ((ln_g != nullptr) != (ln_b != nullptr)) return GWEN_EINVAL;
+  if (ln_g) {                          // only the shapes with a fused instantiation (the caller asks gwen_mlp2_ln_supported)
+    const bool edge = G1 && idx1 && G2 && idx2 && agg && res && res == A;
+    const bool node = G1 && !idx1 && !G2 && !agg && res && res != A;
+    if (!(edge || node) || !gwen_mlp2_ln_supported(F, contract, edge ? GWEN_MLP2_LN_EDGE : GWEN_MLP2_LN_NODE) ||
+        !(ln_eps >= 0.0f) || !gwen_aligned(ln_g, 16) || !gwen_aligned(ln_b, 16))
+      return GWEN_EINVAL;
+  }
   const int f16 = contract == GWEN_CONTRACT_F16X3;
   if (act != GWEN_ACT_NONE && act != GWEN_ACT_RELU && act != GWEN_ACT_SILU) return GWEN_EINVAL;
   if (agg && (!rowptr || !tile_row || n_tiles < 1)) return GWEN_EINVAL;
@@ -759,10 +776,35 @@ extern "C" int gwen_mlp2_contract_f32(const float *A, const float *W1, const flo
                            (uint32_t)(ldg2 * 4), st)
   if (F == 256 || F == 64)
     return gwen_mlp2_rows_launch((int)F, f16, m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, tile_row,
-                                 n_tiles, agg, mean, workspace, (uint32_t)(ldg1 * 4), (uint32_t)(ldg2 * 4), st);
+                                 n_tiles, agg, mean, workspace, (uint32_t)(ldg1 * 4), (uint32_t)(ldg2 * 4), st, ln_g, ln_b,
+                                 ln_eps);
   GWEN_M(32); GWEN_M(128);
 #undef GWEN_M
   return GWEN_EINVAL;
+}
+
+extern "C" int gwen_mlp2_contract_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+                                      int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
+                                      int64_t G2_rows, int64_t ldg2,
+                                      const float *b1, const float *W2, const float *b2, const float *res,
+                                      float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
+                                      const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
+                                      int mean, int contract, void *workspace, size_t workspace_bytes,
+                                      gwen_stream_t stream_) {
+  return mlp2_run(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act, rowptr, tile_row,
+                  n_tiles, agg, N_agg, mean, contract, workspace, workspace_bytes, stream_, nullptr, nullptr, 0.0f);
+}
+
+extern "C" int gwen_mlp2_ln_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+                                int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
+                                int64_t G2_rows, int64_t ldg2,
+                                const float *b1, const float *W2, const float *b2, const float *res,
+                                float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
+                                const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
+                                int mean, int contract, const float *ln_gamma, const float *ln_beta, float ln_eps,
+                                void *workspace, size_t workspace_bytes, gwen_stream_t stream_) {
+  return mlp2_run(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act, rowptr, tile_row,
+                  n_tiles, agg, N_agg, mean, contract, workspace, workspace_bytes, stream_, ln_gamma, ln_beta, ln_eps);
 }
 
 extern "C" int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,

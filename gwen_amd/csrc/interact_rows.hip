@@ -202,7 +202,17 @@ struct Vis {
 // step into the E registers that step has just split.  The residual is read again from memory in the store (row
 // layout, 256 contiguous bytes per 16 lanes), so E is free after the first contraction: the un-scaling epilogues
 // need those registers at 256 channels (held to the end of the pass, as 3xbf16 does, they spill).
-template <int F, int RT, int M1, int M2, bool SEG, int RES, bool HID = false, bool F16 = false>
+//
+// LN (gwen_mlp2_ln_f32): y is LayerNorm-ed over its F columns before the residual and the aggregation -- a wave owns ALL
+// columns of its 16 rows, so a row's mean and variance are a per-lane sum over rc plus two cross-lane steps (the lanes
+// l, l ^ 16, l ^ 32, l ^ 48 of a row: the reduction row_scale does for the maxima), and rc, normalised in place, is what
+// the store and the aggregation read afterwards.  fp32 on both tiers; the variance from deviations about the mean (a
+// second sweep over the registers).  gamma | beta: 2 F floats of LDS behind everything else (kOffL).  F16: rc is
+// still in the scaled domain here and is un-scaled tile by tile inside the store (finish_y); the two sweeps un-scale a
+// tile transiently (unscale4 + b2, accumulate, discard) and the normalisation joins finish_y -- three times the ldexp
+// work, no new live registers beyond mu and rstd.  Rows past the pass repeat its last row (finite statistics); they
+// are never stored or aggregated.
+template <int F, int RT, int M1, int M2, bool SEG, int RES, bool HID = false, bool F16 = false, bool LN = false>
 __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k_mlp2r(
     const float *__restrict__ A, const char *__restrict__ img, const float *__restrict__ W1f,
     const float *__restrict__ W2f, const float *__restrict__ G1,
@@ -210,17 +220,21 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
     const float *__restrict__ b1, const float *__restrict__ b2, const float *__restrict__ res,
     float *__restrict__ out, int32_t R, int act, const int32_t *__restrict__ rowptr,
     const int32_t *__restrict__ tile_row, int32_t n_tiles, float *__restrict__ agg, int mean,
-    uint32_t ldb1, uint32_t ldb2, float *__restrict__ hid = nullptr, const int32_t *__restrict__ wexp = nullptr) {
+    uint32_t ldb1, uint32_t ldb2, float *__restrict__ hid = nullptr, const int32_t *__restrict__ wexp = nullptr,
+    const float *__restrict__ ln_g = nullptr, const float *__restrict__ ln_b = nullptr, float ln_eps = 0.0f) {
   using C = RCfg<F, RT>;
   constexpr int NR = RT * C::NJ;                                     // float4 registers per set
   constexpr bool G2R = F16 && M2 != kNone;
   // (F16 at 64 channels keeps the MFMA-layout A loads and stores of 256 channels: no ROWIO turn through the y tile)
   constexpr bool ROWIO = C::ROWIO && !F16;
-  __shared__ __attribute__((aligned(1024))) char lds[F16 ? C::lds_f16 : C::lds_bytes];
+  constexpr int kOffL = F16 ? C::lds_f16 : C::lds_bytes;            // LN: gamma | beta
+  static_assert(!LN || (!HID && kOffL % 16 == 0 && kOffL + 2 * F * 4 <= 160 * 1024), "LN: forward only, and it must fit");
+  __shared__ __attribute__((aligned(1024))) char lds[kOffL + (LN ? 2 * F * 4 : 0)];
   const uint32_t lds0 = (uint32_t)(uintptr_t)lds;
   float *ytile = reinterpret_cast<float *>(lds + C::kOffY);
   float *bl = reinterpret_cast<float *>(lds + C::kOffB);           // b1 | b2
   uint8_t *sx = reinterpret_cast<uint8_t *>(lds + C::kOffS);        // F16: W1's | W2's column exponents + 128
+  float *lnl = reinterpret_cast<float *>(lds + kOffL);              // LN: gamma | beta
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int mi = lane & 15, g = lane >> 4;
@@ -230,6 +244,10 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
   for (int f = t; f < F; f += C::NW * 64) {
     bl[f] = b1 ? b1[f] : 0.0f;
     bl[F + f] = b2 ? b2[f] : 0.0f;
+    if constexpr (LN) {
+      lnl[f] = ln_g[f];
+      lnl[F + f] = ln_b[f];
+    }
     if constexpr (F16 && !C::RESIDENT) {
       sx[f] = (uint8_t)(wexp[f] + 128);
       sx[F + f] = (uint8_t)(wexp[F + f] + 128);
@@ -570,10 +588,61 @@ __global__ __launch_bounds__((RCfg<F, RT>::NW * 64), (RCfg<F, RT>::MINW)) void k
     });
     // F16: y = the second contraction un-scaled, + b2 -- column tile by column tile as the store below reaches it (all
     // at once, with the residual and the next pass's A rows live, the 256-channel kernel spills)
+    // LN: the rows' mean and 1 / sqrt(variance + eps) over all F columns of y, two sweeps (sum, then squared deviations)
+    float ln_mu[RT], ln_rs[RT];
+    if constexpr (LN) {
+      auto y_of = [&](int rt, int j) {                                // y's column tile j, as finish_y leaves it without LN
+        if constexpr (F16)
+          return unscale4(rc[rt * C::NJ + j], sh[rt], sx + F + col(j)) + *reinterpret_cast<const float4_t *>(bl + F + col(j));
+        else
+          return rc[rt * C::NJ + j];
+      };
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        float s = 0.0f;
+#pragma unroll
+        for (int j = 0; j < C::NJ; ++j) {
+          const float4_t v = y_of(rt, j);
+          s += (v[0] + v[1]) + (v[2] + v[3]);
+          if constexpr (F16) asm volatile("" ::: "memory");         // (one column tile's LDS reads at a time)
+        }
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        const float mu = s * (1.0f / F);
+        float q = 0.0f;
+#pragma unroll
+        for (int j = 0; j < C::NJ; ++j) {
+          const float4_t d = y_of(rt, j) - float4_t{mu, mu, mu, mu};
+          q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+          if constexpr (F16) asm volatile("" ::: "memory");
+        }
+        q += __shfl_xor(q, 16);
+        q += __shfl_xor(q, 32);
+        ln_mu[rt] = mu;
+        ln_rs[rt] = 1.0f / sqrtf(q * (1.0f / F) + ln_eps);
+      }
+    }
+    auto ln_apply = [&](float4_t v, int rt, int j) {
+      const float mu = ln_mu[rt], rs = ln_rs[rt];
+      return (v - float4_t{mu, mu, mu, mu}) * float4_t{rs, rs, rs, rs} * *reinterpret_cast<const float4_t *>(lnl + col(j)) +
+             *reinterpret_cast<const float4_t *>(lnl + F + col(j));
+    };
+    if constexpr (LN && !F16) {                                      // 3xbf16: rc holds y; normalised in place
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int j = 0; j < C::NJ; ++j) {
+          rc[rt * C::NJ + j] = ln_apply(rc[rt * C::NJ + j], rt, j);
+          asm volatile("" ::: "memory");
+        }
+    }
     auto finish_y = [&](int rt, int j) {
-      if constexpr (F16)
-        rc[rt * C::NJ + j] = unscale4(rc[rt * C::NJ + j], sh[rt], sx + F + col(j)) +
-                             *reinterpret_cast<const float4_t *>(bl + F + col(j));
+      if constexpr (F16) {
+        const float4_t y = unscale4(rc[rt * C::NJ + j], sh[rt], sx + F + col(j)) +
+                           *reinterpret_cast<const float4_t *>(bl + F + col(j));
+        if constexpr (LN) rc[rt * C::NJ + j] = ln_apply(y, rt, j);
+        else rc[rt * C::NJ + j] = y;
+      }
     };
     if constexpr (F16) {
       if (!out) {
@@ -751,7 +820,7 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
                 const int32_t *idx2, const float *b1, const float *W2, const float *b2, const float *res,
                 float *out, int64_t R, int act, const int32_t *rowptr, const int32_t *tile_row,
                 int64_t n_tiles, float *agg, int mean, void *workspace, uint32_t ldb1, uint32_t ldb2,
-                hipStream_t st) {
+                hipStream_t st, const float *ln_g = nullptr, const float *ln_b = nullptr, float ln_eps = 0.0f) {
   using C = RCfg<F, K6R_RT>;
   const bool seg = agg != nullptr;
   bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);
@@ -769,6 +838,24 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
   if (blocks > tiles) blocks = tiles;
   const int r = !res ? kResNone : (res == A ? kResA : kResOther);
   const char *im = reinterpret_cast<const char *>(img);
+  if (ln_g) {
+    // LN exists for the two shapes the block launches (gwen_mlp2_ln_supported): the edge MLP -- both tables indexed, per-
+    // target sums, residual = A -- and the node MLP -- G1 row for row, no sums, a residual other than A
+    // ... at 64 channels.  The 256-channel instantiations are NOT shipped: the kernel sits at 256 registers without LN and
+    // hipcc spills with it (edge 36 / node 192 registers on 3xbf16, 40 / 6 on f16x3); that width takes the unfused route
+    constexpr bool kEdge = M1 == kIdx && M2 == kIdx, kNode = M1 == kSelf && M2 == kNone;
+    if constexpr ((kEdge || kNode) && C::RESIDENT) {
+      if (kEdge ? (!seg || r != kResA) : (seg || r != kResOther)) return GWEN_EINVAL;
+      k_mlp2r<F, K6R_RT, M1, M2, kEdge, kEdge ? kResA : kResOther, false, F16, true><<<(unsigned)blocks, C::NW * 64, 0, st>>>(
+          A, im, W1, W2, G1, idx1, G2, idx2, b1, b2, res, out, (int32_t)R, act, kEdge ? rowptr : nullptr,
+          kEdge ? tile_row : nullptr, (int32_t)tiles, kEdge ? agg : nullptr, kEdge ? mean : 0, ldb1, ldb2, nullptr, wexp,
+          ln_g, ln_b, ln_eps);
+      GWEN_LAUNCH_CHECK();
+      return GWEN_OK;
+    } else {
+      return GWEN_EINVAL;
+    }
+  }
 #define GWEN_R(SEGV, RV)                                                                              \
   k_mlp2r<F, K6R_RT, M1, M2, SEGV, RV, false, F16><<<(unsigned)blocks, C::NW * 64, 0, st>>>(                 \
       A, im, W1, W2, G1, idx1, G2, idx2, b1, b2, res, out, (int32_t)R, act, SEGV ? rowptr : nullptr,  \
@@ -830,11 +917,12 @@ int gwen_mlp2_rows_launch(int F, int f16, int m1, int m2, const float *A, const 
                           const float *G2, const int32_t *idx2, const float *b1, const float *W2,
                           const float *b2, const float *res, float *out, int64_t R, int act,
                           const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg,
-                          int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st) {
+                          int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st, const float *ln_g,
+                          const float *ln_b, float ln_eps) {
 #define GWEN_MODE(FF, A1, A2, H)                                                                      \
   if (F == FF && m1 == A1 && m2 == A2 && (f16 != 0) == H)                                             \
     return launch_rows<FF, A1, A2, H>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
-                                      tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st)
+                                      tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st, ln_g, ln_b, ln_eps)
   GWEN_MODE(256, kNone, kNone, false); GWEN_MODE(256, kSelf, kNone, false); GWEN_MODE(256, kIdx, kNone, false);
   GWEN_MODE(256, kIdx, kIdx, false);
   GWEN_MODE(64, kNone, kNone, false); GWEN_MODE(64, kSelf, kNone, false); GWEN_MODE(64, kIdx, kNone, false);

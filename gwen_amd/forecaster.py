@@ -84,10 +84,15 @@ class InteractionForecaster(nn.Module):
     (``noise_embed`` = Wz, an ``nn.Linear(K, hidden, bias=False)``, zero-initialised: a fresh noisy model computes what
     its deterministic self computes).  Without ``noise=`` the step is deterministic (z = 0).  Every call that takes a
     stream leaves it ``n_steps`` draws further on; member m at step t of a call that starts at draw d gets
-    z(seed, 0, d + t, m, node, k), whichever path runs it."""
+    z(seed, 0, d + t, m, node, k), whichever path runs it.
+
+    ``layer_norm=True`` (off by default; ``norm_eps``): the encoder, every processor block and the decoder normalise both
+    MLP outputs (``InteractionNet(layer_norm=True)``: m_e = LN(MLP_e(..)), x' = x + LN(MLP_n(..))); the embedders and the
+    read-out stay plain ``Linear``s."""
 
     def __init__(self, grid_channels: int, hidden: int, steps: int = 4, activation: str = "silu",
-                 aggr: str = "sum", precision: str = "3xbf16", noise_channels: int = 0):
+                 aggr: str = "sum", precision: str = "3xbf16", noise_channels: int = 0, layer_norm: bool = False,
+                 norm_eps: float = 1e-5):
         super().__init__()
         self.grid_channels, self.hidden, self.steps = grid_channels, hidden, steps
         self.grid_embed = nn.Linear(grid_channels, hidden)
@@ -95,9 +100,11 @@ class InteractionForecaster(nn.Module):
         self.g2m_edge_embed = nn.Linear(4, hidden)
         self.mesh_edge_embed = nn.Linear(4, hidden)
         self.m2g_edge_embed = nn.Linear(4, hidden)
-        self.encoder = InteractionNet(hidden, activation, aggr)
-        self.processor = nn.ModuleList([InteractionNet(hidden, activation, aggr) for _ in range(steps)])
-        self.decoder = InteractionNet(hidden, activation, aggr)
+        ln = {"layer_norm": True, "norm_eps": norm_eps} if layer_norm else {}        # (off: the blocks as they were)
+        self.layer_norm = bool(layer_norm)
+        self.encoder = InteractionNet(hidden, activation, aggr, **ln)
+        self.processor = nn.ModuleList([InteractionNet(hidden, activation, aggr, **ln) for _ in range(steps)])
+        self.decoder = InteractionNet(hidden, activation, aggr, **ln)
         self.readout = nn.Linear(hidden, grid_channels)
         self.set_precision(precision)
         if noise_channels not in (0,) + noise_mod.INJECT_CHANNELS:

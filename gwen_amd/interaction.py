@@ -8,6 +8,16 @@ oracle/interaction_oracle.py, PARITY UNPINNED):
     agg_d = sum / mean of m_e over the in-edges of d
     x'_d  = x_dst_d + MLP_n([x_dst_d, agg_d]) ,   e' = e + m_e
 
+``layer_norm=True`` (off by default) puts a LayerNorm behind each MLP, before the residual and before the aggregation,
+as the published encode-process-decode models do:
+    m_e = LN_edge(MLP_e(..)),  x'_d = x_dst_d + LN_node(MLP_n(..)),   LN(m)_c = (m_c - mu) rstd gamma_c + beta_c,
+    mu = mean_c m_c,  rstd = 1 / sqrt(mean_c (m_c - mu)^2 + eps)       (torch.nn.LayerNorm(F); biased variance)
+At 64 channels the normalisation is fused into K6 (a row's statistics are a per-lane sum and two cross-lane steps in
+the row-stationary kernel: no extra launch, no message tensor in HBM); at 32, 128 and 256 channels (256: the fused
+instantiations spill) K6 writes the messages and ONE launch of the row kernel (csrc/layernorm.hip)
+forms e' and agg.  The backward recomputes the two
+pre-norm outputs by K3 and puts the LayerNorm backward kernel in front of each MLP's own backward.
+
 How it runs (3 launches on a square graph, 4 on a bipartite one; training: _InteractionNetFunction, whose backward
 is assembled from atomic-free launches of libgwen_hip.so as well -- csrc/interact_bwd.hip):
   * the node halves of both first layers are projected per NODE, not per edge, by ONE K3 launch with the
@@ -166,21 +176,33 @@ def mlp2(a: Tensor, w1: Tensor, w2: Tensor, b2: Optional[Tensor] = None, *,
          g1: Optional[Tensor] = None, idx1: Optional[Tensor] = None, g2: Optional[Tensor] = None,
          idx2: Optional[Tensor] = None, b1: Optional[Tensor] = None, res: Optional[Tensor] = None,
          act: str = "silu", graph: Optional[EdgeGraph] = None, mean: bool = False,
-         want_out: bool = True, contract: str = "3xbf16") -> Tuple[Optional[Tensor], Optional[Tensor]]:
-    """K6 (gwen_mlp2_contract_f32): returns (out, agg); ``agg`` only with ``graph`` (rows = its stored edges).
-    ``contract``: "3xbf16" (gwen_mlp2_f32's split, the default) or "f16x3" (fp32-class)."""
+         want_out: bool = True, contract: str = "3xbf16", ln_weight: Optional[Tensor] = None,
+         ln_bias: Optional[Tensor] = None, ln_eps: float = 1e-5) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """K6 (gwen_mlp2_ln_f32): returns (out, agg); ``agg`` only with ``graph`` (rows = its stored edges).
+    ``contract``: "3xbf16" (gwen_mlp2_f32's split, the default) or "f16x3" (fp32-class).
+    ``ln_weight`` / ``ln_bias`` (both or neither, fp32 [F]): y = LN(act(pre) W2^T + b2) before ``res`` and ``agg`` --
+    fused into the kernel where an instantiation exists (gwen_mlp2_ln_supported: the block's two launch shapes at 64
+    channels), else K6 without ``res`` / ``agg`` followed by one launch of the row kernel (same semantics)."""
     code = _mlp2_contract(contract)
+    if (ln_weight is None) != (ln_bias is None):
+        raise ValueError("ln_weight and ln_bias come together")
     f = a.size(-1)
     if a.dim() != 2 or not mlp2_supported(f):
         raise ValueError(f"K6 needs [rows, F] with F in (32, 64, 128, 256); got {tuple(a.shape)}")
     if tuple(w1.shape) != (f, f) or tuple(w2.shape) != (f, f):
         raise ValueError("W1 and W2 must be [F, F]")
+    if ln_weight is not None and (tuple(ln_weight.shape) != (f,) or tuple(ln_bias.shape) != (f,)):
+        raise ValueError("ln_weight and ln_bias must be [F]")
     ts = {"a": a, "w1": w1, "w2": w2, "b1": b1, "b2": b2, "res": res}
     for name, t in ts.items():
         if t is not None:
             ops._require(t, name)
             ts[name] = t.contiguous()
     a, w1, w2, b1, b2, res = (ts[k] for k in ("a", "w1", "w2", "b1", "b2", "res"))
+    if ln_weight is not None:
+        ops._require(ln_weight, "ln_weight")
+        ops._require(ln_bias, "ln_bias")
+        ln_weight, ln_bias = ln_weight.contiguous(), ln_bias.contiguous()
     # a table may be a column block of a wider row-major matrix (several projections from one launch)
     for name, g in (("g1", g1), ("g2", g2)):
         if g is not None:
@@ -197,26 +219,42 @@ def mlp2(a: Tensor, w1: Tensor, w2: Tensor, b2: Optional[Tensor] = None, *,
     if res is not None and res.shape != a.shape:
         raise ValueError("res must have the shape of A")
     dev = a.device
+    if graph is not None and graph.num_edges != rows:
+        raise ValueError("A must hold one row per stored edge of the graph")
+    if ln_weight is not None and rows > 0:
+        edge = g1 is not None and idx1 is not None and g2 is not None and idx2 is not None and graph is not None \
+            and res is not None and res.data_ptr() == a.data_ptr()
+        node = g1 is not None and idx1 is None and g2 is None and graph is None and res is not None \
+            and res.data_ptr() != a.data_ptr()
+        shape = _lib.MLP2_LN_EDGE if edge else _lib.MLP2_LN_NODE if node else None
+        if _LN_FORCE_UNFUSED or shape is None or not _lib.lib().gwen_mlp2_ln_supported(f, code, shape):
+            # the unfused route: K6 writes the pre-norm rows, ONE launch of the row kernel writes out = res + LN(m) and agg
+            m, _ = mlp2(a, w1, w2, b2, g1=g1, idx1=idx1, g2=g2, idx2=idx2, b1=b1, act=act, contract=contract)
+            return ops.layer_norm_rows(m, ln_weight, ln_bias, ln_eps, res, None if graph is None else graph.rowptr,
+                                       0 if graph is None else graph.num_dst, mean, want_out)
+    else:
+        ln_weight = ln_bias = None                 # (no rows: nothing to normalise, every target's sum is empty)
     out = torch.empty_like(a) if want_out else None
     agg, tile_row, n_tiles = None, None, 0
     if graph is not None:
-        if graph.num_edges != rows:
-            raise ValueError("A must hold one row per stored edge of the graph")
         agg = torch.empty(graph.num_dst, f, dtype=torch.float32, device=dev)
         tile_row, n_tiles = graph.tiles(int(_lib.lib().gwen_mlp2_rows(f)))
     nws = int(_lib.lib().gwen_mlp2_contract_workspace_bytes(f, code))
     ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws > 0 else None
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_mlp2_contract_f32(
+        rc = _lib.lib().gwen_mlp2_ln_f32(
             _ptr(a), _ptr(w1), _ptr(g1), _ptr(idx1), 0 if g1 is None else g1.size(0),
             0 if g1 is None else g1.stride(0), _ptr(g2), _ptr(idx2), 0 if g2 is None else g2.size(0),
             0 if g2 is None else g2.stride(0), _ptr(b1), _ptr(w2), _ptr(b2),
             _ptr(res), _ptr(out), rows, f, _ACT[act],
             _ptr(graph.rowptr) if graph else None, _ptr(tile_row), n_tiles, _ptr(agg),
-            graph.num_dst if graph else 0, int(mean), code,
+            graph.num_dst if graph else 0, int(mean), code, _ptr(ln_weight), _ptr(ln_bias), ln_eps,
             _ptr(ws), nws, _stream(dev))
-    _lib.check(rc, "gwen_mlp2_contract_f32")
+    _lib.check(rc, "gwen_mlp2_ln_f32")
     return out, agg
+
+
+_LN_FORCE_UNFUSED = False      # tests: K6 with LayerNorm takes the unfused route where a fused instantiation exists
 
 
 def _mlp(fin: int, f: int, act: str) -> nn.Sequential:
@@ -231,9 +269,15 @@ class InteractionNet(nn.Module):
 
     ``precision`` ("3xbf16", the default, or "f16x3": fp32-class) governs everything the block contracts: the node
     projections (K3: "f16x3" runs its fp32-class split, bf16x6), both K6 launches, and every product and weight
-    gradient of the backward.  A setting, not a parameter: it is not in ``state_dict()`` (pickling keeps it)."""
+    gradient of the backward.  A setting, not a parameter: it is not in ``state_dict()`` (pickling keeps it).
 
-    def __init__(self, channels: int, activation: str = "silu", aggr: str = "sum", precision: str = "3xbf16"):
+    ``layer_norm=True``: m_e = LN_edge(MLP_e(..)) and x' = x + LN_node(MLP_n(..)) (module docstring); the module then owns
+    ``edge_norm`` and ``node_norm``, each an ``nn.LayerNorm(channels, eps=norm_eps)`` used as a parameter holder (gamma = 1,
+    beta = 0 at init): ``state_dict()`` gains ``{edge,node}_norm.{weight,bias}`` after the eight keys above.  Statistics and
+    the affine step are fp32 on both precisions.  Off by default: the same launches, bits and keys as before."""
+
+    def __init__(self, channels: int, activation: str = "silu", aggr: str = "sum", precision: str = "3xbf16",
+                 layer_norm: bool = False, norm_eps: float = 1e-5):
         super().__init__()
         if activation not in _ACT or aggr not in ("sum", "mean"):
             raise ValueError("activation in (none, relu, silu), aggr in (sum, mean)")
@@ -241,6 +285,10 @@ class InteractionNet(nn.Module):
         self.precision = precision
         self.edge_mlp = _mlp(3 * channels, channels, activation)
         self.node_mlp = _mlp(2 * channels, channels, activation)
+        self._layer_norm = bool(layer_norm)
+        if layer_norm:
+            self.edge_norm = nn.LayerNorm(channels, eps=norm_eps)
+            self.node_norm = nn.LayerNorm(channels, eps=norm_eps)
         self._blocks = None          # contiguous [F,F] blocks of the two first layers + their versions
 
     def _weight_blocks(self):
@@ -267,6 +315,17 @@ class InteractionNet(nn.Module):
     def precision(self, p: str) -> None:
         _mlp2_contract(p)
         self._precision = p
+
+    @property
+    def layer_norm(self) -> bool:
+        return self.__dict__.get("_layer_norm", False)            # (a module pickled before the setting existed)
+
+    def _ln(self, which: str) -> dict:
+        """mlp2's LayerNorm arguments for the edge / node MLP ({} without LayerNorm)."""
+        if not self.layer_norm:
+            return {}
+        n = self.edge_norm if which == "edge" else self.node_norm
+        return {"ln_weight": n.weight, "ln_bias": n.bias, "ln_eps": n.eps}
 
     def __getstate__(self):          # the cache is derived data: keep modules picklable and small
         state = self.__dict__.copy()
@@ -301,9 +360,10 @@ class InteractionNet(nn.Module):
             pd, q = p[:, :f], p[:, f:]
         e_new, agg = mlp2(e, we, self.edge_mlp[2].weight, self.edge_mlp[2].bias,
                           g1=ps, idx1=graph.src, g2=pd, idx2=graph.dst, res=e, act=self.activation,
-                          graph=graph, mean=self.aggr == "mean", want_out=update_edges, contract=prec)
+                          graph=graph, mean=self.aggr == "mean", want_out=update_edges, contract=prec,
+                          **self._ln("edge"))
         x_new, _ = mlp2(agg, wa, self.node_mlp[2].weight, self.node_mlp[2].bias, g1=q,
-                        res=x_dst, act=self.activation, contract=prec)
+                        res=x_dst, act=self.activation, contract=prec, **self._ln("node"))
         # (training keeps the aggregate and the node projections: node-sized arrays this pass makes anyway)
         return (x_new, e_new, agg, p, None if x_src is x_dst else ps) if return_agg else (x_new, e_new)
 
@@ -420,6 +480,8 @@ class _InteractionNetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx, ge):
+        if ctx.net.layer_norm:
+            return _backward_layer_norm(ctx, gx, ge)
         x_src, x_dst, e, agg, w1, b1, w2, b2, w3, b3, w4, b4, pall, ps = ctx.saved_tensors
         net, g, same = ctx.net, ctx.graph, ctx.same
         f, act, mean = net.channels, net.activation, net.aggr == "mean"
@@ -524,3 +586,75 @@ class _InteractionNetFunction(torch.autograd.Function):
         pick = lambda k, t: t if need[k] else None                                          # noqa: E731
         return (None, None, None, None, pick(4, g_xs), pick(5, g_xd), pick(6, g_e), pick(7, g_w1), pick(8, g_b1),
                 pick(9, g_w2), pick(10, g_b2), pick(11, g_w3), pick(12, g_b3), pick(13, g_w4), pick(14, g_b4))
+
+
+def _backward_layer_norm(ctx, gx, ge):
+    """``_InteractionNetFunction.backward`` of a block with LayerNorm.  The message gradient g_m = LN'(ge + g_agg[dst]) is
+    not linear across a target's edges, so the one-launch edge backward (g_m W2 = ge W2 + T[dst]) does not apply: this is
+    the general (``_gather_add``) walk with two additions -- the pre-norm outputs m = h1 W2^T + b2 and m3 = h3 W4^T + b4
+    recomputed by K3 next to the hidden layers, and the LayerNorm backward kernel (csrc/layernorm.hip) between the
+    incoming gradient and each MLP's own backward, which also yields the four norm-parameter gradients (per-chunk
+    partials, finished with every other gradient in the GradBatch's one launch).  Atomic-free, fixed order."""
+    x_src, x_dst, e, agg, w1, b1, w2, b2, w3, b3, w4, b4, gam_e, _, gam_n, _, pall, ps = ctx.saved_tensors
+    net, g, same = ctx.net, ctx.graph, ctx.same
+    f, act, mean = net.channels, net.activation, net.aggr == "mean"
+    n_src, n_dst = g.num_src, g.num_dst
+    prec = net.precision
+    eps_e, eps_n = net.edge_norm.eps, net.node_norm.eps
+    with torch.no_grad():
+        lin = lambda x, w, b=None: ops.linear(x, w, b, contract=prec)                       # noqa: E731
+        x_src, x_dst, e = x_src.detach().contiguous(), x_dst.detach().contiguous(), e.detach().contiguous()
+        gx = gx.contiguous()
+        has_ge = bool(ctx.update_edges and ge is not None and ge.numel() > 0)
+        ge = ge.contiguous() if has_ge else None
+        w1t, w3t, w2t, w4t = (w.t().contiguous() for w in (w1, w3, w2, w4))
+        wet, wst, wdt, wxt, wat = w1t[:f], w1t[f:2 * f], w1t[2 * f:], w3t[:f], w3t[f:]
+        we, wa, _, _ = net._weight_blocks()
+        if same:
+            ps, pd, q = pall[:, :f], pall[:, f:2 * f], pall[:, 2 * f:]
+        else:
+            pd, q = pall[:, :f], pall[:, f:]
+        h1, d1 = _act_pair(lin(e, we), act, ps, g.src, pd, g.dst)
+        del ps, pd
+        h3, d3 = _act_pair(lin(agg, wa), act, q)
+        del pall, q
+        gb = ops.GradBatch()
+        gw = lambda a, b_: gb.grad_weight(a, b_, prec)                                       # noqa: E731
+        gwb = lambda a, b_: gb.grad_weight_bias(a, b_, prec)                                 # noqa: E731
+        # ---- node MLP: x' = x + LN_node(m3) ------------------------------------------------------------------------
+        g_m3, g_ln_n = ops.layer_norm_backward(lin(h3, w4, b4), gx, gam_n, eps_n, gb)
+        g_w4, g_b4 = gwb(g_m3, h3)
+        g_pre3 = _ew(_lib.EW_MUL, lin(g_m3, w4t), d3)
+        del h3, d3, g_m3
+        g_w3a, g_b3 = gwb(g_pre3, x_dst)
+        g_w3 = [g_w3a, gw(g_pre3, agg)]
+        g_agg = lin(g_pre3, wat)
+        g_xd = _ew(_lib.EW_ADD, lin(g_pre3, wxt), gx)
+        del g_pre3, agg
+        # ---- messages: m_e = LN_edge(m), gradient of m_e = ge + g_agg[dst] (/ degree) -----------------------------------
+        g_y = _gather_add(ge, g_agg, g.dst, g.inv_degree() if mean else None)
+        g_m, g_ln_e = ops.layer_norm_backward(lin(h1, w2, b2), g_y, gam_e, eps_e, gb)
+        del g_y, g_agg
+        g_b2, g_w2 = gb.grad_bias(g_m), gw(g_m, h1)
+        g_pre1 = _ew(_lib.EW_MUL, lin(g_m, w2t), d1)
+        del g_m, h1, d1
+        big_d = _segsum(g.segments("dst"), g_pre1, n_dst)
+        g_b1 = gb.grad_bias(big_d)
+        big_s = _segsum(g.segments("src"), g_pre1, n_src)
+        g_w1 = [gw(g_pre1, e), gw(big_s, x_src), gw(big_d, x_dst)]
+        gb.finish()
+        g_w1, g_w3 = torch.cat(g_w1, dim=1), torch.cat(g_w3, dim=1)
+        g_e = lin(g_pre1, wet)
+        if has_ge:
+            g_e = _ew(_lib.EW_ADD, g_e, ge)
+        del g_pre1
+        g_xs = lin(big_s, wst)
+        g_xd = _ew(_lib.EW_ADD, g_xd, lin(big_d, wdt))
+        if same:
+            g_xd = _ew(_lib.EW_ADD, g_xd, g_xs)
+            g_xs = None
+    need = ctx.needs_input_grad
+    pick = lambda k, t: t if need[k] else None                                              # noqa: E731
+    return (None, None, None, None, pick(4, g_xs), pick(5, g_xd), pick(6, g_e), pick(7, g_w1), pick(8, g_b1),
+            pick(9, g_w2), pick(10, g_b2), pick(11, g_w3), pick(12, g_b3), pick(13, g_w4), pick(14, g_b4),
+            pick(15, g_ln_e[:f]), pick(16, g_ln_e[f:]), pick(17, g_ln_n[:f]), pick(18, g_ln_n[f:]))

@@ -449,6 +449,97 @@ class GradBatch:
         self._tasks, self._keep = [], []
 
 
+def _layer_norm_args(x: Tensor, weight: Tensor, bias: Tensor, res: Optional[Tensor]) -> None:
+    if x.dim() != 2 or not _lib.lib().gwen_layer_norm_supported(x.size(-1)):
+        raise ValueError(f"layer_norm needs [rows, F] with F a multiple of 4 up to 1024; got {tuple(x.shape)}")
+    f = x.size(-1)
+    if tuple(weight.shape) != (f,) or tuple(bias.shape) != (f,):
+        raise ValueError("layer_norm: weight and bias must be [F]")
+    if res is not None and res.shape != x.shape:
+        raise ValueError("layer_norm: res must have the shape of x")
+    for name, t in (("x", x), ("weight", weight), ("bias", bias), ("res", res)):
+        if t is not None:
+            _require(t, name)
+
+
+def layer_norm_rows(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5, res: Optional[Tensor] = None,
+                    rowptr: Optional[Tensor] = None, n_dst: int = 0, mean: bool = False, want_out: bool = True):
+    """gwen_layer_norm_f32 without autograd: (out, agg) with out = (res +) LN(x) and -- given the ``rowptr`` of
+    target-sorted rows -- agg[d] = sum / mean of LN(x) over target d's rows in stored order, from the same pass."""
+    _layer_norm_args(x, weight, bias, res)
+    x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
+    res = None if res is None else res.contiguous()
+    rows, f = x.shape
+    dev = x.device
+    out = torch.empty_like(x) if want_out else None
+    agg = torch.empty(n_dst, f, dtype=torch.float32, device=dev) if rowptr is not None else None
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_layer_norm_f32(_ptr(x), _ptr(weight), _ptr(bias), eps, _ptr(res), _ptr(out), rows, f,
+                                            _ptr(rowptr), _ptr(agg), n_dst, int(mean), _stream(dev))
+    _lib.check(rc, "gwen_layer_norm_f32")
+    return out, agg
+
+
+def layer_norm_backward(x: Tensor, g: Tensor, weight: Tensor, eps: float, batch: Optional["GradBatch"] = None,
+                        want_params: bool = True):
+    """gwen_layer_norm_bwd_f32: (g_x, grad_weight | grad_bias as ONE [2 F] tensor, or None) for y = LN(x) and the
+    gradient ``g`` of y.  The parameter gradients are per-chunk partials finished in a fixed order -- with ``batch`` in
+    that GradBatch's one finish launch (complete after its ``finish()``), else here."""
+    x, g, weight = x.contiguous(), g.contiguous(), weight.contiguous()
+    rows, f = x.shape
+    dev = x.device
+    gx = torch.empty_like(x)
+    gp = torch.zeros(2 * f, dtype=torch.float32, device=dev) if want_params else None
+    if rows == 0:
+        return gx, gp
+    nch = int(_lib.lib().gwen_layer_norm_bwd_chunks(rows))
+    part = None
+    if want_params:
+        part = gp if nch == 1 else torch.empty(nch * 2 * f, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_layer_norm_bwd_f32(_ptr(x), _ptr(g), _ptr(weight), eps, _ptr(gx), _ptr(part), rows, f,
+                                                _stream(dev))
+    _lib.check(rc, "gwen_layer_norm_bwd_f32")
+    if want_params and nch > 1:
+        own = batch is None
+        batch = GradBatch() if own else batch
+        batch._dev = dev
+        batch._add(part, gp, 2 * f, nch)
+        if own:
+            batch.finish()
+    return gx, gp
+
+
+class LayerNormFunction(torch.autograd.Function):
+    """y = (res +) LN(x) on csrc/layernorm.hip, forward and backward (atomic-free: two runs are bitwise equal)."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, bias: Tensor, eps: float, res: Optional[Tensor]) -> Tensor:
+        out, _ = layer_norm_rows(x, weight, bias, eps, res)
+        ctx.save_for_backward(x, weight)
+        ctx.eps, ctx.has_res = eps, res is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        x, weight = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        f = x.size(-1)
+        g = g.contiguous()
+        gx, gp = layer_norm_backward(x.detach(), g, weight.detach(), ctx.eps, want_params=need[1] or need[2])
+        return (gx if need[0] else None, gp[:f] if need[1] else None, gp[f:] if need[2] else None, None,
+                g if ctx.has_res and need[4] else None)
+
+
+def layer_norm(x: Tensor, weight: Tensor, bias: Tensor, eps: float = 1e-5, res: Optional[Tensor] = None) -> Tensor:
+    """``(res +) torch.nn.functional.layer_norm(x, [F], weight, bias, eps)`` for fp32 ``[rows, F]`` (F a multiple of 4 up
+    to 1024): biased variance, formed from deviations about the mean; with autograd (x, weight, bias, res)."""
+    _layer_norm_args(x, weight, bias, res)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias, res)):
+        return LayerNormFunction.apply(x, weight, bias, eps, res)
+    return layer_norm_rows(x, weight, bias, eps, res)[0]
+
+
 def relu_backward(y: Tensor, g: Tensor) -> Tensor:
     y = y.contiguous(); g = g.contiguous()
     out = torch.empty_like(g)

@@ -510,6 +510,20 @@ int gwen_gnn_backward_f32(const struct gwen_graph *graph_t, const struct gwen_la
  *   of gwen_mlp2_supported (the backward: F in {64, 256}); GWEN_CONTRACT_F32 / BF16X6 return GWEN_EINVAL.
  *   workspace: gwen_mlp2_contract_workspace_bytes(F, contract) (F = 256: the images + 2 F int32 column exponents).
  *
+ * gwen_mlp2_ln_f32: gwen_mlp2_contract_f32 with a LayerNorm behind the second layer, before the residual and the sums:
+ *     y[r] = LN(act(pre[r]) W2^T + b2),   LN(m)_c = (m_c - mu) * rstd * ln_gamma_c + ln_beta_c,
+ *     mu = mean_c m_c,  var = mean_c (m_c - mu)^2 (BIASED),  rstd = 1 / sqrt(var + ln_eps)      (torch.nn.LayerNorm(F))
+ *   ln_gamma, ln_beta: fp32 [F], 16-byte aligned; both NULL: gwen_mlp2_contract_f32, the same launch bit for bit; one
+ *   NULL: GWEN_EINVAL.  ln_eps >= 0 (1e-5 is the usual value).  Statistics and the affine step are fp32 on both
+ *   contracts (the contract governs the two contractions only); the variance is formed from DEVIATIONS about the mean
+ *   in a second sweep over the row, never as E[m^2] - mu^2 (which loses rows whose mean is large against their
+ *   spread).  A row holding +-Inf or NaN gets NaN in every column of y (its mean is non-finite) and, with agg, in its
+ *   target's sum; every other row is untouched.  Fused instantiations exist for the launch shapes of the
+ *   InteractionNet block only -- gwen_mlp2_ln_supported(F, contract, shape): GWEN_MLP2_LN_EDGE = G1 and G2 both
+ *   indexed, agg, res == A (out optional); GWEN_MLP2_LN_NODE = G1 row for row, no G2, no agg, res != A -- at F = 64
+ *   (F = 256: the instantiations spill and are not built); every other call with ln_gamma returns GWEN_EINVAL before any launch, and the caller runs
+ *   gwen_mlp2_contract_f32 without res / agg followed by ONE gwen_layer_norm_f32 (same semantics).
+ *
  * gwen_edge_tiles: row-aligned tiling of a CSR's entries.  tile c owns the target rows whose first
  *   entry lies in [cT, (c+1)T); n_tiles = gwen_edge_tiles_count(E, T) = max(1, ceil(E/T)); T <= 128.
  *   T = gwen_mlp2_rows(F) - (max row length - 1) (at least 1) keeps each tile a single pass of the
@@ -541,6 +555,42 @@ int gwen_mlp2_contract_f32(const float *A, const float *W1, const float *G1, con
                            int64_t R, int64_t F, int act, const int32_t *rowptr, const int32_t *tile_row,
                            int64_t n_tiles, float *agg, int64_t N_agg, int mean, int contract, void *workspace,
                            size_t workspace_bytes, gwen_stream_t stream);
+#define GWEN_MLP2_LN_EDGE 0
+#define GWEN_MLP2_LN_NODE 1
+int gwen_mlp2_ln_supported(int64_t F, int contract, int shape);
+int gwen_mlp2_ln_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
+                     int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
+                     int64_t G2_rows, int64_t ldg2,
+                     const float *b1, const float *W2, const float *b2, const float *res, float *out,
+                     int64_t R, int64_t F, int act, const int32_t *rowptr, const int32_t *tile_row,
+                     int64_t n_tiles, float *agg, int64_t N_agg, int mean, int contract,
+                     const float *ln_gamma, const float *ln_beta, float ln_eps, void *workspace,
+                     size_t workspace_bytes, gwen_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Row LayerNorm, forward and backward (csrc/layernorm.hip) -- the unfused route of K6 with LayerNorm, the LayerNorm
+ * half of the InteractionNet block's backward, and gwen_amd.ops.layer_norm.  BUILD-DEFINED like the block; LN, eps,
+ * the biased variance and the deviations form exactly as under gwen_mlp2_ln_f32.  x, res, out, g, gx: fp32
+ * [rows, F] contiguous; gamma, beta: [F]; everything 16-byte aligned; gwen_layer_norm_supported(F): F % 4 == 0,
+ * F <= 1024.  A row holding +-Inf or NaN gets NaN in every column (and in its target's agg row / in its chunk of the
+ * gamma / beta partials); other rows are untouched.
+ *   gwen_layer_norm_f32:      out[r] = (res ? res[r] : 0) + LN(x[r])     (out may alias x or res row for row).
+ *                             With agg (then rowptr int32 [N_agg + 1], rowptr[N_agg] == rows: rows stored by target):
+ *                             agg[d] = sum (mean != 0: mean) of LN(x[r]) over rowptr[d] <= r < rowptr[d + 1], in stored
+ *                             order -- of LN(x), not of out; targets without rows get 0; out may then be NULL.
+ *   gwen_layer_norm_bwd_f32:  with y^ = (x - mu) rstd recomputed and gg = g * gamma:
+ *                             gx[r] = rstd (gg - mean_c(gg) - y^ mean_c(gg * y^))      (gx may alias g, not x);
+ *                             partial (may be NULL) [gwen_layer_norm_bwd_chunks(rows), 2 F]: per chunk of 256 rows
+ *                             [sum_r g * y^ | sum_r g] in a fixed order; grad_gamma | grad_beta = the sum over chunks
+ *                             (gwen_reduce_chunks_batched with count = 2 F).  Atomic-free: two runs bitwise equal.
+ * ------------------------------------------------------------------------------------------- */
+int gwen_layer_norm_supported(int64_t F);
+int gwen_layer_norm_f32(const float *x, const float *gamma, const float *beta, float eps, const float *res, float *out,
+                        int64_t rows, int64_t F, const int32_t *rowptr, float *agg, int64_t N_agg, int mean,
+                        gwen_stream_t stream);
+int64_t gwen_layer_norm_bwd_chunks(int64_t rows);
+int gwen_layer_norm_bwd_f32(const float *x, const float *g, const float *gamma, float eps, float *gx, float *partial,
+                            int64_t rows, int64_t F, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K6^T  pieces of the InteractionNet block's BACKWARD (build-defined like K6; serves the training step of the

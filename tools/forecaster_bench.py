@@ -2,8 +2,9 @@
 nu = 100 (100 002 vertices, 200 000 grid cells), 4 processor blocks, 4-step autoregressive rollout of M local
 members (c5: 32 members over 8 GPUs = 4 per GPU) -- all members through ONE launch set per step (block-diagonal
 graph) against one member after the other.
-python tools/forecaster_bench.py [grid_channels] [hidden] [steps] [members] [precision]   -> one JSON line
-(precision: "3xbf16", the default, or "f16x3" -- InteractionForecaster.set_precision)"""
+python tools/forecaster_bench.py [grid_channels] [hidden] [steps] [members] [precision] [layer_norm 0|1]   -> one JSON line
+(precision: "3xbf16", the default, or "f16x3" -- InteractionForecaster.set_precision; layer_norm: a LayerNorm behind both
+MLPs of every block, InteractionForecaster(layer_norm=True))"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, gwen_amd
@@ -13,10 +14,11 @@ H = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 S = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 M = int(sys.argv[4]) if len(sys.argv) > 4 else 4
 P = sys.argv[5] if len(sys.argv) > 5 else "3xbf16"
+LN = len(sys.argv) > 6 and sys.argv[6] not in ("0", "false", "False")
 dev = "cuda:0"
 mesh = gwen_amd.geodesic_mesh(100, reorder="hilbert")
 torch.manual_seed(23)
-model = InteractionForecaster(C, H, S, precision=P).to(dev).eval()
+model = InteractionForecaster(C, H, S, precision=P, layer_norm=LN).to(dev).eval()
 graphs = model.prepare(mesh, dev)
 x = torch.randn(mesh.faces.shape[0], C, device=dev)
 xm = torch.randn(M, mesh.faces.shape[0], C, device=dev)
@@ -55,4 +57,4 @@ print(json.dumps({"workload": f"InteractionNet forecaster nu=100 grid={mesh.face
                   "rollout4_ms_members_batched": round(d_batch * 1e3, 3),
                   "members_per_s_4step_batched": round(M / d_batch, 2),
                   "edge_updates_per_s_batched": round(4 * M * edges / d_batch), "batched_equals_loop_bitwise": bool(same),
-                  "precision": P, "two_rollouts_bitwise_equal": bool(torch.equal(r1, r2))}))
+                  "precision": P, "layer_norm": LN, "two_rollouts_bitwise_equal": bool(torch.equal(r1, r2))}))

@@ -2,7 +2,8 @@
 ms per step with the product's backward (K6^T: atomic-free launches of libgwen_hip.so, gwen_amd/interaction.py)
 and, for comparison, with round 2's backward -- the block restated in torch device ops (rocBLAS GEMMs,
 index_select, index_add_ float atomics) and differentiated by autograd, kept HERE only as the "before" of that
-comparison.      python tools/inet_train_bench.py [hidden] [blocks] [nu]   -> one JSON line"""
+comparison.      python tools/inet_train_bench.py [hidden] [blocks] [nu] [precision] [layer_norm 0|1]
+-> one JSON line  (layer_norm: InteractionForecaster(layer_norm=True); the torch comparison does not know it and is skipped)"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, gwen_amd
@@ -12,10 +13,12 @@ from gwen_amd.forecaster import InteractionForecaster
 H = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 S = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 NU = int(sys.argv[3]) if len(sys.argv) > 3 else 100
+P = sys.argv[4] if len(sys.argv) > 4 else "3xbf16"
+LN = len(sys.argv) > 5 and sys.argv[5] not in ("0", "false", "False")
 C, dev = 8, "cuda:0"
 mesh = gwen_amd.geodesic_mesh(NU, reorder="hilbert")
 torch.manual_seed(23)
-model = InteractionForecaster(C, H, S).to(dev).train()
+model = InteractionForecaster(C, H, S, precision=P, layer_norm=LN).to(dev).train()
 graphs = model.prepare(mesh, dev)
 x = torch.randn(mesh.faces.shape[0], C, device=dev)
 y = torch.randn(mesh.faces.shape[0], C, device=dev)
@@ -113,7 +116,7 @@ try:
     t_graph = float("nan") if os.environ.get("INET_SKIP_OLD") == "1" else round(graphed_step_ms(), 3)
 except Exception as exc:                                # capture is best effort: say why it did not work
     t_graph = f"not captured: {type(exc).__name__}: {str(exc)[:200]}"
-if os.environ.get("INET_SKIP_OLD") == "1":           # (profiling runs: only the product's kernels in the trace)
+if os.environ.get("INET_SKIP_OLD") == "1" or LN:     # (profiling runs: only the product's kernels in the trace)
     t_old = float("nan")
 else:
     keep = I._InteractionNetFunction.backward
@@ -134,4 +137,4 @@ print(json.dumps({"workload": f"InteractionNet forecaster training step, nu={NU}
                   "train_step_ms_k6t_backward": round(t_new * 1e3, 3),
                   "train_step_ms_replayed_from_a_hipgraph": t_graph,
                   "train_step_ms_torch_recompute_backward_round2": round(t_old * 1e3, 3),
-                  "inference_forward_ms": round(t_fwd * 1e3, 3)}))
+                  "inference_forward_ms": round(t_fwd * 1e3, 3), "precision": P, "layer_norm": LN}))
