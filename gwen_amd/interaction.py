@@ -172,6 +172,18 @@ def _mlp2_contract(contract: str) -> int:
     return MLP2_CONTRACTS[contract]
 
 
+TABLE_BYTES_LIMIT = 1 << 32      # K6 gathers table rows through 32-bit byte offsets: rows * row stride * 4 stays below this
+
+
+def _check_table(name: str, rows: int, ld: int) -> None:
+    """A gathered table of ``rows`` rows at a row stride of ``ld`` floats must span less than 2^32 bytes (the C layer
+    answers GWEN_ERANGE from ``rows * ld * 4 >= 2^32``): refused here, by name and size, before anything is launched."""
+    if rows * ld * 4 >= TABLE_BYTES_LIMIT:
+        raise ValueError(f"K6: table {name} spans {rows} rows x {ld * 4} bytes = {rows * ld * 4} bytes; the limit is "
+                         f"{TABLE_BYTES_LIMIT - 1} bytes (32-bit byte offsets), i.e. at most "
+                         f"{(TABLE_BYTES_LIMIT - 1) // (ld * 4)} rows at this row stride")
+
+
 def mlp2(a: Tensor, w1: Tensor, w2: Tensor, b2: Optional[Tensor] = None, *,
          g1: Optional[Tensor] = None, idx1: Optional[Tensor] = None, g2: Optional[Tensor] = None,
          idx2: Optional[Tensor] = None, b1: Optional[Tensor] = None, res: Optional[Tensor] = None,
@@ -210,6 +222,7 @@ def mlp2(a: Tensor, w1: Tensor, w2: Tensor, b2: Optional[Tensor] = None, *,
             if g.dim() != 2 or g.size(1) != f or g.stride(1) != 1 or g.stride(0) % 4 or g.stride(0) < f \
                     or g.data_ptr() % 16:
                 raise ValueError(f"{name} must be [rows, F] with unit column stride and 16-byte aligned rows")
+            _check_table(name, g.size(0), g.stride(0))
     rows = a.size(0)
     for name, idx, g in (("idx1", idx1, g1), ("idx2", idx2, g2)):
         if idx is not None and (g is None or idx.dtype != torch.int32 or idx.numel() != rows):
@@ -348,6 +361,12 @@ class InteractionNet(nn.Module):
         f = self.channels
         we, wa, wn, bn = self._weight_blocks()
         prec = self.precision
+        # the node projections are K6's gathered tables: too large a node set is refused before the first launch
+        if x_src is x_dst:
+            _check_table("[Ps | Pd | Q] (the stacked node projections)", graph.num_dst, 3 * f)
+        else:
+            _check_table("Ps (the source projections)", graph.num_src, f)
+            _check_table("[Pd | Q] (the target projections)", graph.num_dst, 2 * f)
         # (the default keeps exact=False: the launch it has always been; "f16x3" -> K3's fp32-class split)
         lin = (lambda x, w, b: ops.linear(x, w, b, exact=False)) if prec == "3xbf16" else \
             (lambda x, w, b: ops.linear(x, w, b, contract=prec))                                # noqa: E731
@@ -439,6 +458,15 @@ def _edge_backward(ge: Tensor, w2t: Tensor, d1: Tensor, t: Tensor, dst: Tensor, 
     return g_pre1[:rows], g_e
 
 
+def _fused_edge_backward(f: int, edges: int, n_dst: int) -> bool:
+    """Does the backward take the one-launch edge route (``_edge_backward``)?  Only where the kernel exists (64 and 256
+    channels) AND its 32-bit byte offsets reach: the edge rows (d1 is read as a table, row for row) and the per-node table
+    T [n_dst, F] both below 2^32 bytes -- gwen_mlp2_bwd_contract_f32 answers GWEN_ERANGE beyond.  Larger blocks (e.g. 7
+    batched members of the 100 002-node mesh at 256 channels) take the general walk, as 32 and 128 channels do."""
+    return bool(_lib.lib().gwen_mlp2_bwd_supported(f)) and edges * f * 4 < TABLE_BYTES_LIMIT \
+        and n_dst * f * 4 < TABLE_BYTES_LIMIT
+
+
 def _segsum(seg: Tuple[Tensor, Tensor, Tensor], h: Tensor, rows: int) -> Tensor:
     """K2 over an edge-position CSR (``EdgeGraph.segments``): out[i] = sum_s val[s] h[col[s]] in stored order."""
     rowptr, col, val = seg
@@ -506,7 +534,7 @@ class _InteractionNetFunction(torch.autograd.Function):
                 ps, pd, q = pall[:, :f], pall[:, f:2 * f], pall[:, 2 * f:]
             else:
                 pd, q = pall[:, :f], pall[:, f:]
-            fused_edge = bool(_lib.lib().gwen_mlp2_bwd_supported(f))
+            fused_edge = _fused_edge_backward(f, g.num_edges, n_dst)
             if fused_edge:       # (edges are stored by target: the hidden layer's per-target sums come out of the same pass)
                 h1, d1, hagg = _act_pair_seg(lin(e, we), act, ps, g.src, pd, g.rowptr, n_dst)
             else:
