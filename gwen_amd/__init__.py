@@ -5,7 +5,8 @@ UpConvLayers, GCNConvLayers, GNNModel, loss_func) plus the ``GCNConv`` layer it 
 torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); build it with
 ``python -m gwen_amd.build``.
 """
-from . import forecaster, g2m, interaction, losses, noise, ops
+from . import attention, forecaster, g2m, interaction, losses, noise, ops
+from .attention import GraphTransformer, edge_attention, edge_attention_kv
 from .forward import GraphedForward, KernelEvents, StackForward, event_bracket_overhead
 from .gcn_conv import GCNConv, Linear
 from .forecaster import InteractionForecaster
@@ -21,6 +22,6 @@ __all__ = [
     "GCNConv", "Linear", "GraphedForward", "KernelEvents", "StackForward", "event_bracket_overhead", "GraphCSR", "GraphCache", "default_cache", "prepare_graph", "Mesh",
     "complete_graph", "geodesic_mesh", "DownConvLayers", "GCNConvLayers", "GNNConfig", "GNNModel",
     "UpConvLayers", "loss_func", "InteractionNet", "InteractionForecaster", "EdgeGraph", "interaction_graph",
-    "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream",
+    "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream", "GraphTransformer", "edge_attention", "edge_attention_kv",
 ]
 __version__ = "0.1.0"

@@ -12,6 +12,8 @@ the CPU in oracle/interaction_oracle.py):
     vm      = Encoder(vg, vm, e_g2m)        InteractionNet, grid -> mesh   (gwen_amd/interaction.py, K6)
     vm, e_m = Processor_k(vm, vm, e_m)      InteractionNet, mesh -> mesh,  k = 1..steps
     vg      = Decoder(vm, vg, e_m2g)        InteractionNet, mesh -> grid
+    (``processor="transformer"``: the processor blocks are ``attention.GraphTransformer``s instead -- multi-head attention
+     over a mesh node's in-edges with the edge term ee_k = lin_e_k(e_m), a static embedding like e_m itself)
     grid_y  = grid_x + vg Wo^T + bo                                          (residual read-out, K3)
 
 The grid is the set of triangle centres of the geodesic mesh; every cell is linked with its three
@@ -31,6 +33,7 @@ from torch import Tensor, nn
 from . import noise as noise_mod
 from . import ops
 from .g2m import grid_mesh_edges
+from .attention import GraphTransformer
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
 from .mesh import Mesh
 
@@ -88,12 +91,22 @@ class InteractionForecaster(nn.Module):
 
     ``layer_norm=True`` (off by default; ``norm_eps``): the encoder, every processor block and the decoder normalise both
     MLP outputs (``InteractionNet(layer_norm=True)``: m_e = LN(MLP_e(..)), x' = x + LN(MLP_n(..))); the embedders and the
-    read-out stay plain ``Linear``s."""
+    read-out stay plain ``Linear``s.
+
+    ``processor="transformer"`` (default "interaction"; ``heads``, 8 by default): the ``steps`` processor blocks are
+    ``attention.GraphTransformer(hidden, heads)``s over the mesh graph -- pre-norm attention with an edge term and a
+    feed-forward half; they carry their own LayerNorms (``norm_eps``), whatever ``layer_norm`` says, which then applies
+    to the encoder and the decoder only.  Each block's edge term ``lin_e(e_m)`` depends on weights only and joins the
+    static embeddings: a rollout step holds no edge-sized dense product.  Mesh edges are not updated.  Encoder and
+    decoder stay InteractionNet; everything else (members, noise, graphed rollouts, ``set_precision``) works alike."""
 
     def __init__(self, grid_channels: int, hidden: int, steps: int = 4, activation: str = "silu",
                  aggr: str = "sum", precision: str = "3xbf16", noise_channels: int = 0, layer_norm: bool = False,
-                 norm_eps: float = 1e-5):
+                 norm_eps: float = 1e-5, processor: str = "interaction", heads: int = 8):
         super().__init__()
+        if processor not in ("interaction", "transformer"):
+            raise ValueError(f"processor must be 'interaction' or 'transformer', got {processor!r}")
+        self.processor_kind = processor
         self.grid_channels, self.hidden, self.steps = grid_channels, hidden, steps
         self.grid_embed = nn.Linear(grid_channels, hidden)
         self.mesh_embed = nn.Linear(3, hidden)
@@ -103,7 +116,12 @@ class InteractionForecaster(nn.Module):
         ln = {"layer_norm": True, "norm_eps": norm_eps} if layer_norm else {}        # (off: the blocks as they were)
         self.layer_norm = bool(layer_norm)
         self.encoder = InteractionNet(hidden, activation, aggr, **ln)
-        self.processor = nn.ModuleList([InteractionNet(hidden, activation, aggr, **ln) for _ in range(steps)])
+        if processor == "transformer":
+            self.heads = heads
+            self.processor = nn.ModuleList([GraphTransformer(hidden, heads, activation, norm_eps=norm_eps)
+                                            for _ in range(steps)])
+        else:
+            self.processor = nn.ModuleList([InteractionNet(hidden, activation, aggr, **ln) for _ in range(steps)])
         self.decoder = InteractionNet(hidden, activation, aggr, **ln)
         self.readout = nn.Linear(hidden, grid_channels)
         self.set_precision(precision)
@@ -148,14 +166,17 @@ class InteractionForecaster(nn.Module):
 
     def _static(self, graphs: ForecastGraphs):
         lin = self._lin
-        return (lin(graphs.mesh_pos, self.mesh_embed), lin(graphs.f_g2m, self.g2m_edge_embed),
-                lin(graphs.f_mesh, self.mesh_edge_embed), lin(graphs.f_m2g, self.m2g_edge_embed))
+        static = (lin(graphs.mesh_pos, self.mesh_embed), lin(graphs.f_g2m, self.g2m_edge_embed),
+                  lin(graphs.f_mesh, self.mesh_edge_embed), lin(graphs.f_m2g, self.m2g_edge_embed))
+        if self.__dict__.get("processor_kind", "interaction") == "transformer":      # (a model pickled before: interaction)
+            static += ([net.edge_term(static[2]) for net in self.processor],)        # every block's ee = lin_e(e_m)
+        return static
 
     def _step(self, grid_x: Tensor, graphs: ForecastGraphs, static, out: Optional[Tensor] = None,
               noise: Optional["noise_mod.NoiseStream"] = None, member0: int = 0) -> Tensor:
         """One step; with ``noise``: the latent noise of members ``member0 ..`` at the stream's draw, which the step
         then advances by one (in stream order: captured with the step)."""
-        vm, e_g2m, e_m, e_m2g = static
+        vm, e_g2m, e_m, e_m2g, *ees = static
         vg = self._lin(grid_x, self.grid_embed)
         vm, _ = self.encoder(vg, vm, e_g2m, graphs.g2m, update_edges=False)
         if noise is not None:
@@ -164,8 +185,12 @@ class InteractionForecaster(nn.Module):
                 grad = torch.is_grad_enabled() and (vm.requires_grad or wz.requires_grad)
                 vm = noise_mod.inject(vm, wz, noise, graphs.mesh_nodes, member0, out=None if grad else vm)
             noise.advance(1)
-        for net in self.processor:
-            vm, e_m = net(vm, vm, e_m, graphs.mesh)
+        if ees:                                                    # processor="transformer": attention blocks
+            for net, ee in zip(self.processor, ees[0]):
+                vm, _ = net(vm, vm, e_m, graphs.mesh, ee=ee)
+        else:
+            for net in self.processor:
+                vm, e_m = net(vm, vm, e_m, graphs.mesh)
         vg, _ = self.decoder(vm, vg, e_m2g, graphs.m2g, update_edges=False)
         delta = self._lin(vg, self.readout)
         return grid_x + delta if out is None else torch.add(grid_x, delta, out=out)      # (out: GraphedStep's buffers)

@@ -704,6 +704,49 @@ int gwen_noise_inject_f32(const uint64_t *state, int64_t member0, int64_t rows, 
                           const float *wz, int64_t H, int64_t K, float *out, gwen_stream_t stream);
 int gwen_noise_advance(uint64_t *state, int64_t n, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Edge attention (csrc/attention.hip): multi-head softmax attention of every target over its in-edges with an edge
+ * term -- the kernel of gwen_amd.attention.GraphTransformer, forward and backward.  BUILD-DEFINED, PARITY UNPINNED (the
+ * reference has no attention); PyG TransformerConv with edge_dim.  H heads, D = F / H, s(e) / d(e) the source / target of
+ * stored edge e (edges stored by target: rowptr int32 [Nd + 1], src int32 [E]):
+ *     sc[e,h]  = (1 / sqrt(D)) sum_{c in head h} q[d(e),c] (k[s(e),c] + ee[e,c])
+ *     p[e,h]   = exp(sc[e,h] - lse[d(e),h]),   lse[d,h] = log sum_{e into d} exp(sc[e,h])
+ *     out[d,c] = sum_{e into d} p[e,h(c)] (v[s(e),c] + ee[e,c])
+ * in stored edge order, as a running-maximum ("online") softmax: no logit magnitude overflows.  A target without
+ * in-edges gets out = 0 and lse = -inf.  ee [E, F] contiguous, in stored order, may be NULL (= 0).  fp32 throughout.
+ * gwen_edge_attention_supported(F, H): F in {32, 64, 128, 256}, H a power of two, D >= 4.
+ * q [Nd, F], k, v [Ns, F] with row strides ldq / ldk / ldv in floats (multiples of 4, >= F: column blocks of a
+ * stacked projection); out, g [Nd, F] and lse [Nd, H] contiguous.  Feature pointers 16-byte aligned.  Row offsets are
+ * 64-bit: no array has a size limit of its own; Nd, Ns or E >= 2^31 answer GWEN_ERANGE.  Outputs alias no input.
+ *   gwen_edge_attention_f32:            out, lse.
+ *   gwen_edge_attention_bwd_target_f32: pass T, one lane group per target; g = dL/dout, delta[d,h] = sum_{c in h} g out,
+ *         dp[e,h] = sum_{c in h} g[d(e),c] (v[s(e),c] + ee[e,c]),   ds[e,h] = p[e,h] (dp[e,h] - delta[d(e),h]):
+ *         gq[d] = (1 / sqrt(D)) sum_{e into d} ds[e,h] (k[s(e)] + ee[e])       [Nd, F] contiguous (0 without in-edges)
+ *         gee[e] = (1 / sqrt(D)) ds[e,h] q[d(e)] + p[e,h] g[d(e)]              [E, F], written when ee is given
+ *         P[e,h] = p, DS[e,h] = ds                                             [E, H] each, for pass S
+ *   gwen_edge_attention_bwd_source_f32: pass S, one lane group per source over (src_rowptr int32 [Ns + 1], src_col
+ *         int32 [E]: the stored positions of a source's out-edges, ascending) and dst int32 [E]:
+ *         gk[s] = (1 / sqrt(D)) sum_{e out of s} ds[e,h] q[d(e)],   gv[s] = sum_{e out of s} p[e,h] g[d(e)]
+ *         with row strides ldgk / ldgv (one [Ns, 2F] array may take both); a source without out-edges gets 0.
+ * No atomics, fixed summation orders: two runs are bitwise equal.  Nothing allocates or synchronises (capturable).
+ * Zero-sized calls (Nd == 0; Ns == 0 for pass S) return GWEN_OK before any HIP call; NULL or misaligned arguments
+ * GWEN_EINVAL.  Non-finite inputs: a target whose in-edges (or own q row) carry +-Inf / NaN comes out non-finite in
+ * that row of out / lse / gq and in those edges' rows of gee / P / DS (hence in gk / gv of their sources) only.
+ * ------------------------------------------------------------------------------------------- */
+int gwen_edge_attention_supported(int64_t F, int64_t H);
+int gwen_edge_attention_f32(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v, int64_t ldv,
+                            const float *ee, const int32_t *rowptr, const int32_t *src, int64_t Nd, int64_t Ns,
+                            int64_t E, int64_t F, int64_t H, float *out, float *lse, gwen_stream_t stream);
+int gwen_edge_attention_bwd_target_f32(const float *q, int64_t ldq, const float *k, int64_t ldk, const float *v,
+                                       int64_t ldv, const float *ee, const int32_t *rowptr, const int32_t *src,
+                                       const float *g, const float *out, const float *lse, int64_t Nd, int64_t Ns,
+                                       int64_t E, int64_t F, int64_t H, float *gq, float *gee, float *P, float *DS,
+                                       gwen_stream_t stream);
+int gwen_edge_attention_bwd_source_f32(const int32_t *src_rowptr, const int32_t *src_col, const int32_t *dst,
+                                       const float *q, int64_t ldq, const float *g, const float *P, const float *DS,
+                                       int64_t Ns, int64_t Nd, int64_t E, int64_t F, int64_t H, float *gk, int64_t ldgk,
+                                       float *gv, int64_t ldgv, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
