@@ -6,6 +6,7 @@ torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); bui
 ``python -m gwen_amd.build``.
 """
 from . import attention, forecaster, g2m, interaction, losses, noise, ops
+from . import products
 from .attention import GraphTransformer, edge_attention, edge_attention_kv
 from .forward import GraphedForward, KernelEvents, StackForward, event_bracket_overhead
 from .gcn_conv import GCNConv, Linear
@@ -13,6 +14,7 @@ from .forecaster import InteractionForecaster
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
 from .losses import EnsembleCRPSLoss, ensemble_crps, ensemble_scores
 from .noise import NoiseStream
+from .products import ensemble_products, ensemble_quantiles, exceedance_probability, rank_histogram
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
 from .models_gnn import (DownConvLayers, GCNConvLayers, GNNConfig, GNNModel, UpConvLayers,
@@ -23,5 +25,6 @@ __all__ = [
     "complete_graph", "geodesic_mesh", "DownConvLayers", "GCNConvLayers", "GNNConfig", "GNNModel",
     "UpConvLayers", "loss_func", "InteractionNet", "InteractionForecaster", "EdgeGraph", "interaction_graph",
     "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream", "GraphTransformer", "edge_attention", "edge_attention_kv",
+    "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
 ]
 __version__ = "0.1.0"

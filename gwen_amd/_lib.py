@@ -192,6 +192,9 @@ SIGNATURES = {
     "gwen_masked_l1_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "gwen_ens_crps_workspace_floats": (_i64, [_i64, _i64, _i64]),
     "gwen_ens_crps_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gwen_ens_products_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "gwen_ens_rank_hist_workspace_floats": (_i64, [_i64, _i64, _i64]),
+    "gwen_ens_rank_hist_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp]),
     "gwen_noise_normal_f32": (_int, [_vp, C.c_uint64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "gwen_noise_inject_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gwen_noise_advance": (_int, [_vp, _i64, _vp]),

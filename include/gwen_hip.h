@@ -677,6 +677,50 @@ int gwen_ens_crps_f32(const float *pred, const float *target, const float *node_
                       float *scores, float *workspace, int64_t workspace_floats, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Ensemble products over the members axis (csrc/products.hip): per-point mean, spread, quantiles and exceedance
+ * probabilities in ONE launch that reads every point once.  BUILD-DEFINED (the reference has none of these).
+ * pred fp32 [M, N, C] (members first, contiguous), 1 <= M <= 64, N >= 1, C >= 1.  Every output is optional (NULL = not
+ * wanted; Q = 0 / T = 0 likewise), at least one must be asked for.  For a point with members x_0..x_{M-1}:
+ *     mean[n,c]  = r + (1/M) sum_i (x_i - r),  r = x_0            (differences to a member: no cancellation at offsets)
+ *     std[n,c]   = sqrt(sum_i ((x_i - r) - dbar)^2 / (M - 1)),  dbar = (1/M) sum_i (x_i - r)
+ *                  unbiased, from deviations about the mean, never E[x^2] - mean^2; M = 1 gives NaN, as torch
+ *     quantiles[j,n,c], j < Q <= 32, q DEVICE fp32 [Q] in [0, 1]: numpy / torch "linear".  s = the members sorted
+ *                  ascending, pos = q[j] (M - 1) rounded once in fp32, lo = floor(pos), frac = pos - lo;
+ *                  frac == 0: s[lo], copied (q = 0 / 1 return the minimum / maximum, infinite ones too);
+ *                  else s[lo] + frac (s[lo + 1] - s[lo]).  A q outside [0, 1] or NaN gives NaN.
+ *     prob[t,n,c], t < T <= 32 = #{i : x_i > thr} / M, strict; thr DEVICE fp32 [T] (thr_per_channel = 0: thr[t]) or
+ *                  [T, C] (thr_per_channel = 1: thr[t, c]).
+ * NaN / Inf: a point with a NaN member has NaN in every quantile, in mean and in std, and no other point is touched;
+ * prob counts a NaN member as not exceeding, as (pred > thr).float().mean(0).  +-Inf members sort as values; mean and
+ * std of a point that has one are +-Inf or NaN, as the expressions above give.
+ * Offsets are 64-bit.  C % 4 == 0 with 16-byte aligned pred / mean / std / prob, Q = 0 and M <= 16 reads 16 bytes per
+ * lane (4 channels a thread); everything else 4 bytes per lane (quantiles sort one point per thread in registers);
+ * every element is computed by the same operations on either path: the same bits.  One launch over persistent blocks
+ * sized by occupancy, no workspace, no atomics, no allocation, no synchronisation.  Compulsory bytes:
+ * 4 N C (M + Q + T + 2) with everything asked for.  Bad arguments (M, N, C, Q, T out of range, thr_per_channel not
+ * 0 / 1, a missing or not 4-byte aligned pointer, nothing asked for) give GWEN_EINVAL before any HIP call.
+ *
+ * Rank (Talagrand) histogram of target fp32 [N, C] in pred: hist fp32 [C, M + 1].  For a point, b = #{i : x_i < y}
+ * and t = #{i : x_i == y}: each of the bins b..b+t receives w_n / (t + 1) (the mid-rank split of ties: the
+ * expectation of random tie-breaking).  node_w fp32 [N] or NULL (ones).  A point whose target or any member is NaN is
+ * not counted; +-Inf compare as values.  normalize != 0 divides every channel's row by its own sum (a row that counted
+ * nothing is NaN).  Two launches: per node chunk a partial histogram per channel, accumulated per thread in node order
+ * and over the block's rows in row order (LDS), then a fixed-order sum over the chunks; no atomics, and the chunking is
+ * a function of (M, N, C) alone, so two runs -- and runs on buffers of different alignment -- are bitwise equal.
+ * workspace: gwen_ens_rank_hist_workspace_floats(M, N, C) = chunks * C * (M + 1) floats, with
+ *     chunks = min(ceil(N / rows), 1024, max(1, 2^22 / (C (M + 1)))),  rows = threads / min(C, threads),
+ *     threads = 256 (M <= 32) or 128:    at most 1024 chunks and at most 16 MiB (C (M + 1) floats if that is more).
+ * Bad arguments, or a shorter workspace, give GWEN_EINVAL before any HIP call (the size function returns 0).
+ * ------------------------------------------------------------------------------------------- */
+int gwen_ens_products_f32(const float *pred, int64_t M, int64_t N, int64_t C, const float *q, int64_t Q,
+                          const float *thr, int64_t T, int thr_per_channel, float *mean, float *std,
+                          float *quantiles, float *prob, gwen_stream_t stream);
+int64_t gwen_ens_rank_hist_workspace_floats(int64_t M, int64_t N, int64_t C);
+int gwen_ens_rank_hist_f32(const float *pred, const float *target, const float *node_w, int64_t M, int64_t N,
+                           int64_t C, int normalize, float *hist, float *workspace, int64_t workspace_floats,
+                           gwen_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Latent noise: reproducible Gaussian noise per ensemble member, a pure function of
  *     z(seed, tag, draw, member, node, k),   k = channel of a noise vector.
  * Philox4x64-10 (numpy.random.Philox) with key = (seed, tag) and counter = (node, member, draw, k / 8), 64-bit words,
