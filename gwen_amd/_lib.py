@@ -42,6 +42,7 @@ _lib = None
 _lock = threading.Lock()
 
 _vp, _i64, _int, _f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
+_f64 = C.c_double
 
 
 
@@ -203,6 +204,13 @@ SIGNATURES = {
     "gwen_edge_attention_bwd_target_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_i64] * 5 + [_vp] * 5),
     "gwen_edge_attention_bwd_source_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp] + [_i64] * 5 +
                                            [_vp, _i64, _vp, _i64, _vp]),
+    "gwen_gridgraph_cells": (_int, [_f64]),
+    "gwen_radius_edges_workspace_bytes": (_int, [_i64, _i64, C.POINTER(C.c_size_t)]),
+    "gwen_radius_edges_count": (_int, [_vp, _i64, _vp, _i64, _f64, _vp, _vp, C.c_size_t, _vp]),
+    "gwen_radius_edges_fill_workspace_bytes": (_int, [_i64, C.POINTER(C.c_size_t)]),
+    "gwen_radius_edges_fill": (_int, [_vp, _i64, _vp, _i64, _f64, _i64, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    "gwen_containing_faces_workspace_bytes": (_int, [_i64, C.POINTER(C.c_size_t)]),
+    "gwen_containing_faces": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 
 

@@ -17,7 +17,8 @@ the CPU in oracle/interaction_oracle.py):
     grid_y  = grid_x + vg Wo^T + bo                                          (residual read-out, K3)
 
 The grid is the set of triangle centres of the geodesic mesh; every cell is linked with its three
-corner vertices (gwen_amd/g2m.py).  Static embeddings (vm, e_*) depend on the weights only and are
+corner vertices (gwen_amd/g2m.py) -- or, with ``prepare(..., grid_pos=)``, any point set on the sphere, linked to the
+mesh by radius (grid -> mesh) and by containing face (mesh -> grid) (gwen_amd/gridgraph.py).  Static embeddings (vm, e_*) depend on the weights only and are
 computed once per ``forward`` / ``rollout`` call.  Trainable (``interaction._InteractionNetFunction``).  A leading members axis
 ``[members, N_grid, C]`` runs as ONE launch set over the block-diagonal graph (``ForecastGraphs.batched``).
 """
@@ -74,6 +75,11 @@ class ForecastGraphs:
     def mesh_nodes(self) -> int:
         """Mesh nodes of ONE member."""
         return self.mesh_pos.size(0) // self.__dict__.get("members", 1)
+
+    @property
+    def grid_nodes(self) -> int:
+        """Grid points of ONE member: the rows of the ``grid_x`` these graphs take."""
+        return self.g2m.num_src // self.__dict__.get("members", 1)
 
 
 class InteractionForecaster(nn.Module):
@@ -140,7 +146,15 @@ class InteractionForecaster(nn.Module):
         return self
 
     @staticmethod
-    def prepare(mesh: Mesh, device) -> ForecastGraphs:
+    def prepare(mesh: Mesh, device, grid_pos=None, radius: Optional[float] = None) -> ForecastGraphs:
+        """``grid_pos=None``: the grid is the mesh's own triangle centres.  ``grid_pos`` ``[N, 3]`` (any points on the
+        sphere: ``gridgraph.latlon_grid``, ``gridgraph.sphere_points`` of ICON cell centres, ...): the grid <-> mesh
+        graphs come from ``gridgraph.grid_graphs`` -- every grid point sends to the mesh nodes within ``radius`` (default
+        0.6 x the longest mesh edge) and receives from the corners of the mesh face that contains it."""
+        if grid_pos is not None:
+            return _prepare_on_grid(mesh, device, grid_pos, radius)
+        if radius is not None:
+            raise ValueError("radius applies to grid_pos; the default grid is linked to the corners of its own faces")
         g2m, m2g = grid_mesh_edges(mesh)
         n_mesh, n_grid = mesh.num_nodes, mesh.faces.shape[0]
         cell = mesh.pos[mesh.faces].mean(axis=1)
@@ -227,6 +241,22 @@ class InteractionForecaster(nn.Module):
                     self._step(cur, graphs, static, noise=noise, member0=member0)
                 states.append(cur)
         return states
+
+
+def _prepare_on_grid(mesh: Mesh, device, grid_pos, radius: Optional[float]) -> ForecastGraphs:
+    """``InteractionForecaster.prepare`` for given grid points: edges from ``gridgraph.grid_graphs`` (built on the device),
+    features ``[length, dx, dy, dz]`` over the normalised points, as on the default grid."""
+    from . import gridgraph
+    grid = gridgraph.unit_vectors(grid_pos, "grid_pos")
+    g2m_t, m2g_t, _ = gridgraph.grid_graphs(mesh, grid_pos, device, radius)
+    n_mesh, n_grid = mesh.num_nodes, grid.shape[0]
+    gs = (interaction_graph(g2m_t, n_grid, n_mesh),
+          interaction_graph(torch.from_numpy(mesh.edge_index).to(device), n_mesh, n_mesh),
+          interaction_graph(m2g_t, n_mesh, n_grid))
+    feats = (edge_features(grid, mesh.pos, g2m_t.cpu().numpy()), edge_features(mesh.pos, mesh.pos, mesh.edge_index),
+             edge_features(mesh.pos, grid, m2g_t.cpu().numpy()))
+    fs = [g.sort_edges(torch.from_numpy(f).to(device)) for g, f in zip(gs, feats)]
+    return ForecastGraphs(*gs, torch.from_numpy(mesh.pos.astype(np.float32)).to(device), *fs)
 
 
 def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,

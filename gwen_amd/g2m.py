@@ -64,13 +64,23 @@ class GridMeshGridModel(nn.Module):
         self.processor = nn.ModuleList([GCNConv(hidden, hidden) for _ in range(steps)])
         self.decoder = BipartiteConv(hidden, grid_channels)
 
-    def prepare(self, mesh: Mesh, device) -> "GridMeshGraphs":
-        g2m, m2g = grid_mesh_edges(mesh)
-        n_mesh, n_grid = mesh.num_nodes, mesh.faces.shape[0]
+    def prepare(self, mesh: Mesh, device, grid_pos=None, radius=None) -> "GridMeshGraphs":
+        """``grid_pos`` ``[N, 3]`` (with ``radius``): any grid on the sphere, linked by ``gridgraph.grid_graphs`` instead of
+        the mesh's own triangle centres."""
+        n_mesh = mesh.num_nodes
+        if grid_pos is None:
+            if radius is not None:
+                raise ValueError("radius applies to grid_pos")
+            g2m, m2g = (torch.from_numpy(e).to(device) for e in grid_mesh_edges(mesh))
+            n_grid = mesh.faces.shape[0]
+        else:
+            from . import gridgraph
+            g2m, m2g, info = gridgraph.grid_graphs(mesh, grid_pos, device, radius)
+            n_grid = info["grid_nodes"]
         return GridMeshGraphs(
-            g2m=prepare_bipartite(torch.from_numpy(g2m).to(device), n_grid, n_mesh),
+            g2m=prepare_bipartite(g2m, n_grid, n_mesh),
             mesh=prepare_graph(torch.from_numpy(mesh.edge_index).to(device), n_mesh),
-            m2g=prepare_bipartite(torch.from_numpy(m2g).to(device), n_mesh, n_grid))
+            m2g=prepare_bipartite(m2g, n_mesh, n_grid))
 
     def forward(self, grid_x: Tensor, graphs: "GridMeshGraphs") -> Tensor:
         h = self.encoder(grid_x, graphs.g2m, relu=True)

@@ -58,6 +58,14 @@ class Mesh:
         den = 1.0 + np.einsum("ij,ij->i", a, b) + np.einsum("ij,ij->i", b, c) + np.einsum("ij,ij->i", c, a)
         return 2.0 * np.arctan2(num, den)
 
+    def max_edge_length(self) -> float:
+        """The longest chord over ``edge_index`` (0.0 without edges): the length scale of the grid graphs
+        (``gwen_amd.gridgraph``: the default grid -> mesh radius is 0.6 of it)."""
+        if self.edge_index.shape[1] == 0:
+            return 0.0
+        d = self.pos[self.edge_index[1]] - self.pos[self.edge_index[0]]
+        return float(np.sqrt((d * d).sum(axis=1).max()))
+
 
 def _morton3(pos: np.ndarray, bits: int = 10) -> np.ndarray:
     q = np.clip(((pos + 1.0) * 0.5 * ((1 << bits) - 1)).round().astype(np.uint64), 0, (1 << bits) - 1)

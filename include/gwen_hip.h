@@ -791,6 +791,48 @@ int gwen_edge_attention_bwd_source_f32(const int32_t *src_rowptr, const int32_t 
                                        int64_t Ns, int64_t Nd, int64_t E, int64_t F, int64_t H, float *gk, int64_t ldgk,
                                        float *gv, int64_t ldgv, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Grid graphs (csrc/gridgraph.hip): the grid <-> mesh graphs of the forecaster for arbitrary grid points.
+ * BUILD-DEFINED, PARITY UNPINNED (the reference has no grid <-> mesh graphs: SURVEY section 0).  Positions are fp64
+ * [n, 3] row-major, on (or near) the unit sphere: every coordinate in [-1, 1] (anything outside is clamped into the
+ * outermost cell, so results stay correct, only slower).  A fixed-radius query runs through a uniform cell list over
+ * [-1, 1]^3 with gwen_gridgraph_cells(R) = clamp(floor(2 / R), 1, 128) cells per axis (128: the dense cell-start table
+ * is 8 MiB), points ordered by cell with one radix sort of unique 64-bit keys.  No atomics; two runs are bitwise equal.
+ * radius must be finite and > 0 (GWEN_EINVAL); a count >= 2^31 - 1 is GWEN_ERANGE.
+ *
+ *   gwen_radius_edges_count: total int64 [1] (DEVICE) = the number of pairs (s, d) with
+ *         (dx dx + dy dy) + dz dz <= R R,   (dx, dy, dz) = dst_pos[d] - src_pos[s],   fp64, in this association
+ *         (no fused multiply-add), summed in 64 bits.  The larger of the two sets queries a cell list of the smaller
+ *         (one thread per querying point); list and per-point offsets stay in `workspace`
+ *         (gwen_radius_edges_workspace_bytes(num_src, num_dst)) for the fill.
+ *   gwen_radius_edges_fill:  edge_index int64 [2, E] row-major (row 0 = s, row 1 = d), sorted by (d, s) ascending, and
+ *         rowptr int32 [num_dst + 1] over it; E is the total the host read back, positions, sizes, radius and
+ *         `workspace` are those of the count, untouched since; sort_workspace: gwen_radius_edges_fill_workspace_bytes(E).
+ *         E >= 2^31 - 1 is GWEN_ERANGE; nothing is ever written at or beyond edge E.  E == 0 writes rowptr only.
+ *   gwen_containing_faces:   for every point p the LOWEST face id f = (a, b, c) -- among the faces whose `centres` row is
+ *         within `radius` of p by the expression above -- with det(p,b,c), det(p,c,a), det(p,a,b) all >= -1e-12, where
+ *         det(u,v,w) = (u0 (v1 w2 - v2 w1) + u1 (v2 w0 - v0 w2)) + u2 (v0 w1 - v1 w0); weights fp64 [n, 3] = the three
+ *         determinants over ((d0 + d1) + d2), so that sum_i w_i vertex_i is parallel to p.  face int32 [n] = -1 (weights 0)
+ *         where no candidate contains p.  faces int64 [num_faces, 3] into mesh_pos [num_nodes, 3], positively oriented;
+ *         a face with an index outside [0, num_nodes) contains nothing.
+ *         workspace: gwen_containing_faces_workspace_bytes(num_faces).
+ * ------------------------------------------------------------------------------------------- */
+int gwen_gridgraph_cells(double radius);
+int gwen_radius_edges_workspace_bytes(int64_t num_src, int64_t num_dst, size_t *bytes /* host */);
+int gwen_radius_edges_count(const double *src_pos, int64_t num_src, const double *dst_pos, int64_t num_dst,
+                            double radius, int64_t *total, void *workspace, size_t workspace_bytes,
+                            gwen_stream_t stream);
+int gwen_radius_edges_fill_workspace_bytes(int64_t E, size_t *bytes /* host */);
+int gwen_radius_edges_fill(const double *src_pos, int64_t num_src, const double *dst_pos, int64_t num_dst,
+                           double radius, int64_t E, int32_t *rowptr, int64_t *edge_index, const void *workspace,
+                           size_t workspace_bytes, void *sort_workspace, size_t sort_workspace_bytes,
+                           gwen_stream_t stream);
+int gwen_containing_faces_workspace_bytes(int64_t num_faces, size_t *bytes /* host */);
+int gwen_containing_faces(const double *points, int64_t n, const double *mesh_pos, int64_t num_nodes,
+                          const int64_t *faces, const double *centres, int64_t num_faces, double radius,
+                          int32_t *face, double *weights, void *workspace, size_t workspace_bytes,
+                          gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
