@@ -5,7 +5,7 @@ UpConvLayers, GCNConvLayers, GNNModel, loss_func) plus the ``GCNConv`` layer it 
 torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); build it with
 ``python -m gwen_amd.build``.
 """
-from . import attention, forecaster, g2m, gridgraph, interaction, losses, noise, ops
+from . import attention, forcings, forecaster, g2m, gridgraph, interaction, losses, noise, ops
 from . import products
 from .attention import GraphTransformer, edge_attention, edge_attention_kv
 from .forward import GraphedForward, KernelEvents, StackForward, event_bracket_overhead
@@ -14,6 +14,7 @@ from .forecaster import InteractionForecaster
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
 from .losses import EnsembleCRPSLoss, ensemble_crps, ensemble_scores
 from .noise import NoiseStream
+from .forcings import ForcingClock
 from .products import ensemble_products, ensemble_quantiles, exceedance_probability, rank_histogram
 from .gridgraph import containing_faces, grid_graphs, latlon_grid, radius_edges, sphere_points
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
@@ -27,6 +28,6 @@ __all__ = [
     "UpConvLayers", "loss_func", "InteractionNet", "InteractionForecaster", "EdgeGraph", "interaction_graph",
     "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream", "GraphTransformer", "edge_attention", "edge_attention_kv",
     "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
-    "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs",
+    "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
 ]
 __version__ = "0.1.0"

@@ -199,6 +199,9 @@ SIGNATURES = {
     "gwen_noise_normal_f32": (_int, [_vp, C.c_uint64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "gwen_noise_inject_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
     "gwen_noise_advance": (_int, [_vp, _i64, _vp]),
+    "gwen_forcing_advance": (_int, [_vp, _i64, _vp]),
+    "gwen_forcing_solar_f32": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "gwen_forcing_embed_f32": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     "gwen_edge_attention_supported": (_int, [_i64, _i64]),
     "gwen_edge_attention_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp] + [_i64] * 5 + [_vp, _vp, _vp]),
     "gwen_edge_attention_bwd_target_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64] + [_vp] * 6 + [_i64] * 5 + [_vp] * 5),

@@ -31,6 +31,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
+from . import forcings as forcings_mod
 from . import noise as noise_mod
 from . import ops
 from .g2m import grid_mesh_edges
@@ -56,6 +57,8 @@ class ForecastGraphs:
     f_m2g: Tensor
     _batched: dict = None   # members -> ForecastGraphs of the block-diagonal graphs
     members: int = 1        # copies of the graphs these are (mesh latent row r = node r % Nm of member r // Nm)
+    grid_latlon: Tensor = None   # [N, 2] float64 radians (lat, lon) of ONE member's grid points: members share them
+    grid_static: Tensor = None   # [N, S] fp32 static fields of ONE member's grid points, or None
 
     def batched(self, members: int) -> "ForecastGraphs":
         """Graphs and static inputs of ``members`` independent copies (EdgeGraph.batched): the c5 path rolls
@@ -68,7 +71,8 @@ class ForecastGraphs:
             rep = lambda t: t.repeat(members, 1)                                   # noqa: E731
             self._batched[members] = ForecastGraphs(
                 self.g2m.batched(members), self.mesh.batched(members), self.m2g.batched(members),
-                rep(self.mesh_pos), rep(self.f_g2m), rep(self.f_mesh), rep(self.f_m2g), members=members)
+                rep(self.mesh_pos), rep(self.f_g2m), rep(self.f_mesh), rep(self.f_m2g), members=members,
+                grid_latlon=self.__dict__.get("grid_latlon"), grid_static=self.__dict__.get("grid_static"))
         return self._batched[members]
 
     @property
@@ -104,11 +108,22 @@ class InteractionForecaster(nn.Module):
     feed-forward half; they carry their own LayerNorms (``norm_eps``), whatever ``layer_norm`` says, which then applies
     to the encoder and the decoder only.  Each block's edge term ``lin_e(e_m)`` depends on weights only and joins the
     static embeddings: a rollout step holds no edge-sized dense product.  Mesh edges are not updated.  Encoder and
-    decoder stay InteractionNet; everything else (members, noise, graphed rollouts, ``set_precision``) works alike."""
+    decoder stay InteractionNet; everything else (members, noise, graphed rollouts, ``set_precision``) works alike.
+
+    Inputs that are never predicted (all off by default), added to the grid embedding in one launch per step
+    (``forcings.embed``): ``vg = grid_embed(grid_x) + static_embed(grid_static) + forcing_embed(f)``.
+    ``static_channels`` S > 0: ``graphs.grid_static`` [N, S] (``prepare(..., grid_static=)``: orography, land-sea mask, ...),
+    the same for every member and every step; its embedding joins the static embeddings.  ``solar=True``: the 5 solar /
+    time channels of ``forcings.solar`` at the time of a ``forcings.ForcingClock`` passed as ``clock=``, evaluated at
+    ``graphs.grid_latlon``.  ``forcing_channels`` Fg > 0: given fields (SST, boundary data) passed as ``forcing=``, [N, Fg]
+    for one step and [n_steps, N, Fg] for a rollout.  f = [solar, given], at most 64 columns.  Every call that takes a
+    clock leaves it ``n_steps`` steps further on.  A model that needs a clock, a forcing or a static field and is not
+    given one raises ``ValueError``."""
 
     def __init__(self, grid_channels: int, hidden: int, steps: int = 4, activation: str = "silu",
                  aggr: str = "sum", precision: str = "3xbf16", noise_channels: int = 0, layer_norm: bool = False,
-                 norm_eps: float = 1e-5, processor: str = "interaction", heads: int = 8):
+                 norm_eps: float = 1e-5, processor: str = "interaction", heads: int = 8, static_channels: int = 0,
+                 solar: bool = False, forcing_channels: int = 0):
         super().__init__()
         if processor not in ("interaction", "transformer"):
             raise ValueError(f"processor must be 'interaction' or 'transformer', got {processor!r}")
@@ -137,6 +152,18 @@ class InteractionForecaster(nn.Module):
         if noise_channels:
             self.noise_embed = nn.Linear(noise_channels, hidden, bias=False)
             nn.init.zeros_(self.noise_embed.weight)
+        width = forcings_mod.SOLAR_CHANNELS * bool(solar) + forcing_channels
+        if static_channels < 0 or forcing_channels < 0 or width > forcings_mod.MAX_CHANNELS or \
+                (width == 0 and static_channels > forcings_mod.MAX_CHANNELS):
+            raise ValueError(f"static_channels >= 0 and 0 <= 5 solar + forcing_channels <= {forcings_mod.MAX_CHANNELS} "
+                             f"expected, got {static_channels}, {solar}, {forcing_channels}")
+        if (static_channels or width) and hidden % 4:
+            raise ValueError(f"static fields and forcings need hidden % 4 == 0, got {hidden}")
+        self.static_channels, self.solar, self.forcing_channels = static_channels, bool(solar), forcing_channels
+        if static_channels:
+            self.static_embed = nn.Linear(static_channels, hidden, bias=False)
+        if width:
+            self.forcing_embed = nn.Linear(width, hidden, bias=False)
 
     def set_precision(self, p: str) -> "InteractionForecaster":
         """The contraction of the encoder, the processors, the decoder and the six embedding / read-out layers."""
@@ -146,13 +173,16 @@ class InteractionForecaster(nn.Module):
         return self
 
     @staticmethod
-    def prepare(mesh: Mesh, device, grid_pos=None, radius: Optional[float] = None) -> ForecastGraphs:
+    def prepare(mesh: Mesh, device, grid_pos=None, radius: Optional[float] = None,
+                grid_static=None) -> ForecastGraphs:
         """``grid_pos=None``: the grid is the mesh's own triangle centres.  ``grid_pos`` ``[N, 3]`` (any points on the
         sphere: ``gridgraph.latlon_grid``, ``gridgraph.sphere_points`` of ICON cell centres, ...): the grid <-> mesh
         graphs come from ``gridgraph.grid_graphs`` -- every grid point sends to the mesh nodes within ``radius`` (default
-        0.6 x the longest mesh edge) and receives from the corners of the mesh face that contains it."""
+        0.6 x the longest mesh edge) and receives from the corners of the mesh face that contains it.
+        ``grid_latlon`` is always filled from the grid's unit vectors (on the default grid: of the face centres);
+        ``grid_static`` [N, S]: the static fields of a model with ``static_channels=S``."""
         if grid_pos is not None:
-            return _prepare_on_grid(mesh, device, grid_pos, radius)
+            return _prepare_on_grid(mesh, device, grid_pos, radius, grid_static)
         if radius is not None:
             raise ValueError("radius applies to grid_pos; the default grid is linked to the corners of its own faces")
         g2m, m2g = grid_mesh_edges(mesh)
@@ -165,7 +195,8 @@ class InteractionForecaster(nn.Module):
         feats = (edge_features(cell, mesh.pos, g2m), edge_features(mesh.pos, mesh.pos, mesh.edge_index),
                  edge_features(mesh.pos, cell, m2g))
         fs = [g.sort_edges(torch.from_numpy(f).to(device)) for g, f in zip(gs, feats)]
-        return ForecastGraphs(*gs, torch.from_numpy(mesh.pos.astype(np.float32)).to(device), *fs)
+        return ForecastGraphs(*gs, torch.from_numpy(mesh.pos.astype(np.float32)).to(device), *fs,
+                              **_grid_fields(cell, grid_static, device))
 
     def _lin(self, x: Tensor, m: nn.Linear) -> Tensor:
         """K3 on the model's precision, as the blocks around it ("3xbf16": bf16x3; "f16x3": K3's fp32-class split);
@@ -184,14 +215,57 @@ class InteractionForecaster(nn.Module):
                   lin(graphs.f_mesh, self.mesh_edge_embed), lin(graphs.f_m2g, self.m2g_edge_embed))
         if self.__dict__.get("processor_kind", "interaction") == "transformer":      # (a model pickled before: interaction)
             static += ([net.edge_term(static[2]) for net in self.processor],)        # every block's ee = lin_e(e_m)
+        S, width = self._forcing_widths()
+        if S and width:                                       # (S alone: the static fields ARE the forcing columns)
+            static += (lin(self._grid_static(graphs, S), self.static_embed),)        # base [N, hidden], members share it
         return static
 
+    def _forcing_widths(self):
+        """(static channels, forcing columns 5 solar + Fg); a model pickled before the settings existed: (0, 0)."""
+        d = self.__dict__
+        return d.get("static_channels", 0), forcings_mod.SOLAR_CHANNELS * d.get("solar", False) + d.get("forcing_channels", 0)
+
+    @staticmethod
+    def _grid_static(graphs: ForecastGraphs, S: int) -> Tensor:
+        gs = graphs.__dict__.get("grid_static")
+        if gs is None or gs.size(1) != S:
+            raise ValueError(f"the model has static_channels={S}: prepare(..., grid_static=[N, {S}]) "
+                             f"(got {None if gs is None else tuple(gs.shape)})")
+        return gs
+
+    def _forced(self, vg: Tensor, graphs: ForecastGraphs, base: Optional[Tensor], clock, forcing) -> Tensor:
+        """vg + static_embed(grid_static) + forcing_embed([solar, forcing]): one launch, in place without autograd."""
+        S, width = self._forcing_widths()
+        d = self.__dict__
+        sol, Fg = d.get("solar", False), d.get("forcing_channels", 0)
+        if sol and clock is None:
+            raise ValueError("the model has solar=True: pass clock= (a forcings.ForcingClock)")
+        if Fg and (forcing is None or forcing.dim() != 2 or forcing.size(1) != Fg):
+            raise ValueError(f"the model has forcing_channels={Fg}: pass forcing= [N, {Fg}] per step "
+                             f"(got {None if forcing is None else tuple(forcing.shape)})")
+        if width:
+            wf, given = self.forcing_embed.weight, forcing if Fg else None
+        else:
+            wf, given = self.static_embed.weight, self._grid_static(graphs, S)
+        grad = torch.is_grad_enabled() and (vg.requires_grad or wf.requires_grad
+                                            or (base is not None and base.requires_grad))
+        return forcings_mod.embed(vg, clock if sol else None, graphs.grid_latlon if sol else None, given, wf, base,
+                                  graphs.grid_nodes, out=None if grad else vg)
+
     def _step(self, grid_x: Tensor, graphs: ForecastGraphs, static, out: Optional[Tensor] = None,
-              noise: Optional["noise_mod.NoiseStream"] = None, member0: int = 0) -> Tensor:
+              noise: Optional["noise_mod.NoiseStream"] = None, member0: int = 0,
+              clock: Optional["forcings_mod.ForcingClock"] = None, forcing: Optional[Tensor] = None) -> Tensor:
         """One step; with ``noise``: the latent noise of members ``member0 ..`` at the stream's draw, which the step
-        then advances by one (in stream order: captured with the step)."""
+        then advances by one (in stream order: captured with the step).  ``clock`` / ``forcing``: the time of the solar
+        forcings, which the step then advances by one ``dt``, and the given forcing fields [N, Fg] of this step."""
         vm, e_g2m, e_m, e_m2g, *ees = static
+        S, width = self._forcing_widths()
+        base = ees.pop() if S and width else None
         vg = self._lin(grid_x, self.grid_embed)
+        if S or width:
+            vg = self._forced(vg, graphs, base, clock, forcing)
+        if clock is not None:
+            clock.advance(1)
         vm, _ = self.encoder(vg, vm, e_g2m, graphs.g2m, update_edges=False)
         if noise is not None:
             if self.__dict__.get("noise_channels", 0):             # (a model pickled before the setting existed: 0)
@@ -210,40 +284,55 @@ class InteractionForecaster(nn.Module):
         return grid_x + delta if out is None else torch.add(grid_x, delta, out=out)      # (out: GraphedStep's buffers)
 
     def forward(self, grid_x: Tensor, graphs: ForecastGraphs, noise: Optional["noise_mod.NoiseStream"] = None,
-                member0: int = 0) -> Tensor:
+                member0: int = 0, clock: Optional["forcings_mod.ForcingClock"] = None,
+                forcing: Optional[Tensor] = None) -> Tensor:
         """``grid_x`` [N_grid, C] or [members, N_grid, C] (members share graphs and weights: one launch set
-        over the block-diagonal graph).  ``noise``: latent noise of members ``member0 ..`` (advances the stream by 1)."""
+        over the block-diagonal graph).  ``noise``: latent noise of members ``member0 ..`` (advances the stream by 1).
+        ``clock``, ``forcing`` [N_grid, Fg]: the forcings, shared by the members (advances the clock by 1)."""
         if grid_x.dim() == 3:
             m = grid_x.size(0)
             gb = graphs.batched(m)
             return self._step(grid_x.reshape(-1, grid_x.size(-1)), gb, self._static(gb), noise=noise,
-                              member0=member0).view_as(grid_x)
-        return self._step(grid_x, graphs, self._static(graphs), noise=noise, member0=member0)
+                              member0=member0, clock=clock, forcing=forcing).view_as(grid_x)
+        return self._step(grid_x, graphs, self._static(graphs), noise=noise, member0=member0, clock=clock,
+                          forcing=forcing)
 
     def rollout(self, grid_x: Tensor, graphs: ForecastGraphs, n_steps: int,
                 graphed: bool = False, noise: Optional["noise_mod.NoiseStream"] = None,
-                member0: int = 0) -> List[Tensor]:
+                member0: int = 0, clock: Optional["forcings_mod.ForcingClock"] = None,
+                forcing: Optional[Tensor] = None) -> List[Tensor]:
         """Autoregressive: state_{t+1} = forward(state_t); returns the n_steps states.
         ``graphed``: capture ONE step (its ~26 launches) into a hipGraph and replay it per step -- the
         launchers allocate and synchronise nothing, so the step is capturable as is; worth it when the
-        host cannot keep ahead of the device (64 channels: 1.31 -> 1.14 ms per step; 128: 2.71 -> 2.39)."""
+        host cannot keep ahead of the device (64 channels: 1.31 -> 1.14 ms per step; 128: 2.71 -> 2.39).
+        ``clock``: the time of step 0's forcings (left ``n_steps`` steps on); ``forcing`` [n_steps, N, Fg]: step t's
+        given fields."""
+        _check_forcing_steps(forcing, n_steps)
         states, cur = [], grid_x
+        kw = {} if noise is None else {"noise": noise, "member0": member0}
+        if clock is not None:
+            kw["clock"] = clock
+        per_step = (lambda t: {}) if forcing is None else (lambda t: {"forcing": forcing[t]})      # noqa: E731
         with torch.no_grad():
             if graphed:
-                step = GraphedStep(self, graphs, grid_x, noise=noise, member0=member0)
-                for _ in range(n_steps):
-                    cur = step(cur)                          # (one of the step's two buffers: the next call reads it in place)
+                step = GraphedStep(self, graphs, grid_x, **kw, **per_step(0))
+                for t in range(n_steps):
+                    cur = step(cur, **per_step(t))           # (one of the step's two buffers: the next call reads it in place)
                     states.append(cur.clone())
                 return states
             static = self._static(graphs)
-            for _ in range(n_steps):
-                cur = self._step(cur, graphs, static) if noise is None else \
-                    self._step(cur, graphs, static, noise=noise, member0=member0)
+            for t in range(n_steps):
+                cur = self._step(cur, graphs, static, **kw, **per_step(t))
                 states.append(cur)
         return states
 
 
-def _prepare_on_grid(mesh: Mesh, device, grid_pos, radius: Optional[float]) -> ForecastGraphs:
+def _check_forcing_steps(forcing: Optional[Tensor], n_steps: int) -> None:
+    if forcing is not None and (forcing.dim() != 3 or forcing.size(0) != n_steps):
+        raise ValueError(f"forcing must be [n_steps = {n_steps}, N, Fg], got {tuple(forcing.shape)}")
+
+
+def _prepare_on_grid(mesh: Mesh, device, grid_pos, radius: Optional[float], grid_static=None) -> ForecastGraphs:
     """``InteractionForecaster.prepare`` for given grid points: edges from ``gridgraph.grid_graphs`` (built on the device),
     features ``[length, dx, dy, dz]`` over the normalised points, as on the default grid."""
     from . import gridgraph
@@ -256,13 +345,27 @@ def _prepare_on_grid(mesh: Mesh, device, grid_pos, radius: Optional[float]) -> F
     feats = (edge_features(grid, mesh.pos, g2m_t.cpu().numpy()), edge_features(mesh.pos, mesh.pos, mesh.edge_index),
              edge_features(mesh.pos, grid, m2g_t.cpu().numpy()))
     fs = [g.sort_edges(torch.from_numpy(f).to(device)) for g, f in zip(gs, feats)]
-    return ForecastGraphs(*gs, torch.from_numpy(mesh.pos.astype(np.float32)).to(device), *fs)
+    return ForecastGraphs(*gs, torch.from_numpy(mesh.pos.astype(np.float32)).to(device), *fs,
+                          **_grid_fields(grid, grid_static, device))
+
+
+def _grid_fields(grid: np.ndarray, grid_static, device) -> dict:
+    """``grid_latlon`` (lat = atan2(z, hypot(x, y)), lon = atan2(y, x) of the unit vectors, float64 radians) and
+    ``grid_static`` of a ``ForecastGraphs``."""
+    g = np.asarray(grid, dtype=np.float64)
+    latlon = np.stack([np.arctan2(g[:, 2], np.hypot(g[:, 0], g[:, 1])), np.arctan2(g[:, 1], g[:, 0])], axis=1)
+    if grid_static is not None:
+        grid_static = torch.as_tensor(grid_static, dtype=torch.float32)
+        if grid_static.dim() != 2 or grid_static.size(0) != g.shape[0]:
+            raise ValueError(f"grid_static must be [{g.shape[0]}, S], got {tuple(grid_static.shape)}")
+        grid_static = grid_static.to(device).contiguous()
+    return {"grid_latlon": torch.from_numpy(latlon).to(device), "grid_static": grid_static}
 
 
 def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,
                       n_steps: int, num_members: int, group=None, graphed: bool = True,
                       batched: bool = True, step_cache: dict = None, gather: bool = True,
-                      noise=None, member0: Optional[int] = None) -> Tensor:
+                      noise=None, member0: Optional[int] = None, clock=None, forcing: Optional[Tensor] = None) -> Tensor:
     """BASELINE config c5: this rank's members ``[members_local, N_grid, C]`` are rolled out ``n_steps``
     steps (independent members, replicated graph and weights), then every rank's final states are gathered
     ONCE (``ensemble.gather_members``: RCCL all-gather over xGMI under the "nccl" backend).  Returns
@@ -280,8 +383,11 @@ def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,
     on one that holds no member (the member-by-member path rewinds it between members).  Cost: ``member0`` is a kernel
     argument, so the graphed member-by-member path with ``noise`` captures one step per member (an eager warm-up step
     and two graph captures each) -- on every call unless ``step_cache`` keeps them; the batched path captures once.
+    ``clock`` (a ``forcings.ForcingClock``), ``forcing`` [n_steps, N_grid, Fg]: the forcings of a model that takes them,
+    shared by the members.  The clock ends ``n_steps`` steps further on, on every rank (rewound between members on the
+    member-by-member path, like the noise).
     ``model`` needs ``_static(graphs)`` and ``_step(x, graphs, static)`` (InteractionForecaster; with ``noise``, also the
-    ``noise=`` and ``member0=`` keywords of its ``_step``)."""
+    ``noise=`` and ``member0=`` keywords of its ``_step``; with ``clock`` / ``forcing``, those keywords)."""
     from . import ensemble
     m_local = x_members.size(0)
     if noise is not None and member0 is None:
@@ -289,36 +395,44 @@ def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,
         on = dist.is_available() and dist.is_initialized()
         rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
         member0 = ensemble.member_range(num_members, rank, world)[0]
+    _check_forcing_steps(forcing, n_steps)
     kw = {} if noise is None else {"noise": noise}
+    if clock is not None:
+        kw["clock"] = clock
+    per_step = (lambda t: {}) if forcing is None else (lambda t: {"forcing": forcing[t]})      # noqa: E731
 
     def captured(g, x0, m0):
         if step_cache is None:
-            return GraphedStep(model, g, x0, **kw, **({} if noise is None else {"member0": m0}))
-        key = (id(model), id(g), tuple(x0.shape)) + (() if noise is None else (id(noise), m0))
+            return GraphedStep(model, g, x0, **kw, **per_step(0), **({} if noise is None else {"member0": m0}))
+        key = (id(model), id(g), tuple(x0.shape)) + (() if noise is None else (id(noise), m0)) + \
+            (() if clock is None else (id(clock),))
         if key not in step_cache:
-            step_cache[key] = GraphedStep(model, g, x0, **kw, **({} if noise is None else {"member0": m0}))
+            step_cache[key] = GraphedStep(model, g, x0, **kw, **per_step(0),
+                                          **({} if noise is None else {"member0": m0}))
         return step_cache[key]
 
-    def one_step(x, g, static, m0):
-        return model._step(x, g, static) if noise is None else model._step(x, g, static, noise=noise, member0=m0)
+    def one_step(x, g, static, m0, t):
+        return model._step(x, g, static, **kw, **per_step(t), **({} if noise is None else {"member0": m0}))
 
     with torch.no_grad():
         if m_local == 0:
             local = x_members.new_empty((0,) + tuple(x_members.shape[1:]))
             if noise is not None:
                 noise.advance(n_steps)                       # a rank without members keeps the others' draw
+            if clock is not None:
+                clock.advance(n_steps)
         elif batched:
             gb = graphs.batched(m_local)
             cur = x_members.reshape(-1, x_members.size(-1))
             if graphed:
                 step = captured(gb, cur, member0)
-                for _ in range(n_steps):             # (the step alternates between its two state buffers: no copies)
-                    cur = step(cur)
+                for t in range(n_steps):             # (the step alternates between its two state buffers: no copies)
+                    cur = step(cur, **per_step(t))
                 cur = cur.clone()
             else:
                 static = model._static(gb)
-                for _ in range(n_steps):
-                    cur = one_step(cur, gb, static, member0)
+                for t in range(n_steps):
+                    cur = one_step(cur, gb, static, member0, t)
             local = cur.view_as(x_members)
         else:
             finals = []
@@ -326,14 +440,16 @@ def ensemble_forecast(model, graphs: ForecastGraphs, x_members: Tensor,
             step = captured(graphs, x_members[0], None) if graphed and noise is None else None
             for m in range(m_local):
                 m0 = None if noise is None else member0 + m
+                if clock is not None and m > 0:
+                    clock.advance(-n_steps)                  # every member starts at the call's time
                 if noise is not None:
                     if m > 0:
                         noise.advance(-n_steps)              # every member starts at the call's draw
                     if graphed:                              # (member0 is a kernel argument: one capture per member)
                         step = captured(graphs, x_members[0], m0)
                 cur = x_members[m]
-                for _ in range(n_steps):
-                    cur = step(cur) if step is not None else one_step(cur, graphs, static, m0)
+                for t in range(n_steps):
+                    cur = step(cur, **per_step(t)) if step is not None else one_step(cur, graphs, static, m0, t)
                 finals.append(cur.clone() if step is not None else cur)
             local = torch.stack(finals)
     if not gather:
@@ -349,20 +465,32 @@ class GraphedStep:
     output buffer -- valid until the call AFTER the next one (clone it to keep it longer).
 
     ``noise``: the captured step injects the latent noise of members ``member0 ..`` at the stream's draw and advances it,
-    so every replay draws fresh noise (the warm-up step's advance is taken back)."""
+    so every replay draws fresh noise (the warm-up step's advance is taken back).
+
+    ``clock``: the captured step reads the clock's time and advances it, so every replay sees the next time (the warm-up's
+    advance is taken back too).  ``forcing`` [N, Fg]: the given fields live in a fixed buffer that ``step(x, forcing=f_t)``
+    copies into before the replay."""
 
     def __init__(self, model: InteractionForecaster, graphs: ForecastGraphs, grid_x: Tensor, noise=None,
-                 member0: int = 0):
+                 member0: int = 0, clock=None, forcing: Optional[Tensor] = None):
         self.bufs = [grid_x.detach().clone(), torch.empty_like(grid_x)]
         self.graphs = graphs                                 # the captured graphs hold raw pointers into these:
         self.noise = noise                                   # (and into the noise state)
+        self.clock = clock                                   # (and into the clock)
+        self.forcing = None if forcing is None else forcing.detach().clone().contiguous()
         self.cur = 0                                         # the buffer the next call reads
         kw = {} if noise is None else {"noise": noise, "member0": member0}
+        if clock is not None:
+            kw["clock"] = clock
+        if forcing is not None:
+            kw["forcing"] = self.forcing
         with torch.no_grad():                                # keep every tensor they read alive
             static = self._static = model._static(graphs)
             model._step(self.bufs[0], graphs, static, out=self.bufs[1], **kw)  # warm-up: occupancy queries, tilings, caches
             if noise is not None:
                 noise.advance(-1)
+            if clock is not None:
+                clock.advance(-1)
             torch.cuda.synchronize(grid_x.device)
             self.replays = []
             for i in (0, 1):
@@ -371,7 +499,11 @@ class GraphedStep:
                     model._step(self.bufs[i], graphs, static, out=self.bufs[1 - i], **kw)
                 self.replays.append(g)
 
-    def __call__(self, x: Tensor) -> Tensor:
+    def __call__(self, x: Tensor, forcing: Optional[Tensor] = None) -> Tensor:
+        if forcing is not None:
+            if self.forcing is None:
+                raise ValueError("the step was captured without forcing=")
+            self.forcing.copy_(forcing)
         src = self.bufs[self.cur]
         if x.data_ptr() != src.data_ptr():
             src.copy_(x)

@@ -749,6 +749,41 @@ int gwen_noise_inject_f32(const uint64_t *state, int64_t member0, int64_t rows, 
 int gwen_noise_advance(uint64_t *state, int64_t n, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Forcings (csrc/forcing.hip): inputs of the forecaster that it never predicts -- static fields (through `base`) and
+ * functions of the valid time and the position -- added to the grid embedding in one launch.  BUILD-DEFINED.
+ * clock: DEVICE int64 [2] = {t, dt}, 8-byte aligned: t seconds since 2000-01-01 00:00:00 UTC (may be negative), dt
+ * seconds per step; read by every launch (a captured hipGraph sees the current time on every replay).
+ * The solar vector of a point at latitude phi, longitude lambda (radians), AT the clock's t, with Y = 31 556 926 s and
+ * mod the floor modulus on INTEGERS (t does not fit a float):
+ *     gamma = 2 pi (t mod Y) / Y,     tau = 2 pi (t mod 86400) / 86400
+ *     delta = 0.006918 - 0.399912 cos g + 0.070257 sin g - 0.006758 cos 2g + 0.000907 sin 2g - 0.002697 cos 3g
+ *             + 0.00148 sin 3g                                                        (Spencer's series; g = gamma)
+ *     E     = 0.000075 + 0.001868 cos g - 0.032077 sin g - 0.014615 cos 2g - 0.040849 sin 2g
+ *     e0    = 1.000110 + 0.034221 cos g + 0.001280 sin g + 0.000719 cos 2g + 0.000077 sin 2g
+ *     h     = tau + lambda + E - pi,     mu = sin phi sin delta + cos phi cos delta cos h
+ *     f     = [e0 max(mu, 0), sin(tau + lambda), cos(tau + lambda), sin gamma, cos gamma]
+ * evaluated in fp64 and rounded once to fp32.  No allocation, no synchronisation, no atomics.
+ *
+ *   gwen_forcing_advance:   clock[0] += n clock[1] (n may be negative), one thread, in stream order.
+ *   gwen_forcing_solar_f32: out[n, :] = f(clock[0], latlon[n, 0], latlon[n, 1]); latlon double [N, 2] (lat, lon),
+ *                           out fp32 [N, 5] contiguous.
+ *   gwen_forcing_embed_f32: out[r, :] = x[r, :] + base[r % N, :] + sum_k f[r % N, k] wf[:, k]
+ *                           f = the solar vector first (clock non-NULL; latlon is needed then), the Fg columns of
+ *                           `given` (fp32 [N, Fg]; NULL with Fg = 0) after it; wf fp32 [H, 5 solar + Fg] (an nn.Linear
+ *                           weight); base fp32 [N, H] or NULL; x, out fp32 [rows, H] (out may be x).  rows % N == 0
+ *                           (rows / N members share latlon, given and base), H % 4 == 0, 1 <= 5 solar + Fg <= 64,
+ *                           x / out / wf / base 16-byte aligned.  The forcing term is accumulated from zero by fmaf in
+ *                           increasing k, then base is added, then x: it depends on no contraction tier and not on how
+ *                           the members are batched, and two launches are bitwise equal.
+ * Bad arguments give GWEN_EINVAL before any HIP call.
+ * ------------------------------------------------------------------------------------------- */
+int gwen_forcing_advance(int64_t *clock, int64_t n, gwen_stream_t stream);
+int gwen_forcing_solar_f32(const int64_t *clock, const double *latlon, int64_t N, float *out, gwen_stream_t stream);
+int gwen_forcing_embed_f32(const int64_t *clock, const double *latlon, const float *given, int64_t Fg, const float *wf,
+                           const float *base, int64_t rows, int64_t N, const float *x, int64_t H, float *out,
+                           gwen_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Edge attention (csrc/attention.hip): multi-head softmax attention of every target over its in-edges with an edge
  * term -- the kernel of gwen_amd.attention.GraphTransformer, forward and backward.  BUILD-DEFINED, PARITY UNPINNED (the
  * reference has no attention); PyG TransformerConv with edge_dim.  H heads, D = F / H, s(e) / d(e) the source / target of
