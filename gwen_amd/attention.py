@@ -222,12 +222,10 @@ class GraphTransformer(nn.Module):
         self._precision = p
 
     def _lin(self, x: Tensor, m: nn.Linear, grad: bool) -> Tensor:
-        prec = self.precision
+        """K3 on the block's precision; with autograd when gradients are needed."""
         if grad:
-            return ops.linear_autograd(x, m.weight, m.bias, contract=prec)
-        if prec == "3xbf16":
-            return ops.linear(x, m.weight, m.bias, exact=False)
-        return ops.linear(x, m.weight, m.bias, contract=prec)
+            return ops.linear_autograd(x, m.weight, m.bias, contract=self.precision)
+        return ops.linear(x, m.weight, m.bias, contract=self.precision)
 
     def edge_term(self, e: Tensor) -> Tensor:
         """ee = lin_e(e) [E, F] (K3 on the block's precision; with autograd when gradients are needed)."""

@@ -340,6 +340,10 @@ class InteractionNet(nn.Module):
         n = self.edge_norm if which == "edge" else self.node_norm
         return {"ln_weight": n.weight, "ln_bias": n.bias, "ln_eps": n.eps}
 
+    def _lin(self, x: Tensor, w: Tensor, b: Optional[Tensor] = None) -> Tensor:
+        """K3 on the block's precision ("f16x3" -> K3's fp32-class split): every dense product, forward and backward."""
+        return ops.linear(x, w, b, contract=self.precision)
+
     def __getstate__(self):          # the cache is derived data: keep modules picklable and small
         state = self.__dict__.copy()
         state["_blocks"] = None
@@ -367,15 +371,12 @@ class InteractionNet(nn.Module):
         else:
             _check_table("Ps (the source projections)", graph.num_src, f)
             _check_table("[Pd | Q] (the target projections)", graph.num_dst, 2 * f)
-        # (the default keeps exact=False: the launch it has always been; "f16x3" -> K3's fp32-class split)
-        lin = (lambda x, w, b: ops.linear(x, w, b, exact=False)) if prec == "3xbf16" else \
-            (lambda x, w, b: ops.linear(x, w, b, contract=prec))                                # noqa: E731
         if x_src is x_dst:                                   # mesh -> mesh: one launch, [N, 3F]
-            p = lin(x_dst, wn, bn)
+            p = self._lin(x_dst, wn, bn)
             ps, pd, q = p[:, :f], p[:, f:2 * f], p[:, 2 * f:]
         else:                                                # bipartite: sources apart
-            ps = lin(x_src, wn[:f], None)
-            p = lin(x_dst, wn[f:], bn[f:])
+            ps = self._lin(x_src, wn[:f])
+            p = self._lin(x_dst, wn[f:], bn[f:])
             pd, q = p[:, :f], p[:, f:]
         e_new, agg = mlp2(e, we, self.edge_mlp[2].weight, self.edge_mlp[2].bias,
                           g1=ps, idx1=graph.src, g2=pd, idx2=graph.dst, res=e, act=self.activation,
@@ -483,14 +484,21 @@ class _InteractionNetFunction(torch.autograd.Function):
     """Training through an InteractionNet block, forward AND backward on libgwen_hip.so.  The forward runs on K6 and
     keeps the node-sized intermediates it makes anyway -- the aggregated messages (saves the backward an edge-sized
     projection and a segmented sum) and the node projections [Ps | Pd | Q]; the backward recomputes the two hidden layers
-    (K3 + ``gwen_act_pair_f32``, which also yields the activation's derivative) and then walks the block in reverse:
-        node MLP:  g_pre3 = (gx W4) * act'(pre3);   g_agg = g_pre3 Wa;   g_x += gx + g_pre3 Wx
+    (K3 + ``gwen_act_pair_f32``, which also yields the activation's derivative) and then walks the block in reverse, ONE
+    walk for every block (``ln``: the block has LayerNorm; ``fused``: the one-launch edge route, ``_fused_edge_backward``):
+        node MLP:  [ln: g_m3 = LN_node'(gx), else g_m3 = gx]   g_pre3 = (g_m3 W4) * act'(pre3);   g_agg = g_pre3 Wa;
+                   g_x += gx + g_pre3 Wx
         messages:  g_m[e] = ge[e] + g_agg[dst(e)] (/ degree for the mean)          (``gwen_gather_add_f32``)
+                   [ln: g_m = LN_edge'(g_m)]
         edge MLP:  g_pre1 = (g_m W2) * act'(pre1);  g_e = ge + g_pre1 We
+                   [fused: messages and edge MLP are ONE launch of K6's kernel, g_m is never formed]
         nodes:     G_d = sum of g_pre1 over a target's edges, G_s over a source's   (K2 over ``EdgeGraph.segments``:
                    stored order, no atomics);  g_x_dst += G_d Wd,  g_x_src = G_s Ws
         weights:   every grad_W = (gradient rows)^T (input rows), grad_b = column sums   (fixed-order reductions; the
                    wide ones -- multiples of 64 from 128 x 128 -- on the block's own bf16x3 split: csrc/grad.hip)
+    With LayerNorm the two pre-norm outputs m = h1 W2^T + b2 and m3 = h3 W4^T + b4 are recomputed by K3 and the LayerNorm
+    backward kernel (csrc/layernorm.hip) stands between the incoming gradient and each MLP's own backward; it also yields
+    the four norm-parameter gradients (per-chunk partials, finished with every other gradient in the GradBatch's one launch).
     Every launch is atomic-free with a fixed summation order: two backward runs are bitwise equal.  BUILD-DEFINED
     like the block (the reference has no edge MLP); gradients are tested against fp64 autograd of the oracle."""
 
@@ -508,15 +516,18 @@ class _InteractionNetFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gx, ge):
-        if ctx.net.layer_norm:
-            return _backward_layer_norm(ctx, gx, ge)
-        x_src, x_dst, e, agg, w1, b1, w2, b2, w3, b3, w4, b4, pall, ps = ctx.saved_tensors
         net, g, same = ctx.net, ctx.graph, ctx.same
         f, act, mean = net.channels, net.activation, net.aggr == "mean"
         n_src, n_dst = g.num_src, g.num_dst
-        prec = net.precision
+        prec, lin = net.precision, net._lin
+        ln = net.layer_norm
+        # with LayerNorm the message gradient g_m = LN'(ge + g_agg[dst]) is not linear across a target's edges, so the
+        # one-launch edge backward (g_m W2 = ge W2 + T[dst], below) does not apply
+        fused = not ln and _fused_edge_backward(f, g.num_edges, n_dst)
+        x_src, x_dst, e, agg, w1, _, w2, b2, w3, _, w4, b4, *norms, pall, ps = ctx.saved_tensors
+        if ln:                                           # (norms = edge gamma, beta, node gamma, beta)
+            gam_e, gam_n, eps_e, eps_n = norms[0], norms[2], net.edge_norm.eps, net.node_norm.eps
         with torch.no_grad():
-            lin = lambda x, w, b=None: ops.linear(x, w, b, contract=prec)                   # noqa: E731
             x_src, x_dst, e = x_src.detach().contiguous(), x_dst.detach().contiguous(), e.detach().contiguous()
             gx = gx.contiguous()
             has_ge = bool(ctx.update_edges and ge is not None and ge.numel() > 0)
@@ -534,31 +545,34 @@ class _InteractionNetFunction(torch.autograd.Function):
                 ps, pd, q = pall[:, :f], pall[:, f:2 * f], pall[:, 2 * f:]
             else:
                 pd, q = pall[:, :f], pall[:, f:]
-            fused_edge = _fused_edge_backward(f, g.num_edges, n_dst)
-            if fused_edge:       # (edges are stored by target: the hidden layer's per-target sums come out of the same pass)
+            if fused:            # (edges are stored by target: the hidden layer's per-target sums come out of the same pass)
                 h1, d1, hagg = _act_pair_seg(lin(e, we), act, ps, g.src, pd, g.rowptr, n_dst)
             else:
                 h1, d1 = _act_pair(lin(e, we), act, ps, g.src, pd, g.dst)
             del ps, pd                                   # (agg = sum / mean of the messages: kept by the forward)
             h3, d3 = _act_pair(lin(agg, wa), act, q)
             del pall, q
-            # ---- node MLP -----------------------------------------------------------------------------------------
             # (every weight / bias gradient: stage 1 launched where its operands are live, the fixed-order finishes of
             #  all of them in ONE launch at the end -- ops.GradBatch)
             gb = ops.GradBatch()
             gw = lambda a, b_: gb.grad_weight(a, b_, prec)                                   # noqa: E731
             gwb = lambda a, b_: gb.grad_weight_bias(a, b_, prec)                             # noqa: E731
-            g_w4, g_b4 = gwb(gx, h3)                                   # (weight gradient + column sums of the same rows)
-            g_pre3 = _ew(_lib.EW_MUL, lin(gx, w4t), d3)
-            del h3, d3
+            # ---- node MLP: x' = x + [LN_node](m3) -----------------------------------------------------------------
+            if ln:
+                g_m3, g_ln_n = ops.layer_norm_backward(lin(h3, w4, b4), gx, gam_n, eps_n, gb)
+            else:
+                g_m3 = gx
+            g_w4, g_b4 = gwb(g_m3, h3)                                 # (weight gradient + column sums of the same rows)
+            g_pre3 = _ew(_lib.EW_MUL, lin(g_m3, w4t), d3)
+            del h3, d3, g_m3
             g_w3a, g_b3 = gwb(g_pre3, x_dst)
             g_w3 = [g_w3a, gw(g_pre3, agg)]
             g_agg = lin(g_pre3, wat)
-            g_xd = _ew(_lib.EW_ADD, lin(g_pre3, wxt), gx)
+            g_xd = _ew(_lib.EW_ADD, lin(g_pre3, wxt), gx)              # (the residual passes gx itself, not g_m3)
             del g_pre3, agg
-            # ---- messages and edge MLP ----------------------------------------------------------------------------
-            if fused_edge:
-                # ONE launch of K6's kernel for the edge-level half (round 4): by linearity g_m W2 = ge W2 + T[dst] with
+            # ---- messages and edge MLP: m_e = [LN_edge](m), gradient of m_e = ge + g_agg[dst] (/ degree) -----------
+            if fused:
+                # ONE launch of K6's kernel for the edge-level half: by linearity g_m W2 = ge W2 + T[dst] with
                 # T = (g_agg / degree) W2 per node, so the message gradient g_m = ge + g_agg[dst] is never formed --
                 # its two uses split the same way: g_m^T h1 = ge^T h1 + g_agg_s^T (sum of h1 over a target's edges),
                 # column sums of g_m = column sums of ge + sum_d degree_d g_agg_s[d]
@@ -567,43 +581,35 @@ class _InteractionNetFunction(torch.autograd.Function):
                 g_agg_s = g_agg * g.inv_degree().view(-1, 1) if mean else g_agg
                 g_pre1, g_e = _edge_backward(ge if has_ge else torch.zeros_like(e), w2t, d1,
                                              lin(g_agg_s, w2t), g.dst, wet, prec)
-                del d1
                 g_b2 = gb.grad_bias(g_agg_s * g.degree())
                 g_w2 = gw(g_agg_s, hagg)
                 g_w2e, g_b2e = gwb(ge, h1) if has_ge else (None, None)
-                del h1, hagg, g_agg, g_agg_s
-                big_d = _segsum(g.segments("dst"), g_pre1, n_dst)
-                big_s = _segsum(g.segments("src"), g_pre1, n_src)
-                g_w1d, g_b1 = gwb(big_d, x_dst)
-                g_w1 = [gw(g_pre1, e), gw(big_s, x_src), g_w1d]
-                del g_pre1
-                g_xs = lin(big_s, wst)
-                g_xd = _ew(_lib.EW_ADD, g_xd, lin(big_d, wdt))
-                if same:
-                    g_xd = _ew(_lib.EW_ADD, g_xd, g_xs)
-                    g_xs = None
-                gb.finish()
-                g_w1, g_w3 = torch.cat(g_w1, dim=1), torch.cat(g_w3, dim=1)
-                if has_ge:
-                    g_b2, g_w2 = g_b2 + g_b2e, g_w2 + g_w2e
-                need = ctx.needs_input_grad
-                pick = lambda k, t: t if need[k] else None                                  # noqa: E731
-                return (None, None, None, None, pick(4, g_xs), pick(5, g_xd), pick(6, g_e), pick(7, g_w1),
-                        pick(8, g_b1), pick(9, g_w2), pick(10, g_b2), pick(11, g_w3), pick(12, g_b3), pick(13, g_w4),
-                        pick(14, g_b4))
-            g_m = _gather_add(ge, g_agg, g.dst, g.inv_degree() if mean else None)
-            g_b2, g_w2 = gb.grad_bias(g_m), gw(g_m, h1)
-            g_pre1 = _ew(_lib.EW_MUL, lin(g_m, w2t), d1)
-            del g_m, h1, d1, g_agg
+                del hagg, g_agg_s
+            else:
+                g_m = _gather_add(ge, g_agg, g.dst, g.inv_degree() if mean else None)
+                if ln:
+                    g_m, g_ln_e = ops.layer_norm_backward(lin(h1, w2, b2), g_m, gam_e, eps_e, gb)
+                g_b2, g_w2 = gb.grad_bias(g_m), gw(g_m, h1)
+                g_pre1 = _ew(_lib.EW_MUL, lin(g_m, w2t), d1)
+                del g_m
+            del h1, d1, g_agg
+            # ---- nodes, first-layer weights, inputs ---------------------------------------------------------------
             big_d = _segsum(g.segments("dst"), g_pre1, n_dst)          # per target: sum over its in-edges
-            g_b1 = gb.grad_bias(big_d)                                 # = column sums of g_pre1, over N_dst rows instead of E
             big_s = _segsum(g.segments("src"), g_pre1, n_src)          # per source: sum over its out-edges
-            g_w1 = [gw(g_pre1, e), gw(big_s, x_src), gw(big_d, x_dst)]
+            # g_b1 = column sums of g_pre1, over N_dst rows instead of E.  (Two forms on purpose: where gwb has its one-launch
+            # kernel it chunks the column sums as it chunks the weight gradient -- on the general route that would be
+            # another launch set and summation order than g_b1 has had)
+            g_w1d, g_b1 = gwb(big_d, x_dst) if fused else (gw(big_d, x_dst), gb.grad_bias(big_d))
+            g_w1 = [gw(g_pre1, e), gw(big_s, x_src), g_w1d]
             gb.finish()
             g_w1, g_w3 = torch.cat(g_w1, dim=1), torch.cat(g_w3, dim=1)
-            g_e = lin(g_pre1, wet)
-            if has_ge:
-                g_e = _ew(_lib.EW_ADD, g_e, ge)
+            if fused:
+                if has_ge:                                             # (ge's own terms of g_m: complete after the finish)
+                    g_b2, g_w2 = g_b2 + g_b2e, g_w2 + g_w2e
+            else:
+                g_e = lin(g_pre1, wet)
+                if has_ge:
+                    g_e = _ew(_lib.EW_ADD, g_e, ge)
             del g_pre1
             g_xs = lin(big_s, wst)
             g_xd = _ew(_lib.EW_ADD, g_xd, lin(big_d, wdt))
@@ -612,77 +618,7 @@ class _InteractionNetFunction(torch.autograd.Function):
                 g_xs = None
         need = ctx.needs_input_grad
         pick = lambda k, t: t if need[k] else None                                          # noqa: E731
+        g_norms = (g_ln_e[:f], g_ln_e[f:], g_ln_n[:f], g_ln_n[f:]) if ln else ()
         return (None, None, None, None, pick(4, g_xs), pick(5, g_xd), pick(6, g_e), pick(7, g_w1), pick(8, g_b1),
-                pick(9, g_w2), pick(10, g_b2), pick(11, g_w3), pick(12, g_b3), pick(13, g_w4), pick(14, g_b4))
-
-
-def _backward_layer_norm(ctx, gx, ge):
-    """``_InteractionNetFunction.backward`` of a block with LayerNorm.  The message gradient g_m = LN'(ge + g_agg[dst]) is
-    not linear across a target's edges, so the one-launch edge backward (g_m W2 = ge W2 + T[dst]) does not apply: this is
-    the general (``_gather_add``) walk with two additions -- the pre-norm outputs m = h1 W2^T + b2 and m3 = h3 W4^T + b4
-    recomputed by K3 next to the hidden layers, and the LayerNorm backward kernel (csrc/layernorm.hip) between the
-    incoming gradient and each MLP's own backward, which also yields the four norm-parameter gradients (per-chunk
-    partials, finished with every other gradient in the GradBatch's one launch).  Atomic-free, fixed order."""
-    x_src, x_dst, e, agg, w1, b1, w2, b2, w3, b3, w4, b4, gam_e, _, gam_n, _, pall, ps = ctx.saved_tensors
-    net, g, same = ctx.net, ctx.graph, ctx.same
-    f, act, mean = net.channels, net.activation, net.aggr == "mean"
-    n_src, n_dst = g.num_src, g.num_dst
-    prec = net.precision
-    eps_e, eps_n = net.edge_norm.eps, net.node_norm.eps
-    with torch.no_grad():
-        lin = lambda x, w, b=None: ops.linear(x, w, b, contract=prec)                       # noqa: E731
-        x_src, x_dst, e = x_src.detach().contiguous(), x_dst.detach().contiguous(), e.detach().contiguous()
-        gx = gx.contiguous()
-        has_ge = bool(ctx.update_edges and ge is not None and ge.numel() > 0)
-        ge = ge.contiguous() if has_ge else None
-        w1t, w3t, w2t, w4t = (w.t().contiguous() for w in (w1, w3, w2, w4))
-        wet, wst, wdt, wxt, wat = w1t[:f], w1t[f:2 * f], w1t[2 * f:], w3t[:f], w3t[f:]
-        we, wa, _, _ = net._weight_blocks()
-        if same:
-            ps, pd, q = pall[:, :f], pall[:, f:2 * f], pall[:, 2 * f:]
-        else:
-            pd, q = pall[:, :f], pall[:, f:]
-        h1, d1 = _act_pair(lin(e, we), act, ps, g.src, pd, g.dst)
-        del ps, pd
-        h3, d3 = _act_pair(lin(agg, wa), act, q)
-        del pall, q
-        gb = ops.GradBatch()
-        gw = lambda a, b_: gb.grad_weight(a, b_, prec)                                       # noqa: E731
-        gwb = lambda a, b_: gb.grad_weight_bias(a, b_, prec)                                 # noqa: E731
-        # ---- node MLP: x' = x + LN_node(m3) ------------------------------------------------------------------------
-        g_m3, g_ln_n = ops.layer_norm_backward(lin(h3, w4, b4), gx, gam_n, eps_n, gb)
-        g_w4, g_b4 = gwb(g_m3, h3)
-        g_pre3 = _ew(_lib.EW_MUL, lin(g_m3, w4t), d3)
-        del h3, d3, g_m3
-        g_w3a, g_b3 = gwb(g_pre3, x_dst)
-        g_w3 = [g_w3a, gw(g_pre3, agg)]
-        g_agg = lin(g_pre3, wat)
-        g_xd = _ew(_lib.EW_ADD, lin(g_pre3, wxt), gx)
-        del g_pre3, agg
-        # ---- messages: m_e = LN_edge(m), gradient of m_e = ge + g_agg[dst] (/ degree) -----------------------------------
-        g_y = _gather_add(ge, g_agg, g.dst, g.inv_degree() if mean else None)
-        g_m, g_ln_e = ops.layer_norm_backward(lin(h1, w2, b2), g_y, gam_e, eps_e, gb)
-        del g_y, g_agg
-        g_b2, g_w2 = gb.grad_bias(g_m), gw(g_m, h1)
-        g_pre1 = _ew(_lib.EW_MUL, lin(g_m, w2t), d1)
-        del g_m, h1, d1
-        big_d = _segsum(g.segments("dst"), g_pre1, n_dst)
-        g_b1 = gb.grad_bias(big_d)
-        big_s = _segsum(g.segments("src"), g_pre1, n_src)
-        g_w1 = [gw(g_pre1, e), gw(big_s, x_src), gw(big_d, x_dst)]
-        gb.finish()
-        g_w1, g_w3 = torch.cat(g_w1, dim=1), torch.cat(g_w3, dim=1)
-        g_e = lin(g_pre1, wet)
-        if has_ge:
-            g_e = _ew(_lib.EW_ADD, g_e, ge)
-        del g_pre1
-        g_xs = lin(big_s, wst)
-        g_xd = _ew(_lib.EW_ADD, g_xd, lin(big_d, wdt))
-        if same:
-            g_xd = _ew(_lib.EW_ADD, g_xd, g_xs)
-            g_xs = None
-    need = ctx.needs_input_grad
-    pick = lambda k, t: t if need[k] else None                                              # noqa: E731
-    return (None, None, None, None, pick(4, g_xs), pick(5, g_xd), pick(6, g_e), pick(7, g_w1), pick(8, g_b1),
-            pick(9, g_w2), pick(10, g_b2), pick(11, g_w3), pick(12, g_b3), pick(13, g_w4), pick(14, g_b4),
-            pick(15, g_ln_e[:f]), pick(16, g_ln_e[f:]), pick(17, g_ln_n[:f]), pick(18, g_ln_n[f:]))
+                pick(9, g_w2), pick(10, g_b2), pick(11, g_w3), pick(12, g_b3), pick(13, g_w4), pick(14, g_b4),
+                *(pick(15 + k, t) for k, t in enumerate(g_norms)))

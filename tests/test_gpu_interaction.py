@@ -387,34 +387,48 @@ def test_interaction_block_backward_vs_oracle_autograd(ga, F, act, aggr, bip):
     assert all(torch.equal(a, b) for a, b in zip(first, again))
 
 
-def test_interaction_block_backward_without_edge_update(ga):
+@pytest.mark.parametrize("F,bip,aggr", [(64, True, "sum"), (64, False, "mean"), (32, True, "mean"), (32, False, "sum")])
+def test_interaction_block_backward_without_edge_update(ga, F, bip, aggr):
     """Encoder / decoder blocks return no edge state (update_edges=False): the message gradient then comes from
-    the aggregate alone."""
+    the aggregate alone.  64 channels take the one-launch edge route, 32 the general one; ``bip=False`` passes one tensor
+    as both x_src and x_dst (its gradient is reported once); two backward runs are bitwise equal."""
     from gwen_amd.interaction import InteractionNet, interaction_graph
     from oracle import interaction_oracle as IO
     rng = np.random.default_rng(5)
-    F, ns, nd, e_ = 64, 90, 140, 700
+    ns, nd, e_ = (90, 140, 700) if bip else (140, 140, 700)
     ei = torch.from_numpy(np.stack([rng.integers(0, ns, size=e_), rng.integers(0, nd, size=e_)]).astype(np.int64))
     torch.manual_seed(SEED)
-    net = InteractionNet(F, "silu", "sum")
+    net = InteractionNet(F, "silu", aggr)
     g = torch.Generator().manual_seed(SEED)
     xs, xd, ef = torch.randn(ns, F, generator=g), torch.randn(nd, F, generator=g), torch.randn(e_, F, generator=g)
     gxo = torch.randn(nd, F, generator=g)
     sd = {k: v.double().clone().requires_grad_() for k, v in net.state_dict().items()}
     xs64, xd64, ef64 = xs.double().requires_grad_(), xd.double().requires_grad_(), ef.double().requires_grad_()
-    wx, _ = IO.interaction(xs64, xd64, ef64, ei, sd, "silu", "sum")
+    wx, _ = IO.interaction(xs64 if bip else xd64, xd64, ef64, ei, sd, "silu", aggr)
     (wx * gxo.double()).sum().backward()
     graph = interaction_graph(ei.to(DEV), ns, nd)
     net = net.to(DEV)
     xsd, xdd = xs.to(DEV).requires_grad_(), xd.to(DEV).requires_grad_()
     efd = graph.sort_edges(ef.to(DEV)).detach().requires_grad_()
-    gx, ge = net(xsd, xdd, efd, graph, update_edges=False)
-    assert ge.numel() == 0
-    (gx * gxo.to(DEV)).sum().backward()
-    assert rel_err(xdd.grad, xd64.grad) <= REL_TOL and rel_err(xsd.grad, xs64.grad) <= REL_TOL
+    leaves = [xdd, efd] + ([xsd] if bip else []) + list(net.parameters())
+
+    def run():
+        for t in leaves:
+            t.grad = None
+        gx, ge = net(xsd if bip else xdd, xdd, efd, graph, update_edges=False)
+        assert ge.numel() == 0
+        (gx * gxo.to(DEV)).sum().backward()
+        return [t.grad.clone() for t in leaves]
+
+    first = run()
+    assert rel_err(xdd.grad, xd64.grad) <= REL_TOL
+    if bip:
+        assert rel_err(xsd.grad, xs64.grad) <= REL_TOL
     assert rel_err(graph.unsort_edges(efd.grad), ef64.grad) <= REL_TOL
     for k, p in net.named_parameters():
         assert rel_err(p.grad, sd[k].grad) <= REL_TOL, k
+    # fixed-order sums, no atomics: a second run gives the same bits
+    assert all(torch.equal(a, b) for a, b in zip(first, run()))
 
 
 def test_forecaster_training_step(ga):
