@@ -6,7 +6,7 @@ torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); bui
 ``python -m gwen_amd.build``.
 """
 from . import attention, forcings, forecaster, g2m, gridgraph, interaction, losses, noise, ops
-from . import products
+from . import products, regrid
 from .attention import GraphTransformer, edge_attention, edge_attention_kv
 from .forward import GraphedForward, KernelEvents, StackForward, event_bracket_overhead
 from .gcn_conv import GCNConv, Linear
@@ -17,6 +17,7 @@ from .noise import NoiseStream
 from .forcings import ForcingClock
 from .products import ensemble_products, ensemble_quantiles, exceedance_probability, rank_histogram
 from .gridgraph import containing_faces, grid_graphs, latlon_grid, radius_edges, sphere_points
+from .regrid import Regridder, nearest_neighbours
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
 from .models_gnn import (DownConvLayers, GCNConvLayers, GNNConfig, GNNModel, UpConvLayers,
@@ -29,5 +30,6 @@ __all__ = [
     "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream", "GraphTransformer", "edge_attention", "edge_attention_kv",
     "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
     "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
+    "Regridder", "nearest_neighbours",
 ]
 __version__ = "0.1.0"

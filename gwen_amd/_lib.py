@@ -88,6 +88,7 @@ KIND_PROPAGATE, KIND_LINEAR, KIND_LAYER, KIND_CHAIN, KIND_SMALL, KIND_WIDE = 2, 
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
 EW_MUL, EW_ADD = 0, 1
 MLP2_LN_EDGE, MLP2_LN_NODE = 0, 1                    # GWEN_MLP2_LN_* (include/gwen_hip.h)
+REGRID_NEAREST, REGRID_IDW = 0, 1                    # GWEN_REGRID_* (include/gwen_hip.h)
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
 
@@ -214,6 +215,10 @@ SIGNATURES = {
     "gwen_radius_edges_fill": (_int, [_vp, _i64, _vp, _i64, _f64, _i64, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     "gwen_containing_faces_workspace_bytes": (_int, [_i64, C.POINTER(C.c_size_t)]),
     "gwen_containing_faces": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _f64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "gwen_knn_workspace_bytes": (_int, [_i64, _i64, C.POINTER(C.c_size_t)]),
+    "gwen_knn_query": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp,
+                              C.c_size_t, _vp]),
+    "gwen_knn_weights": (_int, [_vp, _vp, _i64, _int, _int, _f64, _vp, _vp, _vp]),
 }
 
 

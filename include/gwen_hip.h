@@ -868,6 +868,46 @@ int gwen_containing_faces(const double *points, int64_t n, const double *mesh_po
                           int32_t *face, double *weights, void *workspace, size_t workspace_bytes,
                           gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Regridding (csrc/regrid.hip): the exact k nearest source points of every target point on the unit sphere, and the
+ * interpolation weights over them.  BUILD-DEFINED, PARITY UNPINNED (the reference moves no field between point sets).
+ * Positions as for the grid graphs: fp64 [n, 3] unit vectors.  The search runs through the same cell list; no atomics, two
+ * builds are bitwise equal.  1 <= k <= 8 (GWEN_EINVAL otherwise); sizes >= 2^31 - 1 are GWEN_ERANGE; bad arguments
+ * return before any HIP call; num_rows == 0 returns 0.
+ *
+ *   Candidates of target t: the listed sources -- and, with max_distance D >= 0 (a chord length; negative: no limit),
+ *         those with d2 <= D D -- where  d2 = (dx dx + dy dy) + dz dz  on  dst_pos[t] - src_pos[s],  fp64, in this
+ *         association (no fused multiply-add).  A SOURCE MASK is applied before the call: list the unmasked sources only
+ *         and pass their original indices as src_ids int32 [num_src] (NULL: a source reports its position in the list).
+ *   Row t:  its min(k, candidates) candidates in ascending (d2, reported index) order, compared lexicographically: the
+ *         lowest index wins every tie.  idx int32 [num_dst, k] padded with -1, d2 fp64 [num_dst, k] padded with +inf,
+ *         count int32 [num_dst] = min(k, candidates).
+ *   gwen_knn_query: ONE ROUND of the search at `radius` R (finite, > 0) for the targets `rows` (int32 [num_rows], each
+ *         in [0, num_dst); NULL: all targets, num_rows == num_dst).  One thread per row keeps its k best within R.  A
+ *         row with at least k candidates within R is final -- everything outside R is farther -- and is written; a row
+ *         with fewer is NOT written: its id goes to next_rows (int32, room for num_rows; row order kept) and
+ *         next_count int32 [1] (DEVICE) counts them.  The caller reads next_count back, doubles R and calls again with
+ *         rows = next_rows (another buffer).  A call with R >= D or R >= 2 (the whole sphere) writes every row it is
+ *         given and sets next_count = 0, so the loop ends; the result does not depend on the first R.
+ *         workspace: gwen_knn_workspace_bytes(num_src, num_dst).
+ *         A pole row of a lat-lon source is nlon coincident points in one cell: a target next to the pole walks all of
+ *         them.  This is accepted.
+ *   gwen_knn_weights: weights fp32 [num_dst, k] (0 in the padding) and entries int32 [num_dst] from d2 / count above,
+ *         computed in fp64 and rounded once.  GWEN_REGRID_IDW: w_j = u_j / ((u_0 + u_1) + ...) with u = d^-power,
+ *         d = sqrt(d2); power 1 and 2 are 1 / sqrt(d2) and 1 / d2 (no pow); power finite and > 0.  COINCIDENCE: a row whose
+ *         nearest d2 <= 1e-24 becomes ONE entry (entries = 1) of weight exactly 1.0f, so a NaN in a neighbour never reaches
+ *         a target that sits on a source.  GWEN_REGRID_NEAREST: one entry of weight 1.0f.  entries = 0 where count = 0.
+ * ------------------------------------------------------------------------------------------- */
+#define GWEN_REGRID_NEAREST 0
+#define GWEN_REGRID_IDW 1
+int gwen_knn_workspace_bytes(int64_t num_src, int64_t num_dst, size_t *bytes /* host */);
+int gwen_knn_query(const double *src_pos, const int32_t *src_ids, int64_t num_src, const double *dst_pos,
+                   int64_t num_dst, const int32_t *rows, int64_t num_rows, int k, double radius, double max_distance,
+                   int32_t *idx, double *d2, int32_t *count, int32_t *next_rows, int32_t *next_count,
+                   void *workspace, size_t workspace_bytes, gwen_stream_t stream);
+int gwen_knn_weights(const double *d2, const int32_t *count, int64_t num_dst, int k, int method, double power,
+                     float *weights, int32_t *entries, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
