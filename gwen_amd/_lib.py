@@ -105,6 +105,7 @@ SIGNATURES = {
     "gwen_gcn_transpose_rect": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "gwen_gcn_group8_capacity": (_i64, [_i64, _i64]),
     "gwen_gcn_group8": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "gwen_gcn_max_entries": (_int, [_vp, _i64, _vp, _vp]),
     "gwen_checksum_workspace_bytes": (_i64, []),
     "gwen_checksum128": (_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
     "gwen_gcn_segments_capacity": (_i64, [_i64, _i64, _i64]),
@@ -117,10 +118,14 @@ SIGNATURES = {
     "gwen_gcn_linear_nn_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp]),
     "gwen_gcn_layer_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                   _i64, _i64, _i64, _int, _int, _vp]),
+    "gwen_gcn_layer_entries_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                          _i64, _i64, _i64, _int, _int, _int, _vp]),
     "gwen_gcn_layer_supported": (_int, [_i64, _i64]),
     "gwen_gcn_chain_supported": (_int, [_i64, _i64, _i64, _int, _int]),
     "gwen_gcn_chain_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                   _int, _i64, _i64, _i64, _int, _vp]),
+    "gwen_gcn_chain_entries_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
+                                          _int, _i64, _i64, _i64, _int, _int, _vp]),
     "gwen_gcn_tiles64_count": (_i64, [_i64]),
     "gwen_gcn_tiles64": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gwen_cluster_rows64_host": (_int, [_vp, _vp, _i64, _i64, _vp]),
@@ -133,6 +138,10 @@ SIGNATURES = {
                                     _vp, _i64, _i64, _vp, C.POINTER(C.c_void_p),
                                     C.POINTER(LaunchInfo), C.c_int32, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_void_p)]),
+    "gwen_gnn_forward_entries_f32": (_int, [C.POINTER(GraphDesc), C.POINTER(LayerDesc), C.c_int32, _vp, _vp,
+                                            _vp, _i64, _i64, _vp, C.POINTER(C.c_void_p),
+                                            C.POINTER(LaunchInfo), C.c_int32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_void_p), _int]),
     "gwen_gcn_layer_bwd_f32": (_int, [_vp] * 8 + [_i64] * 4 + [_int, _vp]),
     "gwen_gcn_layer_bwd_bias_rows": (_i64, [_i64, _i64]),
     "gwen_gcn_layer_bwd_bias_f32": (_int, [_vp] * 8 + [_i64] * 4 + [_int, _vp, _vp, _vp]),

@@ -88,7 +88,9 @@ struct Cfg {
   static_assert(NWB % NJ1 == 0 && (F2 == 0 || NWB % NJ2 == 0), "waves must tile the columns");
 };
 
-template <int FIN, int F1, int F2, bool PRE, bool UNI, int NS>
+// GE: gathered entries per group (gather_rows.h; 7 only on the uniform layout).  It sits before NS because profile
+// tooling keys this kernel's name on its first and its last template argument.
+template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int NS>
 __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W1,
@@ -124,7 +126,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
   else               { if (bias) bpost = *reinterpret_cast<const float4_t *>(bias + j1 * 16 + 4 * mh); }
 
   // ---- phase 1: gather + aggregate (+ bias, ReLU when activation-first) -> LDS hi/lo -------------
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI>(
+  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE>(
       rowptr, col, val, xb, N, b0, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if constexpr (PRE) {
           acc = acc + bpre;
@@ -202,7 +204,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
 
 // Activation-first layer with nothing chained: out = act(A~ h + bias) on the grouped layout (the
 // fma form of K2; K2 itself keeps the rounded-product order that is bit-identical to the CPU path).
-template <int FIN, bool UNI>
+template <int FIN, bool UNI, int GE = 8>
 __global__ __launch_bounds__(256) void k_gather(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ bias,
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(256) void k_gather(
   const char *xb = reinterpret_cast<const char *>(x + (int64_t)blockIdx.y * mstride_x);
   float *om = out + (int64_t)blockIdx.y * mstride_o;
   const uint32_t lane_off = gl * 16;
-  gwen::gather_passes<FIN, 1, BR, UNI>(
+  gwen::gather_passes<FIN, 1, BR, UNI, GE>(
       rowptr, col, val, xb, N, lb * BR, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if (bias) acc = acc + *reinterpret_cast<const float4_t *>(bias + gl * 4);
         if (relu) {
@@ -231,9 +233,16 @@ __global__ __launch_bounds__(256) void k_gather(
 template <int FIN>
 int launch_gather(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
                   const float *bias, float *out, int64_t N, int64_t members, int64_t msx,
-                  int64_t mso, int relu, hipStream_t st) {
+                  int64_t mso, int relu, int entries, hipStream_t st) {
   constexpr int BR = 4 * (64 / (FIN / 4));
   dim3 grid((unsigned)((N + BR - 1) / BR), (unsigned)members);
+  if constexpr (FIN <= 64) {
+    if (!rowptr && entries == 7) {
+      k_gather<FIN, true, 7><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
+      GWEN_LAUNCH_CHECK();
+      return GWEN_OK;
+    }
+  }
   if (!rowptr)
     k_gather<FIN, true><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
   else
@@ -245,15 +254,23 @@ int launch_gather(const int32_t *rowptr, const int32_t *col, const float *val, c
 template <int FIN, int F1, int F2, bool PRE, int NS>
 int launch_ns(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
               const float *W1, const float *W2, const float *bias, float *out, int64_t N,
-              int64_t members, int64_t msx, int64_t mso, int relu, hipStream_t st) {
+              int64_t members, int64_t msx, int64_t mso, int relu, int entries, hipStream_t st) {
   using C = Cfg<FIN, F1, F2, PRE, NS>;
   const int64_t blocks = (N + C::BR - 1) / C::BR;
   dim3 grid((unsigned)blocks, (unsigned)members);
+  if constexpr (FIN <= 64 && F1 <= 64) {           // 7 gathered entries: the narrow kernels only
+    if (!rowptr && entries == 7) {
+      k_chain<FIN, F1, F2, PRE, true, 7, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
+                                                                           (int32_t)N, msx, mso, relu);
+      GWEN_LAUNCH_CHECK();
+      return GWEN_OK;
+    }
+  }
   if (!rowptr)
-    k_chain<FIN, F1, F2, PRE, true, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
+    k_chain<FIN, F1, F2, PRE, true, 8, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
                                                                       (int32_t)N, msx, mso, relu);
   else
-    k_chain<FIN, F1, F2, PRE, false, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
+    k_chain<FIN, F1, F2, PRE, false, 8, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
                                                                        out, (int32_t)N, msx, mso, relu);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
@@ -262,15 +279,15 @@ int launch_ns(const int32_t *rowptr, const int32_t *col, const float *val, const
 template <int FIN, int F1, int F2, bool PRE>
 int launch(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
            const float *W1, const float *W2, const float *bias, float *out, int64_t N,
-           int64_t members, int64_t msx, int64_t mso, int relu, int contract, hipStream_t st) {
+           int64_t members, int64_t msx, int64_t mso, int relu, int contract, int entries, hipStream_t st) {
   if (contract == GWEN_CONTRACT_BF16X6) {
     // width triples whose three images do not fit a CU's LDS are refused by gwen_gcn_chain_supported already
     if constexpr (Cfg<FIN, F1, F2, PRE, 3>::lds_elems * 2 <= 160 * 1024)
-      return launch_ns<FIN, F1, F2, PRE, 3>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, st);
+      return launch_ns<FIN, F1, F2, PRE, 3>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, st);
     else
       return GWEN_EINVAL;
   }
-  return launch_ns<FIN, F1, F2, PRE, 2>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, st);
+  return launch_ns<FIN, F1, F2, PRE, 2>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, st);
 }
 
 constexpr bool width_ok(int64_t f) { return f == 16 || f == 32 || f == 64 || f == 128; }
@@ -296,11 +313,13 @@ extern "C" int gwen_gcn_chain_supported(int64_t Fin, int64_t F1, int64_t F2, int
   return chain_lds_bytes(Fin, F1, F2, ns) <= 80 * 1024 ? 1 : 0;
 }
 
-extern "C" int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                  const float *x, const float *W1, const float *W2,
-                                  const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
-                                  int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
-                                  int64_t mstride_o, int contract, gwen_stream_t stream_) {
+// entries = 7: the caller's promise (uniform layout, every row at most 7 stored entries), see gwen_gcn_layer_entries_f32
+extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                          const float *x, const float *W1, const float *W2,
+                                          const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                          int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                          int64_t mstride_o, int contract, int entries, gwen_stream_t stream_) {
+  if (entries != 7 && entries != 8) return GWEN_EINVAL;
   if (N < 0 || members < 0) return GWEN_EINVAL;
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return GWEN_EINVAL;
   if (N == 0 || members == 0) return GWEN_OK;
@@ -315,18 +334,18 @@ extern "C" int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, con
   if (pre && F1 == 0) {
 #define GWEN_G(FI)                                                                                  \
   if (Fin == FI)                                                                                    \
-    return launch_gather<FI>(rowptr, col, val, x, bias, out, N, members, mstride_x, mstride_o, relu, st)
+    return launch_gather<FI>(rowptr, col, val, x, bias, out, N, members, mstride_x, mstride_o, relu, entries, st)
     GWEN_G(16); GWEN_G(32); GWEN_G(64); GWEN_G(128);
 #undef GWEN_G
   }
 #define GWEN_P(FI, FA)                                                                              \
   if (pre && Fin == FI && F1 == FA)                                                                 \
     return launch<FI, FA, 0, true>(rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x,   \
-                                   mstride_o, relu, contract, st)
+                                   mstride_o, relu, contract, entries, st)
 #define GWEN_C(FI, FA, FB)                                                                          \
   if (!pre && Fin == FI && F1 == FA && F2 == FB)                                                    \
     return launch<FI, FA, FB, false>(rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, \
-                                     mstride_o, relu, contract, st)
+                                     mstride_o, relu, contract, entries, st)
 #define GWEN_ROW(FI)                                                                                \
   GWEN_P(FI, 16); GWEN_P(FI, 32); GWEN_P(FI, 64); GWEN_P(FI, 128);                                  \
   GWEN_C(FI, 32, 16); GWEN_C(FI, 64, 16); GWEN_C(FI, 64, 32);                                       \
@@ -336,4 +355,13 @@ extern "C" int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, con
 #undef GWEN_C
 #undef GWEN_P
   return GWEN_EINVAL;
+}
+
+extern "C" int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                  const float *x, const float *W1, const float *W2,
+                                  const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                  int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                  int64_t mstride_o, int contract, gwen_stream_t stream_) {
+  return gwen_gcn_chain_entries_f32(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members,
+                                    mstride_x, mstride_o, contract, 8, stream_);
 }

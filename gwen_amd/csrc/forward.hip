@@ -73,12 +73,14 @@ extern "C" int64_t gwen_gnn_forward_scratch_floats(int64_t N, int64_t members,
   return P.total;
 }
 
-extern "C" int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
-                                    int32_t n_layers, const float *x, float *out, float *scratch,
-                                    int64_t scratch_floats, int64_t members, gwen_stream_t stream,
-                                    void **events, gwen_launch_info *info, int32_t max_launches,
-                                    int32_t *n_launches, float *const *acts) {
-  if (!graph) return GWEN_EINVAL;
+// entries: what the K4 / K5 launches are told about the grouped layout (gwen_gcn_layer_entries_f32): 8, or 7 when
+// g_rowptr is NULL and every row of the graph holds at most 7 stored entries (gwen_gcn_max_entries)
+extern "C" int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
+                                            int32_t n_layers, const float *x, float *out, float *scratch,
+                                            int64_t scratch_floats, int64_t members, gwen_stream_t stream,
+                                            void **events, gwen_launch_info *info, int32_t max_launches,
+                                            int32_t *n_launches, float *const *acts, int entries) {
+  if (!graph || (entries != 7 && entries != 8)) return GWEN_EINVAL;
   const int64_t N = graph->N;
   const int32_t *rowptr = graph->rowptr, *col = graph->col, *g_rowptr = graph->g_rowptr,
                 *g_col = graph->g_col;
@@ -154,16 +156,16 @@ extern "C" int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_de
       float *dst = acts ? acts[i] : ((last) ? out : buf[nbuf++ & 1]);
       if (chain) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fo, layers[i + 1].fout));
-        GWEN_TRY(gwen_gcn_chain_f32(g_rowptr, g_col, g_val, cur, layers[i + 1].W, nullptr, L.bias,
+        GWEN_TRY(gwen_gcn_chain_entries_f32(g_rowptr, g_col, g_val, cur, layers[i + 1].W, nullptr, L.bias,
                                     dst, N, fo, layers[i + 1].fout, 0, 1, L.relu, members, N * fo,
-                                    N * layers[i + 1].fout, cn, stream));
+                                    N * layers[i + 1].fout, cn, entries, stream));
         GWEN_TRY(after());
         projected = true;
       } else if (have_grouped && gwen_gcn_chain_supported(fo, 0, 0, 1, GWEN_CONTRACT_BF16X3)) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fo, fo));
-        GWEN_TRY(gwen_gcn_chain_f32(g_rowptr, g_col, g_val, cur, nullptr, nullptr, L.bias, dst, N,
+        GWEN_TRY(gwen_gcn_chain_entries_f32(g_rowptr, g_col, g_val, cur, nullptr, nullptr, L.bias, dst, N,
                                     fo, 0, 0, 1, L.relu, members, N * fo, N * fo, GWEN_CONTRACT_BF16X3,
-                                    stream));           // no contraction in this form
+                                    entries, stream));  // no contraction in this form
         GWEN_TRY(after());
         projected = false;
       } else {
@@ -199,16 +201,16 @@ extern "C" int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_de
       float *dst = acts ? acts[i] : ((last && !chain) ? out : buf[nbuf++ & 1]);
       if (chain) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fi, layers[i + 1].fout));
-        GWEN_TRY(gwen_gcn_chain_f32(g_rowptr, g_col, g_val, cur, L.W, layers[i + 1].W, L.bias, dst,
+        GWEN_TRY(gwen_gcn_chain_entries_f32(g_rowptr, g_col, g_val, cur, L.W, layers[i + 1].W, L.bias, dst,
                                     N, fi, fo, layers[i + 1].fout, 0, L.relu, members, N * fi,
-                                    N * layers[i + 1].fout, cc, stream));
+                                    N * layers[i + 1].fout, cc, entries, stream));
         GWEN_TRY(after());
         projected = true;
       } else {
         GWEN_TRY(before(GWEN_KIND_LAYER, i, fi, fo));
-        GWEN_TRY(gwen_gcn_layer_f32(g_rowptr, g_col, g_val, cur, L.W, L.bias, dst, N, fi, fo, fi, fo,
+        GWEN_TRY(gwen_gcn_layer_entries_f32(g_rowptr, g_col, g_val, cur, L.W, L.bias, dst, N, fi, fo, fi, fo,
                                     members, N * fi, N * fo, L.relu,
-                                    o == GWEN_ORDER_FUSED_EXACT ? GWEN_CONTRACT_F32 : cc, stream));
+                                    o == GWEN_ORDER_FUSED_EXACT ? GWEN_CONTRACT_F32 : cc, entries, stream));
         GWEN_TRY(after());
       }
       cur = dst;
@@ -241,6 +243,15 @@ extern "C" int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_de
 #undef GWEN_TRY
   if (n_launches) *n_launches = nl;
   return GWEN_OK;
+}
+
+extern "C" int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
+                                    int32_t n_layers, const float *x, float *out, float *scratch,
+                                    int64_t scratch_floats, int64_t members, gwen_stream_t stream,
+                                    void **events, gwen_launch_info *info, int32_t max_launches,
+                                    int32_t *n_launches, float *const *acts) {
+  return gwen_gnn_forward_entries_f32(graph, layers, n_layers, x, out, scratch, scratch_floats, members, stream,
+                                      events, info, max_launches, n_launches, acts, 8);
 }
 
 extern "C" int gwen_event_create(void **event) {

@@ -7,6 +7,14 @@
 // the column indices of pass p+1 are requested before pass p's row gathers are waited for, and
 // pass p's weights ride along with its gathers, so a pass costs one memory round trip, not two.
 // UNI: uniform layout (every row exactly one group, rowptr == NULL): row r is the group at 8 r.
+// GE: entries of a group that are gathered (8, or 7 on a uniform layout whose rows all hold at most 7
+// entries -- a geodesic mesh: 6 neighbours + the self loop -- so that slot 7 is padding on EVERY row).
+// With GE = 7 the slot's row load and its 4 FMAs are not issued; the two 16-B index loads and the two
+// 16-B weight loads stay whole and the layout is the same.  It is a template argument, never a per-lane
+// or per-row branch, for the reason above: every load that is issued stays unconditional.
+// Results: the skipped term is fma(0, v, acc), so for finite inputs every value is the same; only the
+// sign of an exact zero can differ (-0 + 0 = +0), and an Inf / NaN in the row of a destination's FIRST
+// entry (the pad slot's column) no longer turns the sum into NaN through 0 * Inf.
 #pragma once
 #include "common.h"
 
@@ -15,33 +23,36 @@ namespace gwen {
 typedef int int4_u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float float4_u __attribute__((ext_vector_type(4), aligned(4)));
 
-template <int FIN>
+template <int FIN, int GE = 8>
 __device__ inline float4_t gather_group(const char *xb, uint32_t lane_off, const int4_u &c0,
                                         const int4_u &c1, const float4_u &w0, const float4_u &w1,
                                         float4_t acc) {
   constexpr uint32_t kRowBytes = FIN * 4;        // x rows are contiguous: base + 32-bit byte offset
-  float4_t v[8];
+  static_assert(GE == 7 || GE == 8, "a group is gathered whole or without its last slot");
+  float4_t v[GE];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     v[u] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)((uint32_t)c0[u] * kRowBytes + lane_off));
-    v[u + 4] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)((uint32_t)c1[u] * kRowBytes + lane_off));
+    if (u + 4 < GE)
+      v[u + 4] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)((uint32_t)c1[u] * kRowBytes + lane_off));
   }
 #pragma unroll
   for (int u = 0; u < 4; ++u)
     acc = __builtin_elementwise_fma(float4_t{w0[u], w0[u], w0[u], w0[u]}, v[u], acc);
 #pragma unroll
-  for (int u = 0; u < 4; ++u)
+  for (int u = 0; u < GE - 4; ++u)
     acc = __builtin_elementwise_fma(float4_t{w1[u], w1[u], w1[u], w1[u]}, v[u + 4], acc);
   return acc;
 }
 
 // sink(lr, acc): lr = row index inside the block (p * RB + wave * R + gr), acc = aggregated 4 floats
-template <int FIN, int NP, int RB, bool UNI, typename Sink>
+template <int FIN, int NP, int RB, bool UNI, int GE = 8, typename Sink>
 __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
                                      const int32_t *__restrict__ col,
                                      const float *__restrict__ val, const char *xb, int32_t N,
                                      int b0, int wave, int gr, uint32_t lane_off, Sink &&sink) {
   constexpr int R = 64 / (FIN / 4);
+  static_assert(GE == 8 || UNI, "only the uniform layout bounds a row by one group");
   // group offset and row end of pass p (absent rows: the null group, which ends at once)
   auto locate = [&](int p, int32_t &s, int32_t &rb) {
     const int r = b0 + p * RB + wave * R + gr;
@@ -72,7 +83,7 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
     }
     const float4_u w0 = *reinterpret_cast<const float4_u *>(val + s);
     const float4_u w1 = *reinterpret_cast<const float4_u *>(val + s + 4);
-    float4_t acc = gather_group<FIN>(xb, lane_off, c0, c1, w0, w1, float4_t{0.f, 0.f, 0.f, 0.f});
+    float4_t acc = gather_group<FIN, GE>(xb, lane_off, c0, c1, w0, w1, float4_t{0.f, 0.f, 0.f, 0.f});
     if constexpr (!UNI) {
       for (int32_t q = s + 8; q < rb; q += 8) {          // rows longer than one group of 8
         const int4_u d0 = *reinterpret_cast<const int4_u *>(col + q);

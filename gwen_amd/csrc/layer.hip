@@ -12,7 +12,9 @@
 //            entries of a group in flight together) from the GROUPED layout (rows padded to whole
 //            groups of 8 with weight-0 entries, null group for absent rows), so every load in the
 //            loop is unconditional -- a load under a per-lane condition makes hipcc branch around it
-//            and wait vmcnt(0), which serialises the gathers.  The aggregated rows go to the block's
+//            and wait vmcnt(0), which serialises the gathers.  On a uniform layout whose rows all hold
+//            at most 7 entries (GE = 7, gather_rows.h) the 8th slot -- padding on every row -- is not
+//            gathered at all.  The aggregated rows go to the block's
 //            LDS tile.  Meanwhile each wave fetches ITS slice of W^T -- the B fragments of its 16
 //            output columns -- straight from global memory (16 KB, L1/L2-resident) into registers;
 //   barrier;
@@ -66,7 +68,8 @@ struct Cfg {
 // BWD (the layer's backward, gwen_gcn_layer_bwd_f32): the aggregated rows are also stored (agg_out: the
 // operand of grad_W) and the result is masked by mask > 0 (the ReLU of the layer below), so the launch
 // returns the gradient the next backward launch starts from.
-template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false>
+// GE: gathered entries per group (gather_rows.h); 7 only on the uniform layout.
+template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8>
 __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void k_layer(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W,
@@ -129,7 +132,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   for (int chunk = lb; chunk < nchunks; chunk += nb) {
   const int b0 = chunk * C::BR;
   // ---- phase 1: gather + aggregate into the LDS tile (gather_rows.h) ------------------------------
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI>(
+  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE>(
       rowptr, col, val, xb, N, b0, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if constexpr (BWD) {
           if (agg_out && b0 + lr < N)
@@ -223,7 +226,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   }
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE = 8>
 int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
                 const float *W, const float *bias, float *out, int64_t N, int64_t ldo, int64_t members,
                 int64_t msx, int64_t mso, int relu, hipStream_t st, bool probe, int64_t *resident_out,
@@ -234,7 +237,7 @@ int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, con
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true>), C::NWB * 64, 0));
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE>), C::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
   const int64_t resident = (int64_t)256 * per_cu;
@@ -260,7 +263,7 @@ int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, con
     }
   }
   if (!rowptr)      // uniform layout: row r is the group at 8 r
-    k_layer<FIN, FOUT, NS, BRMIN, true><<<grid, C::NWB * 64, 0, st>>>(
+    k_layer<FIN, FOUT, NS, BRMIN, true, false, GE><<<grid, C::NWB * 64, 0, st>>>(
         rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu);
   else
     k_layer<FIN, FOUT, NS, BRMIN, false><<<grid, C::NWB * 64, 0, st>>>(
@@ -269,14 +272,15 @@ int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, con
   return GWEN_OK;
 }
 
-template <int FIN, int FOUT, int NS>
+template <int FIN, int FOUT, int NS, int GE = 8>
 int launch(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
            const float *W, const float *bias, float *out, int64_t N, int64_t ldo, int64_t members,
            int64_t msx, int64_t mso, int relu, hipStream_t st, float *agg_out = nullptr,
            const float *mask = nullptr, bool bwd = false, float *bsum_out = nullptr, int64_t *chunks_out = nullptr) {
 #define GWEN_ROWS(BRV, PROBE, RES)                                                                  \
-  launch_rows<FIN, FOUT, NS, BRV>(rowptr, col, val, x, W, bias, out, N, ldo, members, msx, mso,  \
-                                     relu, st, PROBE, RES, agg_out, mask, bwd, bsum_out, chunks_out)
+  launch_rows<FIN, FOUT, NS, BRV, GE>(rowptr, col, val, x, W, bias, out, N, ldo, members, msx, mso,  \
+                                      relu, st, PROBE, RES, agg_out, mask, bwd, bsum_out, chunks_out)
+  static_assert(GE == 8 || (FIN <= 64 && FOUT <= 64), "7 gathered entries: narrow layers only");
   if constexpr (FIN <= 64 && FOUT <= 64) {
     // Narrow layers run as ONE round of co-resident blocks when a block size makes that possible: with
     // 64-row blocks the c2 mesh needs 1 563 blocks against 1 024 resident ones (4 per CU at 64 -> 64),
@@ -303,11 +307,8 @@ int launch(const int32_t *rowptr, const int32_t *col, const float *val, const fl
     return GWEN_ROWS(64, false, nullptr);
   } else {
     // rows per block: enough that W (read once per block) stays a small fraction of the gathered bytes
-#ifndef K4_BR256X6
-#define K4_BR256X6 64
-#endif
-    // 256: 64 rows keep two blocks per CU in LDS (bf16x3); K4_BR256X6: rows per block at 256 channels on bf16x6
-    constexpr int BRMIN = FIN == 128 ? 128 : (FIN == 256 && NS == 3 ? K4_BR256X6 : 64);
+    // 256: 64 rows keep two blocks per CU in LDS (bf16x3), and 64 rows at 256 channels on bf16x6 as well
+    constexpr int BRMIN = FIN == 128 ? 128 : 64;
     return GWEN_ROWS(BRMIN, false, nullptr);
   }
 #undef GWEN_ROWS
@@ -321,11 +322,14 @@ extern "C" int gwen_gcn_layer_supported(int64_t Fin, int64_t Fout) {
   return width_ok(Fin) && width_ok(Fout) ? 1 : 0;
 }
 
-extern "C" int gwen_gcn_layer_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                  const float *x, const float *W, const float *bias, float *out,
-                                  int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
-                                  int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
-                                  int exact, gwen_stream_t stream_) {
+// entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
+// kernels turn into one gather less per row; every other shape and layout gathers whole groups
+extern "C" int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                          const float *x, const float *W, const float *bias, float *out,
+                                          int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                          int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                          int exact, int entries, gwen_stream_t stream_) {
+  if (entries != 7 && entries != 8) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
   if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
   if (N == 0 || members == 0) return GWEN_OK;
@@ -336,6 +340,22 @@ extern "C" int gwen_gcn_layer_f32(const int32_t *rowptr, const int32_t *col, con
     return GWEN_EINVAL;                       // x rows must be contiguous (32-bit row offsets)
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   hipStream_t st = gwen_stream(stream_);
+  if (entries == 7 && !rowptr && Fin <= 64 && Fout <= 64) {
+#define GWEN_L7(FI, FO)                                                                          \
+  if (Fin == FI && Fout == FO)                                                                   \
+    return exact == GWEN_CONTRACT_F32                                                            \
+               ? launch<FI, FO, 0, 7>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, \
+                                      mstride_o, relu, st)                                       \
+               : (exact == GWEN_CONTRACT_BF16X6                                                  \
+                      ? launch<FI, FO, 3, 7>(rowptr, col, val, x, W, bias, out, N, ldo, members, \
+                                             mstride_x, mstride_o, relu, st)                     \
+                      : launch<FI, FO, 2, 7>(rowptr, col, val, x, W, bias, out, N, ldo, members, \
+                                             mstride_x, mstride_o, relu, st))
+    GWEN_L7(16, 16); GWEN_L7(16, 32); GWEN_L7(16, 64);
+    GWEN_L7(32, 16); GWEN_L7(32, 32); GWEN_L7(32, 64);
+    GWEN_L7(64, 16); GWEN_L7(64, 32); GWEN_L7(64, 64);
+#undef GWEN_L7
+  }
 #define GWEN_L(FI, FO)                                                                           \
   if (Fin == FI && Fout == FO)                                                                   \
     return exact == GWEN_CONTRACT_F32                                                            \
@@ -354,6 +374,15 @@ extern "C" int gwen_gcn_layer_f32(const int32_t *rowptr, const int32_t *col, con
   GWEN_L(256, 16); GWEN_L(256, 32); GWEN_L(256, 64); GWEN_L(256, 128); GWEN_L(256, 256);
 #undef GWEN_L
   return GWEN_EINVAL;
+}
+
+extern "C" int gwen_gcn_layer_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                  const float *x, const float *W, const float *bias, float *out,
+                                  int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                  int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                  int exact, gwen_stream_t stream_) {
+  return gwen_gcn_layer_entries_f32(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members,
+                                    mstride_x, mstride_o, relu, exact, 8, stream_);
 }
 
 // The layer's backward as ONE launch of the same kernel on the TRANSPOSED graph (grouped arrays of the

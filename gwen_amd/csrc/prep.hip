@@ -188,6 +188,29 @@ __global__ void k_glen(const int32_t *__restrict__ rowptr, int64_t N, int32_t *_
 
 __global__ void k_set1(int32_t *p) { *p = 1; }
 
+// the longest row of a CSR: ONE block strides over the rows, lanes meet by shuffles, waves through LDS in wave order
+// (no atomics; once per graph, 100 k rows are 100 loads per thread)
+__global__ __launch_bounds__(1024) void k_maxlen(const int32_t *__restrict__ rowptr, int64_t N,
+                                                 int32_t *__restrict__ out) {
+  __shared__ int32_t wmax[16];
+  int32_t m = 0;
+  for (int64_t r = threadIdx.x; r < N; r += blockDim.x) {
+    const int32_t len = rowptr[r + 1] - rowptr[r];
+    m = len > m ? len : m;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int32_t t = __shfl_xor(m, o);
+    m = t > m ? t : m;
+  }
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = wmax[w] > m ? wmax[w] : m;
+    *out = m;
+  }
+}
+
 // ---- row segmentation (long rows): row r of length len is cut into max(1, ceil(len / S)) segments -----
 __global__ void k_segcount(const int32_t *__restrict__ rowptr, int64_t N, int32_t S,
                            int32_t *__restrict__ cnt, int32_t *__restrict__ status) {
@@ -450,6 +473,14 @@ extern "C" int gwen_gcn_group8(const int32_t *rowptr, const int32_t *col, const 
                                          rocprim::plus<int32_t>(), stream));
   k_gfill<<<blocks_for((N + 1) * 8), kThreads, 0, stream>>>(rowptr, col, val, g_rowptr, N, g_col,
                                                             g_val);
+  GWEN_LAUNCH_CHECK();
+  return GWEN_OK;
+}
+
+extern "C" int gwen_gcn_max_entries(const int32_t *rowptr, int64_t N, int32_t *max_entries, gwen_stream_t stream_) {
+  if (N < 0 || !max_entries || (N > 0 && !rowptr)) return GWEN_EINVAL;
+  if (N >= (int64_t(1) << 31) - 2) return GWEN_ERANGE;
+  k_maxlen<<<1, 1024, 0, gwen_stream(stream_)>>>(rowptr, N, max_entries);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
 }

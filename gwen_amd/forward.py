@@ -267,14 +267,15 @@ class StackForward:
         scratch = self._scratch_for(members, dev)
         gd = self._graph_desc(members)
         with torch.cuda.device(dev):
-            rc = _lib.lib().gwen_gnn_forward_f32(
+            rc = _lib.lib().gwen_gnn_forward_entries_f32(
                 C.byref(gd), self.desc, len(self.desc), _ptr(x),
                 _ptr(out), _ptr(scratch), scratch.numel(), members, _stream(dev),
                 None if events is None else events._ev,
                 None if events is None else events.info,
                 0 if events is None else events.max_launches,
-                None if events is None else C.byref(events.n), acts_arr)
-        _lib.check(rc, "gwen_gnn_forward_f32")
+                None if events is None else C.byref(events.n), acts_arr,
+                8 if self._small else self.graph.entries())
+        _lib.check(rc, "gwen_gnn_forward_entries_f32")
         return out
 
 

@@ -49,6 +49,7 @@ class GraphCSR:
     _workspace: Optional[Tensor] = field(default=None, repr=False)
     _transposed: Optional[Tuple[Tensor, Tensor, Tensor]] = field(default=None, repr=False)
     _grouped: Optional[Tuple[Optional[Tensor], Tensor, Tensor]] = field(default=None, repr=False)
+    _entries: int = field(default=8, repr=False)
     _dense: Optional[Tensor] = field(default=None, repr=False)
     _dense_tsq: Optional[Tensor] = field(default=None, repr=False)
     _tiles: Optional[tuple] = field(default=None, repr=False)
@@ -74,6 +75,12 @@ class GraphCSR:
         if self._grouped is None:
             self._grouped = _grouped_impl(self)
         return self._grouped
+
+    def entries(self) -> int:
+        """Entries of a group that K4 / K5 have to gather on this graph's grouped layout: 7 when the layout is uniform
+        and no row holds more than 7 stored entries (geodesic meshes: slot 7 is padding on every row), else 8."""
+        self.grouped()
+        return self._entries
 
     def tiles(self) -> Optional[Tuple[Tensor, Tensor, Tensor, int]]:
         """Tile layout for K8 (t_rows, t_lid, t_val, largest union): destination rows in tiles of 64 with the union of the
@@ -256,17 +263,23 @@ def _grouped_impl(g: "GraphCSR") -> Tuple[Tensor, Tensor, Tensor]:
     g_rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
     g_col = torch.empty(gcap, dtype=torch.int32, device=dev)
     g_val = torch.empty(gcap, dtype=torch.float32, device=dev)
-    uniform = torch.empty(1, dtype=torch.int32, device=dev)
+    uniform = torch.empty(2, dtype=torch.int32, device=dev)       # [uniform flag, longest row]
     ws = g._workspace if g._workspace is not None else _alloc_workspace(n, g.num_edges, dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().gwen_gcn_group8(_ptr(g.rowptr), _ptr(g.col), _ptr(g.val), n, cap,
                                         _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(uniform),
                                         _ptr(ws), ws.numel(), _stream(dev))
+        rc2 = _lib.lib().gwen_gcn_max_entries(_ptr(g.rowptr), n, _ptr(uniform[1:]), _stream(dev))
     _lib.check(rc, "gwen_gcn_group8")
+    _lib.check(rc2, "gwen_gcn_max_entries")
     # uniform layout (every row exactly one group, e.g. bounded-degree meshes): the kernels take
-    # rowptr = NULL and compute the group offset 8 r themselves; one flag read-back, once per graph
-    if n > 0 and int(uniform.item()) == 1 and n < (1 << 28):
+    # rowptr = NULL and compute the group offset 8 r themselves; one read-back of the flag and the bound, once per
+    # graph.  With a bound of 7 the kernels skip the group's last slot (padding on every row).
+    flag, bound = uniform.tolist()
+    if n > 0 and flag == 1 and n < (1 << 28):
+        g._entries = 7 if bound <= 7 else 8
         return None, g_col, g_val
+    g._entries = 8
     return g_rowptr, g_col, g_val
 
 

@@ -209,11 +209,11 @@ def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tenso
     dev = x.device
     g_rowptr, g_col, g_val = graph.grouped()
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_layer_f32(
+        rc = _lib.lib().gwen_gcn_layer_entries_f32(
             _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), _ptr(weight), _ptr(bias),
             _ptr(out), n, fin, fout, fin, fout, m, n_src * fin, n * fout, int(relu),
-            _dense_code(contract, exact), _stream(dev))
-    _lib.check(rc, "gwen_gcn_layer_f32")
+            _dense_code(contract, exact), graph.entries(), _stream(dev))
+    _lib.check(rc, "gwen_gcn_layer_entries_f32")
     return out
 
 
@@ -312,12 +312,12 @@ def chain(graph: GraphCSR, x: Tensor, w1: Tensor, w2: Optional[Tensor], bias: Op
     g_rowptr, g_col, g_val = graph.grouped()
     dev = x.device
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_chain_f32(
+        rc = _lib.lib().gwen_gcn_chain_entries_f32(
             _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), _ptr(w1.contiguous()),
             None if w2 is None else _ptr(w2.contiguous()), None if bias is None else _ptr(bias.contiguous()),
             _ptr(out), n, fin, f1, f2, int(pre), int(relu), m, n * fin, n * fw, _dense_code(contract),
-            _stream(dev))
-    _lib.check(rc, "gwen_gcn_chain_f32")
+            graph.entries(), _stream(dev))
+    _lib.check(rc, "gwen_gcn_chain_entries_f32")
     return out
 
 

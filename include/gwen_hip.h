@@ -93,6 +93,11 @@ int64_t gwen_gcn_group8_capacity(int64_t N, int64_t cap);
 int gwen_gcn_group8(const int32_t *rowptr, const int32_t *col, const float *val, int64_t N,
                     int64_t cap, int32_t *g_rowptr, int32_t *g_col, float *g_val, int32_t *uniform,
                     void *workspace, size_t workspace_bytes, gwen_stream_t stream);
+/* The bound of a prepared CSR: *max_entries (device int32 [1]) = the largest number of stored entries of any row
+ * (0 for N = 0).  One small launch, no atomics; read it back once per graph, with `uniform`.  On a uniform layout
+ * whose bound is at most 7 -- a geodesic mesh: 6 neighbours and the self loop -- slot 7 of every group is padding,
+ * and the *_entries_f32 forms of K4 / K5 / the stack launcher may be told entries = 7. */
+int gwen_gcn_max_entries(const int32_t *rowptr, int64_t N, int32_t *max_entries, gwen_stream_t stream);
 
 /* Content checksum of a device buffer (128 bits: two independent position-dependent 64-bit sums over its
  * 8-byte words), the key under which a caller caches prepared graphs: the reference's loaders hand every
@@ -198,6 +203,18 @@ int gwen_gcn_layer_f32(const int32_t *rowptr, const int32_t *col, const float *v
                        int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
                        int64_t mstride_o, int relu, int exact, gwen_stream_t stream);
 int gwen_gcn_layer_supported(int64_t Fin, int64_t Fout);
+/* The same with the number of entries of a group that are gathered: entries = 8 is gwen_gcn_layer_f32; entries = 7
+ * is the CALLER'S PROMISE that rowptr is NULL (uniform layout) and that every row holds at most 7 stored entries
+ * (gwen_gcn_max_entries), like the `uniform` contract itself: on a graph with a row of 8 the 8th entry is silently
+ * dropped.  Fin, Fout <= 64 then issue 7 row gathers and 7 FMA groups per row instead of 8; with a non-NULL rowptr or at
+ * other widths the whole group is gathered.  For finite inputs every value equals that of entries = 8 (the skipped
+ * term is fma(0, v, acc)); only the sign of an exact zero can differ, and an Inf / NaN in the row of a destination's
+ * first entry (the padding slot's column) is no longer turned into NaN through 0 * Inf.  entries outside {7, 8}:
+ * GWEN_EINVAL. */
+int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                               const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                               int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                               int64_t mstride_o, int relu, int exact, int entries, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K8  K4's contract for WIDE layers on locality-ordered bounded-degree graphs (meshes), tile-staged:
@@ -264,6 +281,11 @@ int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, const float *v
                        const float *W1, const float *W2, const float *bias, float *out, int64_t N,
                        int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
                        int64_t mstride_x, int64_t mstride_o, int contract, gwen_stream_t stream);
+/* entries: as gwen_gcn_layer_entries_f32 (7 acts at Fin, F1 <= 64, the activation-first form included). */
+int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                               const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+                               int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
+                               int64_t mstride_x, int64_t mstride_o, int contract, int entries, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-stack forward == GNNModel.forward (/root/reference/src/gwen/models_gnn.py:292-303 ->
@@ -337,6 +359,12 @@ int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
                          int64_t members, gwen_stream_t stream, void **events,
                          gwen_launch_info *info, int32_t max_launches, int32_t *n_launches,
                          float *const *acts);
+/* entries: handed to every K4 / K5 launch of the stack (gwen_gcn_layer_entries_f32); 8 = gwen_gnn_forward_f32. */
+int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_layer_desc *layers, int32_t n_layers,
+                                 const float *x, float *out, float *scratch, int64_t scratch_floats,
+                                 int64_t members, gwen_stream_t stream, void **events,
+                                 gwen_launch_info *info, int32_t max_launches, int32_t *n_launches,
+                                 float *const *acts, int entries);
 
 /* ---------------------------------------------------------------------------------------------
  * K7  a whole GCNConv layer on a SMALL graph (N <= 256) with wide features -- the reference's own
