@@ -28,6 +28,7 @@ from typing import Optional, Tuple
 
 import torch
 from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from .graph import _ptr, _stream
@@ -180,6 +181,32 @@ class _ActFunction(torch.autograd.Function):
         return _ew(_lib.EW_MUL, g.contiguous().clone(), d), None
 
 
+class _FeedForwardFunction(torch.autograd.Function):
+    """x1 + mlp.2(act(mlp.0(norm2(x1)))) with autograd.  The forward is the launch set the block takes without
+    gradients -- the LayerNorm kernel and ONE K6 launch (mlp2 with the residual) -- so a training forward and an inference
+    forward are the same bits; it saves x1 and the six parameters, nothing hidden-sized.  The backward forms the half
+    again piece by piece (``GraphTransformer._feed_forward_pieces``: LayerNorm, K3, activation, K3, each with its own
+    autograd Function on libgwen_hip.so) and differentiates that."""
+
+    @staticmethod
+    def forward(ctx, net, x1: Tensor, *params) -> Tensor:
+        ctx.net = net
+        ctx.save_for_backward(x1, *params)
+        return net._feed_forward_fused(x1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g: Tensor):
+        x1, *params = ctx.saved_tensors
+        needs = ctx.needs_input_grad[1:]
+        with torch.enable_grad():
+            xd = x1.detach().requires_grad_(needs[0])
+            y = ctx.net._feed_forward_pieces(xd)
+        wanted = [t for t, n in zip([xd, *ctx.net._feed_forward_parameters()], needs) if n]
+        grads = iter(torch.autograd.grad(y, wanted, g, allow_unused=True))
+        return (None,) + tuple(next(grads) if n else None for n in needs)
+
+
 class GraphTransformer(nn.Module):
     """``forward(x_src, x_dst, e, graph, update_edges=True, ee=None) -> (x_dst', e)`` (module docstring); edges are not
     updated: ``e`` is returned as given (None with ``update_edges=False``, as InteractionNet).  ``ee=``: the edge term
@@ -189,8 +216,9 @@ class GraphTransformer(nn.Module):
     Parameters: ``norm1, lin_q, lin_kv, lin_e, lin_o, norm2, mlp.0, mlp.2`` (lin_kv.weight [2F, F]: rows k, then v;
     lin_e has no bias).  ``precision`` ("3xbf16", the default, or "f16x3": fp32-class) governs every K3 / K6 contraction
     of the block, as in InteractionNet; the attention kernel, the LayerNorms and the residuals are fp32 on both.  A
-    setting, not a parameter.  Without gradients the feed-forward half is ONE K6 launch (mlp2 with the residual); with
-    gradients every piece runs through its own autograd Function on libgwen_hip.so."""
+    setting, not a parameter.  The feed-forward half is ONE K6 launch (mlp2 with the residual), with gradients too
+    (``_FeedForwardFunction``: its backward forms the half again piece by piece), so the block computes the same bits
+    with and without gradients; every other piece runs through its own autograd Function on libgwen_hip.so."""
 
     def __init__(self, channels: int, heads: int, activation: str = "silu", precision: str = "3xbf16",
                  norm_eps: float = 1e-5):
@@ -240,7 +268,7 @@ class GraphTransformer(nn.Module):
             raise ValueError("x_src / x_dst / e do not match the graph and the channel count")
         grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                                for t in (x_src, x_dst, e, ee, *self.parameters()))
-        n1, n2 = self.norm1, self.norm2
+        n1 = self.norm1
         if ee is None:
             ee = self._lin(e, self.lin_e, grad)
         if grad:
@@ -254,14 +282,27 @@ class GraphTransformer(nn.Module):
         att = edge_attention_kv(q, kv, graph, self.heads, ee)
         o = self._lin(att, self.lin_o, grad)
         if grad:
-            x1 = x_dst + o
-            h = self._lin(ops.layer_norm(x1, n2.weight, n2.bias, n2.eps), self.mlp[0], True)
-            if self.activation != "none":
-                h = _ActFunction.apply(h, self.activation)
-            x_new = x1 + self._lin(h, self.mlp[2], True)
+            x_new = _FeedForwardFunction.apply(self, x_dst + o, *self._feed_forward_parameters())
         else:
-            x1 = _ew(_lib.EW_ADD, o, x_dst.contiguous())
-            h2 = ops.layer_norm_rows(x1, n2.weight, n2.bias, n2.eps)[0]
-            x_new, _ = mlp2(h2, self.mlp[0].weight, self.mlp[2].weight, self.mlp[2].bias, b1=self.mlp[0].bias, res=x1,
-                            act=self.activation, contract=self.precision)
+            x_new = self._feed_forward_fused(_ew(_lib.EW_ADD, o, x_dst.contiguous()))
         return x_new, (e if update_edges else None)
+
+    def _feed_forward_parameters(self):
+        return (self.norm2.weight, self.norm2.bias, self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight,
+                self.mlp[2].bias)
+
+    def _feed_forward_fused(self, x1: Tensor) -> Tensor:
+        """x1 + mlp.2(act(mlp.0(norm2(x1)))) without autograd: the LayerNorm kernel and ONE K6 launch."""
+        n2 = self.norm2
+        x1 = x1.contiguous()
+        h2 = ops.layer_norm_rows(x1, n2.weight, n2.bias, n2.eps)[0]
+        return mlp2(h2, self.mlp[0].weight, self.mlp[2].weight, self.mlp[2].bias, b1=self.mlp[0].bias, res=x1,
+                    act=self.activation, contract=self.precision)[0]
+
+    def _feed_forward_pieces(self, x1: Tensor) -> Tensor:
+        """The same half under autograd, every piece through its own Function (the backward of ``_FeedForwardFunction``)."""
+        n2 = self.norm2
+        h = self._lin(ops.layer_norm(x1, n2.weight, n2.bias, n2.eps), self.mlp[0], True)
+        if self.activation != "none":
+            h = _ActFunction.apply(h, self.activation)
+        return x1 + self._lin(h, self.mlp[2], True)

@@ -19,7 +19,8 @@ the CPU in oracle/interaction_oracle.py):
 The grid is the set of triangle centres of the geodesic mesh; every cell is linked with its three
 corner vertices (gwen_amd/g2m.py) -- or, with ``prepare(..., grid_pos=)``, any point set on the sphere, linked to the
 mesh by radius (grid -> mesh) and by containing face (mesh -> grid) (gwen_amd/gridgraph.py).  Static embeddings (vm, e_*) depend on the weights only and are
-computed once per ``forward`` / ``rollout`` call.  Trainable (``interaction._InteractionNetFunction``).  A leading members axis
+computed once per ``forward`` / ``rollout`` call.  Trainable (``interaction._InteractionNetFunction``), over several lead
+times with ``rollout(grad=True)`` (gwen_amd/checkpoint.py: one step's activations at a time).  A leading members axis
 ``[members, N_grid, C]`` runs as ONE launch set over the block-diagonal graph (``ForecastGraphs.batched``).
 """
 from __future__ import annotations
@@ -36,6 +37,7 @@ from . import noise as noise_mod
 from . import ops
 from .g2m import grid_mesh_edges
 from .attention import GraphTransformer
+from .checkpoint import checkpointed_step
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
 from .mesh import Mesh
 
@@ -300,19 +302,43 @@ class InteractionForecaster(nn.Module):
     def rollout(self, grid_x: Tensor, graphs: ForecastGraphs, n_steps: int,
                 graphed: bool = False, noise: Optional["noise_mod.NoiseStream"] = None,
                 member0: int = 0, clock: Optional["forcings_mod.ForcingClock"] = None,
-                forcing: Optional[Tensor] = None) -> List[Tensor]:
+                forcing: Optional[Tensor] = None, grad: bool = False, checkpoint: bool = True) -> List[Tensor]:
         """Autoregressive: state_{t+1} = forward(state_t); returns the n_steps states.
         ``graphed``: capture ONE step (its ~26 launches) into a hipGraph and replay it per step -- the
         launchers allocate and synchronise nothing, so the step is capturable as is; worth it when the
         host cannot keep ahead of the device (64 channels: 1.31 -> 1.14 ms per step; 128: 2.71 -> 2.39).
         ``clock``: the time of step 0's forcings (left ``n_steps`` steps on); ``forcing`` [n_steps, N, Fg]: step t's
-        given fields."""
+        given fields.
+
+        ``grad=True``: the states take part in autograd (train on a loss over several lead times).  ``grid_x`` is then
+        [N, C] or [members, N, C] (one launch set over the block-diagonal graph, as ``forward``), the static embeddings are
+        computed once per call, under autograd, and the stream and the clock end ``n_steps`` further on; the backward does
+        not move them.  ``checkpoint`` (default): every step keeps its input state only and its backward runs the step's
+        forward again (``checkpoint.checkpointed_step``) -- one step's activations alive at a time, for one more forward
+        per step.  ``checkpoint=False``: the plain chain of steps, every step's saved tensors alive until the backward
+        (for comparison and small models).  Not with ``graphed``: a captured step holds the static embeddings of the
+        weights at capture time and no autograd graph."""
         _check_forcing_steps(forcing, n_steps)
         states, cur = [], grid_x
         kw = {} if noise is None else {"noise": noise, "member0": member0}
         if clock is not None:
             kw["clock"] = clock
         per_step = (lambda t: {}) if forcing is None else (lambda t: {"forcing": forcing[t]})      # noqa: E731
+        if grad:
+            if graphed:
+                raise ValueError("rollout: grad=True cannot replay a captured step (graphed=True): it holds the static "
+                                 "embeddings of the weights at capture time")
+            if grid_x.dim() == 3:
+                graphs = graphs.batched(grid_x.size(0))
+                cur = grid_x.reshape(-1, grid_x.size(-1))
+            static = self._static(graphs)
+            for t in range(n_steps):
+                if checkpoint:
+                    cur = checkpointed_step(self, cur, graphs, static, **kw, **per_step(t))
+                else:
+                    cur = self._step(cur, graphs, static, **kw, **per_step(t))
+                states.append(cur.view_as(grid_x) if grid_x.dim() == 3 else cur)
+            return states
         with torch.no_grad():
             if graphed:
                 step = GraphedStep(self, graphs, grid_x, **kw, **per_step(0))
