@@ -67,15 +67,17 @@ struct Frag {
 };
 
 // FIN: gathered width.  F1: width after the first contraction.  F2: width after the second (0: none).
-template <int FIN, int F1, int F2, bool PRE, int NS>
+// BRQ: rows per block asked for below 128 channels (64; 96 / 112 where they are whole gather passes: chain_rows_ok)
+template <int FIN, int F1, int F2, bool PRE, int NS, int BRQ = 64>
 struct Cfg {
   static constexpr int G = FIN / 4, R = 64 / G;
   static constexpr int NJ1 = F1 / 16, NJ2 = F2 / 16;
   static constexpr int NWB = NJ1 > 4 ? 8 : 4;
   static constexpr int RB = NWB * R;
-  static constexpr int BRMIN = FIN >= 128 ? 128 : 64;
+  static constexpr int BRMIN = FIN >= 128 ? 128 : BRQ;
   static constexpr int BR = RB > BRMIN ? RB : BRMIN;
   static constexpr int NP = BR / RB, NT = BR / kTile;
+  static_assert(BR % RB == 0 && BR % kTile == 0, "a block is whole gather passes and whole row tiles");
   static constexpr int PB0 = pitch_bf16(FIN), PB1 = pitch_bf16(F1);
   static constexpr int FW = F2 > 0 ? F2 : F1;              // stored width
   // bf16x6 (three images): the first product's images take the place of the aggregated rows' (one more barrier,
@@ -88,15 +90,16 @@ struct Cfg {
   static_assert(NWB % NJ1 == 0 && (F2 == 0 || NWB % NJ2 == 0), "waves must tile the columns");
 };
 
-// GE: gathered entries per group (gather_rows.h; 7 only on the uniform layout).  It sits before NS because profile
-// tooling keys this kernel's name on its first and its last template argument.
-template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int NS>
+// GE: gathered entries per group (gather_rows.h; 7 only on the uniform layout).  D: gather depth (gather_rows.h).
+// BRQ: Cfg's.  They sit before NS because profile tooling keys this kernel's name on its first and its last
+// template argument.
+template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int NS>
 __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W1,
     const float *__restrict__ W2, const float *__restrict__ bias, float *__restrict__ out, int32_t N,
     int64_t mstride_x, int64_t mstride_o, int relu) {
-  using C = Cfg<FIN, F1, F2, PRE, NS>;
+  using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
   __shared__ __attribute__((aligned(16))) __bf16 lds[C::lds_elems];
   constexpr int kImg0 = C::BR * C::PB0, kImg1 = C::BR * C::PB1;
   __bf16 *t0 = lds;                                                      // aggregated rows: NS x [BR][PB0]
@@ -126,7 +129,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
   else               { if (bias) bpost = *reinterpret_cast<const float4_t *>(bias + j1 * 16 + 4 * mh); }
 
   // ---- phase 1: gather + aggregate (+ bias, ReLU when activation-first) -> LDS hi/lo -------------
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE>(
+  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(
       rowptr, col, val, xb, N, b0, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if constexpr (PRE) {
           acc = acc + bpre;
@@ -144,11 +147,13 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
   __syncthreads();
 
   // ---- phase 2: first contraction; result to global (F2 == 0) or to the second LDS image ----------
-  constexpr int NIT = C::NT / (C::NWB / C::NJ1);                          // row tiles of this wave
+  constexpr int TS1 = C::NWB / C::NJ1;                                   // row tiles are strided over the waves
+  constexpr int NIT = (C::NT + TS1 - 1) / TS1;                           // row tiles of this wave (at most)
   float4_t keep[C::ALIAS ? NIT : 1];
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int tt = wave / C::NJ1 + it * (C::NWB / C::NJ1);
+    const int tt = wave / C::NJ1 + it * TS1;
+    if (C::NT % TS1 != 0 && tt >= C::NT) continue;                       // 96 / 112 rows: the last stride is partial
     f32x4 d = {0.f, 0.f, 0.f, 0.f};
     d = b1.mma(t0, kImg0, (tt * kTile + mi) * C::PB0, mh, d);
     const int lr = tt * kTile + mi;
@@ -178,7 +183,8 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     __syncthreads();                                   // every wave is done reading the aggregated rows
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
-      const int lr = (wave / C::NJ1 + it * (C::NWB / C::NJ1)) * kTile + mi;
+      if (C::NT % TS1 != 0 && wave / C::NJ1 + it * TS1 >= C::NT) continue;
+      const int lr = (wave / C::NJ1 + it * TS1) * kTile + mi;
       const float o4[4] = {keep[it][0], keep[it][1], keep[it][2], keep[it][3]};
       bf16x4 im[NS];
       gwen::split_images<4, NS>(o4, im);
@@ -204,7 +210,8 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
 
 // Activation-first layer with nothing chained: out = act(A~ h + bias) on the grouped layout (the
 // fma form of K2; K2 itself keeps the rounded-product order that is bit-identical to the CPU path).
-template <int FIN, bool UNI, int GE = 8>
+// D: accepted for symmetry with K4 / K5 -- a wave gathers ONE pass here, so both depths are the same code
+template <int FIN, bool UNI, int GE = 8, int D = 1>
 __global__ __launch_bounds__(256) void k_gather(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ bias,
@@ -218,7 +225,7 @@ __global__ __launch_bounds__(256) void k_gather(
   const char *xb = reinterpret_cast<const char *>(x + (int64_t)blockIdx.y * mstride_x);
   float *om = out + (int64_t)blockIdx.y * mstride_o;
   const uint32_t lane_off = gl * 16;
-  gwen::gather_passes<FIN, 1, BR, UNI, GE>(
+  gwen::gather_passes<FIN, 1, BR, UNI, GE, D>(
       rowptr, col, val, xb, N, lb * BR, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if (bias) acc = acc + *reinterpret_cast<const float4_t *>(bias + gl * 4);
         if (relu) {
@@ -230,64 +237,116 @@ __global__ __launch_bounds__(256) void k_gather(
       });
 }
 
-template <int FIN>
+template <int FIN, int D = 1>
 int launch_gather(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
                   const float *bias, float *out, int64_t N, int64_t members, int64_t msx,
-                  int64_t mso, int relu, int entries, hipStream_t st) {
+                  int64_t mso, int relu, int entries, int block_rows, hipStream_t st) {
   constexpr int BR = 4 * (64 / (FIN / 4));
+  if (block_rows != 0 && block_rows != BR) return GWEN_EINVAL;      // one pass per wave: one block size
   dim3 grid((unsigned)((N + BR - 1) / BR), (unsigned)members);
   if constexpr (FIN <= 64) {
     if (!rowptr && entries == 7) {
-      k_gather<FIN, true, 7><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
+      k_gather<FIN, true, 7, D><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
       GWEN_LAUNCH_CHECK();
       return GWEN_OK;
     }
   }
   if (!rowptr)
-    k_gather<FIN, true><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
+    k_gather<FIN, true, 8, D><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
   else
-    k_gather<FIN, false><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
+    k_gather<FIN, false, 8, D><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
 }
 
+// rows per block that the narrow kernels (Fin, F1 <= 64) can be asked for: whole gather passes (chain_rows_valid
+// is the same rule at run time); at 112 rows the largest of them, 64 -> 64 -> 32 on bf16x3, holds 70 KiB of LDS
 template <int FIN, int F1, int F2, bool PRE, int NS>
-int launch_ns(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+constexpr bool chain_rows_ok(int br) {
+  return FIN <= 64 && F1 <= 64 && (br == 64 || br == 96 || br == 112) && br % Cfg<FIN, F1, F2, PRE, NS>::RB == 0;
+}
+
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ>
+int launch_br(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
               const float *W1, const float *W2, const float *bias, float *out, int64_t N,
               int64_t members, int64_t msx, int64_t mso, int relu, int entries, hipStream_t st) {
-  using C = Cfg<FIN, F1, F2, PRE, NS>;
+  using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
+  static_assert(C::lds_elems * 2 <= 160 * 1024, "one block must fit a CU's LDS");
   const int64_t blocks = (N + C::BR - 1) / C::BR;
   dim3 grid((unsigned)blocks, (unsigned)members);
   if constexpr (FIN <= 64 && F1 <= 64) {           // 7 gathered entries: the narrow kernels only
     if (!rowptr && entries == 7) {
-      k_chain<FIN, F1, F2, PRE, true, 7, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
-                                                                           (int32_t)N, msx, mso, relu);
+      k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
+                                                                                   out, (int32_t)N, msx, mso, relu);
       GWEN_LAUNCH_CHECK();
       return GWEN_OK;
     }
   }
   if (!rowptr)
-    k_chain<FIN, F1, F2, PRE, true, 8, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
-                                                                      (int32_t)N, msx, mso, relu);
+    k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
+                                                                                 (int32_t)N, msx, mso, relu);
   else
-    k_chain<FIN, F1, F2, PRE, false, 8, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
-                                                                       out, (int32_t)N, msx, mso, relu);
+    k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
+                                                                                  out, (int32_t)N, msx, mso, relu);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
+}
+
+// block_rows: 0 = the library's choice; 96 / 112 where chain_rows_ok says.
+// The library's choice is 64 rows (128 from 128 channels on).  K4's "smallest size whose grid is co-resident" finds no
+// such size for the c2 mesh here (64 -> 64 -> 32: 4, 3 and 2 blocks per CU at 64 / 96 / 112 rows against 1 563 / 1 042 /
+// 893 blocks) and 96 / 112 rows measured SLOWER at depth 1 (23.3 / 23.5 against 22.2 us), so depth 1 keeps 64.  At depth
+// 2 one member whose 64-row grid is more than one resident round runs 112-row blocks where the width allows it: the
+// two-deep gather fills and drains once per block (20.1 against 20.8 us).
+template <int FIN, int F1, int F2, bool PRE, int NS, int D>
+int launch_ns(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+              const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+              int64_t members, int64_t msx, int64_t mso, int relu, int entries, int block_rows, hipStream_t st) {
+#define GWEN_BR(BRV)                                                                                \
+  launch_br<FIN, F1, F2, PRE, NS, D, BRV>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, st)
+  if constexpr (D == 2 && chain_rows_ok<FIN, F1, F2, PRE, NS>(112)) {
+    if (block_rows == 0 && members == 1) {
+      static int per_cu[3] = {0, 0, 0};                // of the 64-row kernel this call would launch otherwise
+      const int v = rowptr ? 2 : (entries == 7 ? 0 : 1);
+      if (per_cu[v] == 0) {
+        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, NS>)
+                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, NS>)
+                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, NS>);
+        int nbk = 0;
+        GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k, Cfg<FIN, F1, F2, PRE, NS>::NWB * 64, 0));
+        per_cu[v] = nbk < 1 ? 1 : nbk;
+      }
+      if ((N + 63) / 64 > (int64_t)256 * per_cu[v]) return GWEN_BR(112);
+    }
+  }
+  if (block_rows == 0 || block_rows == Cfg<FIN, F1, F2, PRE, NS>::BR) return GWEN_BR(64);
+  if constexpr (chain_rows_ok<FIN, F1, F2, PRE, NS>(96)) { if (block_rows == 96) return GWEN_BR(96); }
+  if constexpr (chain_rows_ok<FIN, F1, F2, PRE, NS>(112)) { if (block_rows == 112) return GWEN_BR(112); }
+#undef GWEN_BR
+  return GWEN_EINVAL;
 }
 
 template <int FIN, int F1, int F2, bool PRE>
 int launch(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
            const float *W1, const float *W2, const float *bias, float *out, int64_t N,
-           int64_t members, int64_t msx, int64_t mso, int relu, int contract, int entries, hipStream_t st) {
+           int64_t members, int64_t msx, int64_t mso, int relu, int contract, int entries, int depth, int block_rows,
+           hipStream_t st) {
+#define GWEN_NS(NSV, DV)                                                                            \
+  launch_ns<FIN, F1, F2, PRE, NSV, DV>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, \
+                                       block_rows, st)
+  constexpr bool narrow = FIN <= 64 && F1 <= 64;   // gather depth 2: the narrow kernels only
   if (contract == GWEN_CONTRACT_BF16X6) {
     // width triples whose three images do not fit a CU's LDS are refused by gwen_gcn_chain_supported already
-    if constexpr (Cfg<FIN, F1, F2, PRE, 3>::lds_elems * 2 <= 160 * 1024)
-      return launch_ns<FIN, F1, F2, PRE, 3>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, st);
-    else
+    if constexpr (Cfg<FIN, F1, F2, PRE, 3>::lds_elems * 2 <= 160 * 1024) {
+      if constexpr (narrow) { if (depth == 2) return GWEN_NS(3, 2); }
+      return GWEN_NS(3, 1);
+    } else {
       return GWEN_EINVAL;
+    }
   }
-  return launch_ns<FIN, F1, F2, PRE, 2>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, st);
+  if constexpr (narrow) { if (depth == 2) return GWEN_NS(2, 2); }
+  return GWEN_NS(2, 1);
+#undef GWEN_NS
 }
 
 constexpr bool width_ok(int64_t f) { return f == 16 || f == 32 || f == 64 || f == 128; }
@@ -313,15 +372,41 @@ extern "C" int gwen_gcn_chain_supported(int64_t Fin, int64_t F1, int64_t F2, int
   return chain_lds_bytes(Fin, F1, F2, ns) <= 80 * 1024 ? 1 : 0;
 }
 
+// The library's gather depth per (Fin, F1, F2, images) on the uniform layout: 2 only where the kernel measured faster
+// on the MI355X (profiles/depth_*); the non-uniform layout and widths above 64 run depth 1.
+static constexpr int chain_depth(int64_t fin, int64_t f1, int64_t f2, int ns) {
+  return fin == 64 && f1 == 64 && f2 == 32 && ns == 3 ? 2 : 1;     // 64 -> 64 -> 32, bf16x6: 23.1 -> 20.3 us on the c2 mesh
+}
+
+// block_rows of gwen_gcn_chain_tuned_f32: 0, the kernel's own size, or 96 / 112 on the narrow kernels (chain_rows_ok)
+static bool chain_rows_valid(int64_t Fin, int64_t F1, int pre, int br) {
+  if (br == 0) return true;
+  const int64_t R = 64 / (Fin / 4);
+  if (pre && F1 == 0) return br == 4 * R;
+  const int64_t rb = (F1 / 16 > 4 ? 8 : 4) * R, brmin = Fin >= 128 ? 128 : 64;
+  if (br == (rb > brmin ? rb : brmin)) return true;
+  return Fin <= 64 && F1 <= 64 && (br == 96 || br == 112) && br % rb == 0;
+}
+
+extern "C" int gwen_gcn_chain_depth(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract) {
+  if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return 0;
+  if (Fin > 64 || F1 > 64) return 1;
+  return chain_depth(Fin, F1, F2, gwen::images_of(contract));
+}
+
 // entries = 7: the caller's promise (uniform layout, every row at most 7 stored entries), see gwen_gcn_layer_entries_f32
-extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                          const float *x, const float *W1, const float *W2,
-                                          const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
-                                          int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
-                                          int64_t mstride_o, int contract, int entries, gwen_stream_t stream_) {
+// depth, block_rows: 0 = the library's choice (chain_depth; launch_ns); neither changes a value
+extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                        const float *x, const float *W1, const float *W2,
+                                        const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                        int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                        int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                        gwen_stream_t stream_) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
+  if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0) return GWEN_EINVAL;
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return GWEN_EINVAL;
+  if (!chain_rows_valid(Fin, F1, pre, block_rows)) return GWEN_EINVAL;
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || (F1 > 0 && !W1) || !out || x == out || (F2 > 0 && !W2))
     return GWEN_EINVAL;                                    // rowptr NULL = uniform layout
@@ -331,21 +416,24 @@ extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *
     return GWEN_EINVAL;
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   hipStream_t st = gwen_stream(stream_);
+  if (depth == 0) depth = rowptr ? 1 : gwen_gcn_chain_depth(Fin, F1, F2, pre, contract);
   if (pre && F1 == 0) {
-#define GWEN_G(FI)                                                                                  \
+#define GWEN_G(FI, DV)                                                                              \
   if (Fin == FI)                                                                                    \
-    return launch_gather<FI>(rowptr, col, val, x, bias, out, N, members, mstride_x, mstride_o, relu, entries, st)
-    GWEN_G(16); GWEN_G(32); GWEN_G(64); GWEN_G(128);
+    return launch_gather<FI, DV>(rowptr, col, val, x, bias, out, N, members, mstride_x, mstride_o, relu, entries, \
+                                 block_rows, st)
+    if (depth == 2) { GWEN_G(16, 2); GWEN_G(32, 2); GWEN_G(64, 2); }
+    GWEN_G(16, 1); GWEN_G(32, 1); GWEN_G(64, 1); GWEN_G(128, 1);
 #undef GWEN_G
   }
 #define GWEN_P(FI, FA)                                                                              \
   if (pre && Fin == FI && F1 == FA)                                                                 \
     return launch<FI, FA, 0, true>(rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x,   \
-                                   mstride_o, relu, contract, entries, st)
+                                   mstride_o, relu, contract, entries, depth, block_rows, st)
 #define GWEN_C(FI, FA, FB)                                                                          \
   if (!pre && Fin == FI && F1 == FA && F2 == FB)                                                    \
     return launch<FI, FA, FB, false>(rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, \
-                                     mstride_o, relu, contract, entries, st)
+                                     mstride_o, relu, contract, entries, depth, block_rows, st)
 #define GWEN_ROW(FI)                                                                                \
   GWEN_P(FI, 16); GWEN_P(FI, 32); GWEN_P(FI, 64); GWEN_P(FI, 128);                                  \
   GWEN_C(FI, 32, 16); GWEN_C(FI, 64, 16); GWEN_C(FI, 64, 32);                                       \
@@ -355,6 +443,15 @@ extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *
 #undef GWEN_C
 #undef GWEN_P
   return GWEN_EINVAL;
+}
+
+extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                          const float *x, const float *W1, const float *W2,
+                                          const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                          int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                          int64_t mstride_o, int contract, int entries, gwen_stream_t stream_) {
+  return gwen_gcn_chain_tuned_f32(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members,
+                                  mstride_x, mstride_o, contract, entries, 0, 0, stream_);
 }
 
 extern "C" int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, const float *val,

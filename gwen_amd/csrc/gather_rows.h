@@ -15,6 +15,16 @@
 // Results: the skipped term is fma(0, v, acc), so for finite inputs every value is the same; only the
 // sign of an exact zero can differ (-0 + 0 = +0), and an Inf / NaN in the row of a destination's FIRST
 // entry (the pad slot's column) no longer turns the sum into NaN through 0 * Inf.
+// D: gather depth, the passes of row loads a wave keeps in flight (1 or 2).  D = 1 is the loop above: a wave has
+// at most GE loads outstanding and runs a pass's FMAs / split / LDS writes with nothing behind them.  D = 2 issues
+// the row loads of pass p+1 BEFORE pass p's FMAs, into a second register buffer (two buffers, alternated by hand in
+// a loop over PAIRS of passes that stays rolled; the last two or three passes are peeled), and requests the column indices
+// two passes ahead -- before the row loads of the pass in between, because vmcnt retires in issue order: indices
+// requested after those row loads could only be waited for together with them.  Issue order per pass q:
+//   indices(q+2)  <  rows + weights(q+1)  <  FMAs, sink(q)
+// so the wait for rows(q) leaves indices(q+2) and rows(q+1) outstanding.  Arithmetic is D = 1's, term for term:
+// every value is bitwise the same.  On the non-uniform layout `locate` itself loads (row pointers, then indices),
+// and its wait drains the older row loads: D = 2 is correct there but only overlaps the vector work.
 #pragma once
 #include "common.h"
 
@@ -45,8 +55,44 @@ __device__ inline float4_t gather_group(const char *xb, uint32_t lane_off, const
   return acc;
 }
 
+// gather_group in two halves (D = 2): the row loads of one group, and -- later -- its FMAs in the same slot order
+template <int FIN, int GE>
+__device__ __forceinline__ void issue_group(const char *xb, uint32_t lane_off, const int4_u &c0, const int4_u &c1,
+                                            float4_t (&v)[GE]) {
+  constexpr uint32_t kRowBytes = FIN * 4;
+  static_assert(GE == 7 || GE == 8, "a group is gathered whole or without its last slot");
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    v[u] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)((uint32_t)c0[u] * kRowBytes + lane_off));
+    if (u + 4 < GE)
+      v[u + 4] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)((uint32_t)c1[u] * kRowBytes + lane_off));
+  }
+}
+
+template <int GE>
+__device__ __forceinline__ float4_t fma_group(const float4_t (&v)[GE], const float4_u &w0, const float4_u &w1,
+                                              float4_t acc) {
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+    acc = __builtin_elementwise_fma(float4_t{w0[u], w0[u], w0[u], w0[u]}, v[u], acc);
+#pragma unroll
+  for (int u = 0; u < GE - 4; ++u)
+    acc = __builtin_elementwise_fma(float4_t{w1[u], w1[u], w1[u], w1[u]}, v[u + 4], acc);
+  return acc;
+}
+
+// one register buffer of the depth-2 gather: a pass's indices (c, s, rb: requested), then its rows and weights
+// (v, w; is, irb: the group offset and row end of the pass whose rows are in v)
+template <int GE>
+struct GatherBuf {
+  int4_u c0, c1;
+  int32_t s, rb, is, irb;
+  float4_u w0, w1;
+  float4_t v[GE];
+};
+
 // sink(lr, acc): lr = row index inside the block (p * RB + wave * R + gr), acc = aggregated 4 floats
-template <int FIN, int NP, int RB, bool UNI, int GE = 8, typename Sink>
+template <int FIN, int NP, int RB, bool UNI, int GE = 8, int D = 1, typename Sink>
 __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
                                      const int32_t *__restrict__ col,
                                      const float *__restrict__ val, const char *xb, int32_t N,
@@ -66,6 +112,66 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
       s = rb > ra ? ra : rowptr[N];
     }
   };
+  static_assert(D == 1 || D == 2, "one or two passes of row loads in flight");
+  if constexpr (D == 2 && NP > 1) {
+    using Buf = GatherBuf<GE>;
+    auto request = [&](int p, Buf &b) {                    // indices of pass p
+      locate(p, b.s, b.rb);
+      b.c0 = *reinterpret_cast<const int4_u *>(col + b.s);
+      b.c1 = *reinterpret_cast<const int4_u *>(col + b.s + 4);
+      __builtin_amdgcn_sched_barrier(0);                   // the issue order above is the point: pin it
+    };
+    auto issue = [&](Buf &b) {                             // rows and weights of the pass whose indices b holds
+      b.is = b.s; b.irb = b.rb;
+      b.w0 = *reinterpret_cast<const float4_u *>(val + b.s);
+      b.w1 = *reinterpret_cast<const float4_u *>(val + b.s + 4);
+      issue_group<FIN, GE>(xb, lane_off, b.c0, b.c1, b.v);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    auto consume = [&](int p, const Buf &b) {
+      float4_t acc = fma_group<GE>(b.v, b.w0, b.w1, float4_t{0.f, 0.f, 0.f, 0.f});
+      if constexpr (!UNI) {
+        for (int32_t q = b.is + 8; q < b.irb; q += 8) {    // rows longer than one group: finished here, in order
+          const int4_u d0 = *reinterpret_cast<const int4_u *>(col + q);
+          const int4_u d1 = *reinterpret_cast<const int4_u *>(col + q + 4);
+          const float4_u x0 = *reinterpret_cast<const float4_u *>(val + q);
+          const float4_u x1 = *reinterpret_cast<const float4_u *>(val + q + 4);
+          acc = gather_group<FIN>(xb, lane_off, d0, d1, x0, x1, acc);
+        }
+      }
+      sink(p * RB + wave * R + gr, acc);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    Buf A, B;
+    request(0, A);
+    request(1, B);
+    issue(A);
+    // One step in the steady state: X holds the rows of pass q (in flight), Y the indices of pass q+1.
+    auto step = [&](int q, Buf &X, Buf &Y) {
+      request(q + 2, X);
+      issue(Y);
+      consume(q, X);
+    };
+    // Rolled over PAIRS of steps, the two buffers written out by hand: hipcc can not hoist a third pass.  Every
+    // step of the loop issues the same loads, and the last two passes are peeled, so that each wait has ONE count of
+    // loads behind it -- a consume shared by a path that issued the next pass and one that did not waits vmcnt(0).
+#pragma unroll 1
+    for (int p = 0; p + 3 < NP; p += 2) {
+      step(p, A, B);
+      step(p + 1, B, A);
+    }
+    if constexpr (NP % 2 == 1) {
+      step(NP - 3, A, B);
+      issue(A);
+      consume(NP - 2, B);
+      consume(NP - 1, A);
+    } else {
+      issue(B);
+      consume(NP - 2, A);
+      consume(NP - 1, B);
+    }
+    return;
+  }
   int32_t s, rb;
   locate(0, s, rb);
   int4_u c0 = *reinterpret_cast<const int4_u *>(col + s);

@@ -69,7 +69,8 @@ struct Cfg {
 // operand of grad_W) and the result is masked by mask > 0 (the ReLU of the layer below), so the launch
 // returns the gradient the next backward launch starts from.
 // GE: gathered entries per group (gather_rows.h); 7 only on the uniform layout.
-template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8>
+// D: gather depth (gather_rows.h): passes of row loads a wave keeps in flight; the backward runs D = 1.
+template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1>
 __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void k_layer(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W,
@@ -132,7 +133,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   for (int chunk = lb; chunk < nchunks; chunk += nb) {
   const int b0 = chunk * C::BR;
   // ---- phase 1: gather + aggregate into the LDS tile (gather_rows.h) ------------------------------
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE>(
+  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(
       rowptr, col, val, xb, N, b0, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if constexpr (BWD) {
           if (agg_out && b0 + lr < N)
@@ -226,7 +227,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   }
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN, int GE = 8>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE = 8, int D = 1>
 int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
                 const float *W, const float *bias, float *out, int64_t N, int64_t ldo, int64_t members,
                 int64_t msx, int64_t mso, int relu, hipStream_t st, bool probe, int64_t *resident_out,
@@ -237,7 +238,7 @@ int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, con
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE>), C::NWB * 64, 0));
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D>), C::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
   const int64_t resident = (int64_t)256 * per_cu;
@@ -263,30 +264,43 @@ int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, con
     }
   }
   if (!rowptr)      // uniform layout: row r is the group at 8 r
-    k_layer<FIN, FOUT, NS, BRMIN, true, false, GE><<<grid, C::NWB * 64, 0, st>>>(
+    k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D><<<grid, C::NWB * 64, 0, st>>>(
         rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu);
   else
-    k_layer<FIN, FOUT, NS, BRMIN, false><<<grid, C::NWB * 64, 0, st>>>(
+    k_layer<FIN, FOUT, NS, BRMIN, false, false, 8, D><<<grid, C::NWB * 64, 0, st>>>(
         rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
 }
 
-template <int FIN, int FOUT, int NS, int GE = 8>
+// block_rows: 0 = the choice below; 64 / 96 / 112 / 128 (narrow layers, whole gather passes only) forces it
+template <int FIN, int FOUT, int NS, int GE = 8, int D = 1>
 int launch(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
            const float *W, const float *bias, float *out, int64_t N, int64_t ldo, int64_t members,
            int64_t msx, int64_t mso, int relu, hipStream_t st, float *agg_out = nullptr,
-           const float *mask = nullptr, bool bwd = false, float *bsum_out = nullptr, int64_t *chunks_out = nullptr) {
+           const float *mask = nullptr, bool bwd = false, float *bsum_out = nullptr, int64_t *chunks_out = nullptr,
+           int block_rows = 0) {
 #define GWEN_ROWS(BRV, PROBE, RES)                                                                  \
-  launch_rows<FIN, FOUT, NS, BRV, GE>(rowptr, col, val, x, W, bias, out, N, ldo, members, msx, mso,  \
-                                      relu, st, PROBE, RES, agg_out, mask, bwd, bsum_out, chunks_out)
+  launch_rows<FIN, FOUT, NS, BRV, GE, D>(rowptr, col, val, x, W, bias, out, N, ldo, members, msx, mso, \
+                                         relu, st, PROBE, RES, agg_out, mask, bwd, bsum_out, chunks_out)
   static_assert(GE == 8 || (FIN <= 64 && FOUT <= 64), "7 gathered entries: narrow layers only");
+  static_assert(D == 1 || (FIN <= 64 && FOUT <= 64), "gather depth 2: narrow layers only");
   if constexpr (FIN <= 64 && FOUT <= 64) {
+    if (block_rows != 0) {
+      constexpr int RBF = Cfg<FIN, FOUT, NS, 64>::RB;
+      if (block_rows == 64) return GWEN_ROWS(64, false, nullptr);
+      if constexpr (96 % RBF == 0) { if (block_rows == 96) return GWEN_ROWS(96, false, nullptr); }
+      if constexpr (112 % RBF == 0) { if (block_rows == 112) return GWEN_ROWS(112, false, nullptr); }
+      if constexpr (128 % RBF == 0) { if (block_rows == 128) return GWEN_ROWS(128, false, nullptr); }
+      return GWEN_EINVAL;
+    }
     // Narrow layers run as ONE round of co-resident blocks when a block size makes that possible: with
     // 64-row blocks the c2 mesh needs 1 563 blocks against 1 024 resident ones (4 per CU at 64 -> 64),
     // i.e. a full round plus a half-empty one of ~10 us each; 112-row blocks (893 of them) fit one round.
     // Rows per block: the smallest of 64 / 96 / 112 / 128 (whole gather passes only) whose grid is
-    // co-resident, else 64.
+    // co-resident, else 64 -- at gather depth 2 else 112 where the width allows it: several rounds of blocks either
+    // way, and the two-deep gather fills and drains once per block, so the longest run of passes is the cheapest
+    // (64 -> 64 on the c2 mesh, bf16x6: 18.2 us against 18.9 at 64 rows; depth 1 the other way round, 19.8 / 19.2).
     int64_t res = 0;
     const int64_t work = N * members;
     { const int rc_ = GWEN_ROWS(64, true, &res); if (rc_ != GWEN_OK) return rc_; }
@@ -304,11 +318,13 @@ int launch(const int32_t *rowptr, const int32_t *col, const float *val, const fl
       { const int rc_ = GWEN_ROWS(128, true, &res); if (rc_ != GWEN_OK) return rc_; }
       if ((N + 127) / 128 <= res) return GWEN_ROWS(128, false, nullptr);
     }
+    if constexpr (D == 2 && 112 % RB == 0) return GWEN_ROWS(112, false, nullptr);
     return GWEN_ROWS(64, false, nullptr);
   } else {
     // rows per block: enough that W (read once per block) stays a small fraction of the gathered bytes
     // 256: 64 rows keep two blocks per CU in LDS (bf16x3), and 64 rows at 256 channels on bf16x6 as well
     constexpr int BRMIN = FIN == 128 ? 128 : 64;
+    if (block_rows != 0 && block_rows != Cfg<FIN, FOUT, NS, BRMIN>::BR) return GWEN_EINVAL;
     return GWEN_ROWS(BRMIN, false, nullptr);
   }
 #undef GWEN_ROWS
@@ -322,16 +338,40 @@ extern "C" int gwen_gcn_layer_supported(int64_t Fin, int64_t Fout) {
   return width_ok(Fin) && width_ok(Fout) ? 1 : 0;
 }
 
+// The library's gather depth per (Fin, Fout, images) on the uniform layout: 2 only where the kernel measured
+// faster on the MI355X (profiles/depth_*); the non-uniform layout and widths above 64 run depth 1.
+static constexpr int layer_depth(int64_t fin, int64_t fout, int ns) {
+  return fin == 64 && fout == 64 && ns == 3 ? 2 : 1;     // 64 -> 64, bf16x6: 19.3 -> 18.3 us on the c2 mesh
+}
+
+// block_rows of gwen_gcn_layer_tuned_f32: 0; narrow layers: 64 / 96 / 112 / 128 that are whole gather passes; wide
+// layers: the kernel's one size (launch())
+static bool layer_rows_valid(int64_t Fin, int64_t Fout, int br) {
+  if (br == 0) return true;
+  const int64_t nj = Fout / 16, rb = (nj > 8 ? 16 : (nj > 4 ? 8 : 4)) * (64 / (Fin / 4));
+  if (Fin <= 64 && Fout <= 64) return (br == 64 || br == 96 || br == 112 || br == 128) && br % rb == 0;
+  const int64_t brmin = Fin == 128 ? 128 : 64;
+  return br == (rb > brmin ? rb : brmin);
+}
+
+extern "C" int gwen_gcn_layer_depth(int64_t Fin, int64_t Fout, int exact) {
+  if (!gwen_gcn_layer_supported(Fin, Fout) || exact < 0 || exact > 2) return 0;
+  if (Fin > 64 || Fout > 64) return 1;
+  return layer_depth(Fin, Fout, exact == GWEN_CONTRACT_F32 ? 0 : (exact == GWEN_CONTRACT_BF16X6 ? 3 : 2));
+}
+
 // entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
-// kernels turn into one gather less per row; every other shape and layout gathers whole groups
-extern "C" int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                          const float *x, const float *W, const float *bias, float *out,
-                                          int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
-                                          int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
-                                          int exact, int entries, gwen_stream_t stream_) {
+// kernels turn into one gather less per row; every other shape and layout gathers whole groups.
+// depth, block_rows: 0 = the library's choice (layer_depth; the co-resident grid of launch()); neither changes a value
+extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                        const float *x, const float *W, const float *bias, float *out,
+                                        int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                        int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                        int exact, int entries, int depth, int block_rows, gwen_stream_t stream_) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
+  if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
-  if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
+  if (!gwen_gcn_layer_supported(Fin, Fout) || !layer_rows_valid(Fin, Fout, block_rows)) return GWEN_EINVAL;
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || !W || !out || x == out) return GWEN_EINVAL;   // rowptr NULL = uniform
   if (N >= (int64_t(1) << 28) || members > 65535) return GWEN_ERANGE;     // 8 N must fit int32
@@ -340,40 +380,62 @@ extern "C" int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *
     return GWEN_EINVAL;                       // x rows must be contiguous (32-bit row offsets)
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   hipStream_t st = gwen_stream(stream_);
-  if (entries == 7 && !rowptr && Fin <= 64 && Fout <= 64) {
-#define GWEN_L7(FI, FO)                                                                          \
+  const bool narrow = Fin <= 64 && Fout <= 64;
+  if (depth == 0) depth = rowptr ? 1 : gwen_gcn_layer_depth(Fin, Fout, exact);
+  if (!narrow) depth = 1;                     // the wide kernels have one depth
+  // narrow layers: GE (7 on the uniform layout when the caller promises it) x D
+#define GWEN_LN(FI, FO, GEV, DV)                                                                 \
   if (Fin == FI && Fout == FO)                                                                   \
     return exact == GWEN_CONTRACT_F32                                                            \
-               ? launch<FI, FO, 0, 7>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, \
-                                      mstride_o, relu, st)                                       \
+               ? launch<FI, FO, 0, GEV, DV>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, mstride_o, \
+                                            relu, st, nullptr, nullptr, false, nullptr, nullptr, block_rows) \
                : (exact == GWEN_CONTRACT_BF16X6                                                  \
-                      ? launch<FI, FO, 3, 7>(rowptr, col, val, x, W, bias, out, N, ldo, members, \
-                                             mstride_x, mstride_o, relu, st)                     \
-                      : launch<FI, FO, 2, 7>(rowptr, col, val, x, W, bias, out, N, ldo, members, \
-                                             mstride_x, mstride_o, relu, st))
-    GWEN_L7(16, 16); GWEN_L7(16, 32); GWEN_L7(16, 64);
-    GWEN_L7(32, 16); GWEN_L7(32, 32); GWEN_L7(32, 64);
-    GWEN_L7(64, 16); GWEN_L7(64, 32); GWEN_L7(64, 64);
-#undef GWEN_L7
+                      ? launch<FI, FO, 3, GEV, DV>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x,   \
+                                                   mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr,  \
+                                                   block_rows)                                   \
+                      : launch<FI, FO, 2, GEV, DV>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x,   \
+                                                   mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr,  \
+                                                   block_rows))
+#define GWEN_LNN(GEV, DV)                                                                        \
+  GWEN_LN(16, 16, GEV, DV); GWEN_LN(16, 32, GEV, DV); GWEN_LN(16, 64, GEV, DV);                  \
+  GWEN_LN(32, 16, GEV, DV); GWEN_LN(32, 32, GEV, DV); GWEN_LN(32, 64, GEV, DV);                  \
+  GWEN_LN(64, 16, GEV, DV); GWEN_LN(64, 32, GEV, DV); GWEN_LN(64, 64, GEV, DV)
+  if (narrow) {
+    const bool seven = entries == 7 && !rowptr;
+    if (seven && depth == 2) { GWEN_LNN(7, 2); }
+    if (seven) { GWEN_LNN(7, 1); }
+    if (depth == 2) { GWEN_LNN(8, 2); }
+    GWEN_LNN(8, 1);
   }
+#undef GWEN_LNN
+#undef GWEN_LN
 #define GWEN_L(FI, FO)                                                                           \
   if (Fin == FI && Fout == FO)                                                                   \
     return exact == GWEN_CONTRACT_F32                                                            \
                ? launch<FI, FO, 0>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, \
-                                   mstride_o, relu, st)                                          \
+                                   mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr, block_rows) \
                : (exact == GWEN_CONTRACT_BF16X6                                                  \
                       ? launch<FI, FO, 3>(rowptr, col, val, x, W, bias, out, N, ldo, members,    \
-                                          mstride_x, mstride_o, relu, st)                        \
+                                          mstride_x, mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr, \
+                                          block_rows)                                            \
                       : launch<FI, FO, 2>(rowptr, col, val, x, W, bias, out, N, ldo, members,    \
-                                          mstride_x, mstride_o, relu, st))
-  GWEN_L(16, 16); GWEN_L(16, 32); GWEN_L(16, 64); GWEN_L(16, 128);
-  GWEN_L(32, 16); GWEN_L(32, 32); GWEN_L(32, 64); GWEN_L(32, 128);
-  GWEN_L(64, 16); GWEN_L(64, 32); GWEN_L(64, 64); GWEN_L(64, 128);
+                                          mstride_x, mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr, \
+                                          block_rows))
+  GWEN_L(16, 128); GWEN_L(32, 128); GWEN_L(64, 128);
   GWEN_L(128, 16); GWEN_L(128, 32); GWEN_L(128, 64); GWEN_L(128, 128);
   GWEN_L(16, 256); GWEN_L(32, 256); GWEN_L(64, 256); GWEN_L(128, 256);
   GWEN_L(256, 16); GWEN_L(256, 32); GWEN_L(256, 64); GWEN_L(256, 128); GWEN_L(256, 256);
 #undef GWEN_L
   return GWEN_EINVAL;
+}
+
+extern "C" int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                          const float *x, const float *W, const float *bias, float *out,
+                                          int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                          int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                          int exact, int entries, gwen_stream_t stream_) {
+  return gwen_gcn_layer_tuned_f32(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x,
+                                  mstride_o, relu, exact, entries, 0, 0, stream_);
 }
 
 extern "C" int gwen_gcn_layer_f32(const int32_t *rowptr, const int32_t *col, const float *val,

@@ -188,9 +188,12 @@ def layer_supported(fin: int, fout: int) -> bool:
 
 
 def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
-                relu: bool = False, exact: bool = False, contract: Optional[str] = None) -> Tensor:
+                relu: bool = False, exact: bool = False, contract: Optional[str] = None,
+                depth: int = 0, block_rows: int = 0) -> Tensor:
     """K4: act((A~ x) W^T + b) in one launch (widths in {16,32,64,128,256}).  ``contract``: "bf16x6", "3xbf16" or
-    "fp32"; when None, ``exact`` picks between "fp32" (True) and "3xbf16" (False)."""
+    "fp32"; when None, ``exact`` picks between "fp32" (True) and "3xbf16" (False).  ``depth`` (gather passes in
+    flight per wave: 1 or 2) and ``block_rows`` (64 / 96 / 112 / 128 where the widths allow) are scheduling choices
+    that change no value; 0 = the library's (gwen_gcn_layer_tuned_f32)."""
     _require(x, "x")
     _require(weight, "weight")
     x = x.contiguous()
@@ -209,12 +212,15 @@ def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tenso
     dev = x.device
     g_rowptr, g_col, g_val = graph.grouped()
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_layer_entries_f32(
+        rc = _lib.lib().gwen_gcn_layer_tuned_f32(
             _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), _ptr(weight), _ptr(bias),
             _ptr(out), n, fin, fout, fin, fout, m, n_src * fin, n * fout, int(relu),
-            _dense_code(contract, exact), graph.entries(), _stream(dev))
-    _lib.check(rc, "gwen_gcn_layer_entries_f32")
+            _dense_code(contract, exact), graph.entries(), int(depth), int(block_rows), _stream(dev))
+    _lib.check(rc, "gwen_gcn_layer_tuned_f32")
     return out
+
+
+layer = layer_fused
 
 
 def wide_supported(fin: int, fout: int) -> bool:
@@ -298,26 +304,27 @@ def small_layer(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tenso
     return out
 
 
-def chain(graph: GraphCSR, x: Tensor, w1: Tensor, w2: Optional[Tensor], bias: Optional[Tensor],
-          relu: bool, pre: bool, contract: str = "3xbf16") -> Tensor:
-    """K5.  pre=False: act((A~ x) w1^T + bias) w2^T;  pre=True: act(A~ x + bias) w1^T  (inference only).
-    ``contract``: "3xbf16" or "bf16x6"."""
+def chain(graph: GraphCSR, x: Tensor, w1: Optional[Tensor], w2: Optional[Tensor], bias: Optional[Tensor],
+          relu: bool, pre: bool, contract: str = "3xbf16", depth: int = 0, block_rows: int = 0) -> Tensor:
+    """K5.  pre=False: act((A~ x) w1^T + bias) w2^T;  pre=True: act(A~ x + bias) w1^T  (inference only); pre=True
+    with w1 = None: act(A~ x + bias), the propagation on the grouped layout.  ``contract``: "3xbf16" or "bf16x6".
+    ``depth`` / ``block_rows``: as ``layer_fused`` (gwen_gcn_chain_tuned_f32); they change no value."""
     _require(x, "x")
     x = x.contiguous()
     m, n, fin = _rows2d(x)
-    f1 = w1.size(0)
+    f1 = 0 if w1 is None else w1.size(0)
     f2 = 0 if w2 is None else w2.size(0)
-    fw = f2 if f2 else f1
+    fw = f2 or f1 or fin
     out = torch.empty(*x.shape[:-1], fw, dtype=torch.float32, device=x.device)
     g_rowptr, g_col, g_val = graph.grouped()
     dev = x.device
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_chain_entries_f32(
-            _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), _ptr(w1.contiguous()),
+        rc = _lib.lib().gwen_gcn_chain_tuned_f32(
+            _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), None if w1 is None else _ptr(w1.contiguous()),
             None if w2 is None else _ptr(w2.contiguous()), None if bias is None else _ptr(bias.contiguous()),
             _ptr(out), n, fin, f1, f2, int(pre), int(relu), m, n * fin, n * fw, _dense_code(contract),
-            graph.entries(), _stream(dev))
-    _lib.check(rc, "gwen_gcn_chain_entries_f32")
+            graph.entries(), int(depth), int(block_rows), _stream(dev))
+    _lib.check(rc, "gwen_gcn_chain_tuned_f32")
     return out
 
 

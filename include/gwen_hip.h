@@ -215,6 +215,21 @@ int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const 
                                const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
                                int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
                                int64_t mstride_o, int relu, int exact, int entries, gwen_stream_t stream);
+/* The same with two scheduling choices of the narrow kernels (Fin, Fout <= 64) exposed, for tests and A/B timing.
+ * NEITHER CHANGES A VALUE: every output is bitwise that of gwen_gcn_layer_entries_f32, which forwards with 0, 0.
+ * depth: passes of row loads a wave keeps in flight while it gathers -- 1, 2, or 0 = the library's choice
+ *   (gwen_gcn_layer_depth on a uniform layout, 1 with a row pointer).  Widths above 64 always run depth 1.
+ * block_rows: destination rows per block -- 0 = the library's choice (the smallest of 64 / 96 / 112 / 128 whose grid
+ *   is co-resident; if none is, 64 at depth 1 and 112 at depth 2), or one of these that is a whole number of gather passes (16 * 64 / Fin rows for Fout <= 64:
+ *   all four at Fin = 64; 64, 96, 128 at Fin = 32; 64, 128 at Fin = 16); widths above 64: 0 or the kernel's one size.
+ * depth outside {0, 1, 2} or any other block_rows: GWEN_EINVAL. */
+int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                             const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                             int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                             int64_t mstride_o, int relu, int exact, int entries, int depth, int block_rows,
+                             gwen_stream_t stream);
+/* the depth gwen_gcn_layer_f32 runs on a uniform layout: 1 or 2 (0: unsupported widths / exact) */
+int gwen_gcn_layer_depth(int64_t Fin, int64_t Fout, int exact);
 
 /* ---------------------------------------------------------------------------------------------
  * K8  K4's contract for WIDE layers on locality-ordered bounded-degree graphs (meshes), tile-staged:
@@ -286,6 +301,18 @@ int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const 
                                const float *W1, const float *W2, const float *bias, float *out, int64_t N,
                                int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
                                int64_t mstride_x, int64_t mstride_o, int contract, int entries, gwen_stream_t stream);
+/* depth, block_rows: as gwen_gcn_layer_tuned_f32 -- neither changes a value; gwen_gcn_chain_entries_f32 forwards
+ * with 0, 0.  depth 2 acts at Fin, F1 <= 64 (the form without a contraction gathers one pass per wave: both depths
+ * are the same code).  block_rows: 0 = the library's choice (64; 128 from Fin = 128 on), or 64 / 96 / 112 at
+ * Fin, F1 <= 64 where that is a whole number of gather passes (16 * 64 / Fin rows); the form without a contraction:
+ * 0 or its one size, 1024 / Fin.  Otherwise GWEN_EINVAL. */
+int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                             const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+                             int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
+                             int64_t mstride_x, int64_t mstride_o, int contract, int entries, int depth,
+                             int block_rows, gwen_stream_t stream);
+/* the depth gwen_gcn_chain_f32 runs on a uniform layout: 1 or 2 (0: gwen_gcn_chain_supported says no) */
+int gwen_gcn_chain_depth(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-stack forward == GNNModel.forward (/root/reference/src/gwen/models_gnn.py:292-303 ->
