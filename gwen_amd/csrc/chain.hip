@@ -16,7 +16,11 @@
 // instead of 64,64,32,16,32,64 (reference call sites: /root/reference/src/gwen/models_gnn.py:147-149,
 // :204-206; the re-bracketing only changes fp32 rounding order).
 // Structure, layout, contraction (bf16 split with NS images per operand, fp32 accumulate: split.h) and numerics
-// are K4's (layer.hip).
+// are K4's (layer.hip), and so is the prologue: raw W1 / W2 loads and an unconditional bias load first, nothing waits
+// for them, the first index request right behind; the split into images goes to gather_passes' shadow callable
+// (chain_pin says per shape whether it is pinned under the first row loads or left to the optimiser from there on).
+// k_gather loads its bias above the gather as well (from x when there is none; nothing is added then), not in the sink,
+// where it was a dependent round trip at the tail of every wave.
 #include "common.h"
 #include "gather_rows.h"
 #include "split.h"
@@ -37,20 +41,33 @@ struct Frag {
   static constexpr int KS = FI / (4 * KF);
   using T = typename BF<KF>::T;
   T im[KS][NS];
-  __device__ inline void load(const float *W, int j, int mi, int mh) {
+  float4_t raw[KS][KF / 4];                                // load_raw .. split: W as loaded (dead afterwards)
+  // load in two halves: the loads alone (issued at the top of the kernel), and the split into images (in the shadow
+  // of the first row loads, gather_rows.h); together they are load()
+  __device__ __forceinline__ void load_raw(const float *W, int j, int mi, int mh) {
     const float *wrow = W + (int64_t)(j * 16 + mi) * FI;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int i = 0; i < KF; i += 4)
+        raw[ks][i / 4] = *reinterpret_cast<const float4_t *>(wrow + KF * (4 * ks + mh) + i);
+  }
+  __device__ __forceinline__ void split() {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       float wv[KF];
-      const float *wp = wrow + KF * (4 * ks + mh);
 #pragma unroll
-      for (int i = 0; i < KF; i += 4) {
-        const float4_t w4 = *reinterpret_cast<const float4_t *>(wp + i);
+      for (int i = 0; i < KF; i += 4)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) wv[i + e] = w4[e];
-      }
+        for (int e = 0; e < 4; ++e) wv[i + e] = raw[ks][i / 4][e];
       gwen::split_images<KF, NS>(wv, im[ks]);
     }
+  }
+  __device__ __forceinline__ void pin() {                  // after split(): the split stays where it was written
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) gwen::pin_here(im[ks][s]);
   }
   // d += W-fragment (A operand) x tile rows arow.. from the NS LDS images, `img` elements apart (B operand): the
   // product comes out TRANSPOSED -- lane (mi, mh) holds row mi, columns 16 j + 4 mh .. +3
@@ -90,6 +107,16 @@ struct Cfg {
   static_assert(NWB % NJ1 == 0 && (F2 == 0 || NWB % NJ2 == 0), "waves must tile the columns");
 };
 
+// The W slices are split into bf16 images in gather_passes' shadow callable (gather_rows.h).  true: the images are pinned
+// there (split.h, pin_here), under the first row loads; false: the optimiser may sink the split from there to the images'
+// first use, the tail of the gather -- fewer registers.  Per (Fin, F1, F2, images), from the registers (no c2 kernel may
+// lose a wave of occupancy) and the per-kernel measurement on the MI355X (profiles/prologue_*, DESIGN 4 K4 "Prologue"):
+// 64 -> 64 -> 32 on bf16x6 is pinned (160 VGPRs, still 3 waves); pinned, 32 -> 16 holds 81 VGPRs and loses its 6th wave.
+// Only with 7 gathered entries, the measured form: with 8 the pinned images take the kernel from 3 waves to 2.
+constexpr bool chain_pin(int fin, int f1, int f2, int ns, int ge) {
+  return fin == 64 && f1 == 64 && f2 == 32 && ns == 3 && ge == 7;
+}
+
 // GE: gathered entries per group (gather_rows.h; 7 only on the uniform layout).  D: gather depth (gather_rows.h).
 // BRQ: Cfg's.  They sit before NS because profile tooling keys this kernel's name on its first and its last
 // template argument.
@@ -117,20 +144,34 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
   float *om = out + (int64_t)blockIdx.y * mstride_o;
   const uint32_t lane_off = gl * 16;
 
-  // weights of both contractions for this wave's column tiles, issued before the gathers
+  // weights of both contractions for this wave's column tiles: the raw loads are issued here, before the first index
+  // request and with no wait behind them; they are split into images in the shadow of the first row
+  // loads (gather_rows.h; chain_pin says whether pinned there).  Bias: never a load under a condition (gather_rows.h) --
+  // without one the same 16 bytes of W1 are read (F1 * FIN floats: at least FIN, at least F1) and masked to +0.
+  constexpr bool kPin = chain_pin(FIN, F1, F2, NS, GE);
   const int j1 = wave % C::NJ1;
   Frag<FIN, NS> b1;
-  b1.load(W1, j1, mi, mh);
+  b1.load_raw(W1, j1, mi, mh);
   const int j2 = wave % (F2 > 0 ? C::NJ2 : 1);
   Frag<(F2 > 0 ? F1 : 16), NS> b2;
-  if constexpr (F2 > 0) b2.load(W2, j2, mi, mh);
+  if constexpr (F2 > 0) b2.load_raw(W2, j2, mi, mh);
   float4_t bpre = {0.f, 0.f, 0.f, 0.f}, bpost = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (PRE) { if (bias) bpre = *reinterpret_cast<const float4_t *>(bias + gl * 4); }
-  else               { if (bias) bpost = *reinterpret_cast<const float4_t *>(bias + j1 * 16 + 4 * mh); }
+  float4_t braw = *reinterpret_cast<const float4_t *>((bias ? bias : W1) + (PRE ? gl * 4 : j1 * 16 + 4 * mh));
+  // the mask waits for the load, so it is applied in the shadow callable, not here
+  auto split_w = [&]() {
+    (PRE ? bpre : bpost) = gwen::masked_f4(braw, bias != nullptr);
+    gwen::pin_here(PRE ? bpre : bpost);                    // or mask and load sink to the value's first use
+    b1.split();
+    if constexpr (F2 > 0) b2.split();
+    if constexpr (kPin) {
+      b1.pin();
+      if constexpr (F2 > 0) b2.pin();
+    }
+  };
+  __builtin_amdgcn_sched_barrier(0);                       // the raw loads stay in front of the first index request
 
   // ---- phase 1: gather + aggregate (+ bias, ReLU when activation-first) -> LDS hi/lo -------------
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(
-      rowptr, col, val, xb, N, b0, wave, gr, lane_off, [&](int lr, float4_t acc) {
+  auto sink = [&](int lr, float4_t acc) {
         if constexpr (PRE) {
           acc = acc + bpre;
           if (relu) {
@@ -143,7 +184,8 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
         gwen::split_images<4, NS>(a4, im);
 #pragma unroll
         for (int s = 0; s < NS; ++s) *reinterpret_cast<bf16x4 *>(t0 + s * kImg0 + lr * C::PB0 + gl * 4) = im[s];
-      });
+      };
+  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink, split_w);
   __syncthreads();
 
   // ---- phase 2: first contraction; result to global (F2 == 0) or to the second LDS image ----------
@@ -225,9 +267,15 @@ __global__ __launch_bounds__(256) void k_gather(
   const char *xb = reinterpret_cast<const char *>(x + (int64_t)blockIdx.y * mstride_x);
   float *om = out + (int64_t)blockIdx.y * mstride_o;
   const uint32_t lane_off = gl * 16;
+  // bias: loaded above the gather (the oldest load: no later wait is longer for it) and never under a condition
+  // (gather_rows.h) -- without one the first row of x is read (N >= 1: at least FIN floats) and nothing is added:
+  // acc + 0 would turn an aggregated -0 into +0
+  const float4_t braw = *reinterpret_cast<const float4_t *>(bias ? reinterpret_cast<const char *>(bias) + lane_off
+                                                                 : xb + lane_off);
+  __builtin_amdgcn_sched_barrier(0);
   gwen::gather_passes<FIN, 1, BR, UNI, GE, D>(
       rowptr, col, val, xb, N, lb * BR, wave, gr, lane_off, [&](int lr, float4_t acc) {
-        if (bias) acc = acc + *reinterpret_cast<const float4_t *>(bias + gl * 4);
+        if (bias) acc = acc + braw;
         if (relu) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[e] = acc[e] < 0.0f ? 0.0f : acc[e];

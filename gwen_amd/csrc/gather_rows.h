@@ -25,7 +25,17 @@
 // so the wait for rows(q) leaves indices(q+2) and rows(q+1) outstanding.  Arithmetic is D = 1's, term for term:
 // every value is bitwise the same.  On the non-uniform layout `locate` itself loads (row pointers, then indices),
 // and its wait drains the older row loads: D = 2 is correct there but only overlaps the vector work.
+// shadow(): a second callable, run exactly ONCE, after the row loads of the FIRST pass have been issued and before
+// their first wait (D = 1: between the loads and the FMAs of pass 0; D = 2: after request(0), request(1), issue(A)).
+// It is where K4 / K5 split W into bf16 images: the raw W loads are issued at the top of the kernel, before the first
+// index request and with no wait in between; vmcnt retires in issue order, so they have landed when the first indices
+// have, and the split's vector work runs while the first rows are in flight instead of in front of the whole chain.
+// The order is pinned with sched_barrier.  With a shadow the depth-1 loop has its first pass peeled (the callable
+// must not sit under a condition inside the rolled loop); NoShadow keeps the loop exactly as it was -- the persistent
+// wide kernels and the backward compile to the code they had.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace gwen {
@@ -56,7 +66,8 @@ __device__ inline float4_t gather_group(const char *xb, uint32_t lane_off, const
 }
 
 // gather_group in two halves (D = 2): the row loads of one group, and -- later -- its FMAs in the same slot order
-template <int FIN, int GE>
+// KEEP: see the end of the body; asked for where further index loads are in flight behind this group's
+template <int FIN, int GE, bool KEEP>
 __device__ __forceinline__ void issue_group(const char *xb, uint32_t lane_off, const int4_u &c0, const int4_u &c1,
                                             float4_t (&v)[GE]) {
   constexpr uint32_t kRowBytes = FIN * 4;
@@ -67,6 +78,12 @@ __device__ __forceinline__ void issue_group(const char *xb, uint32_t lane_off, c
     if (u + 4 < GE)
       v[u + 4] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)((uint32_t)c1[u] * kRowBytes + lane_off));
   }
+  // GE = 7: c1[3] is never read, and the register allocator hands its register out again while the 16-B index load
+  // that writes it is still in flight -- the overwrite then waits vmcnt(0) for that load, the youngest one, and
+  // with it for every row load in front of it.  A (free) use of the whole vector behind the row addresses keeps
+  // the register taken until the indices have been waited for anyway.  It costs registers (K4 16 -> 32: 57 -> 62, a wave),
+  // so it is only asked for where a younger index request exists: every depth-2 pass, and depth 1 with NP > 1.
+  if constexpr (GE == 7 && KEEP) asm volatile("" ::"v"(c1));
 }
 
 template <int GE>
@@ -91,13 +108,28 @@ struct GatherBuf {
   float4_t v[GE];
 };
 
+// v where keep, else +0 in every lane: the unconditional form of `if (p) v = *p` (load from an address that is always
+// valid, then mask).  Written as a mask because the optimiser sinks a load whose only use is conditional back under
+// the condition -- and a load under a condition is what the rule above forbids.
+__device__ __forceinline__ float4_t masked_f4(float4_t v, bool keep) {
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  const uint32_t m = keep ? 0xffffffffu : 0u;
+  return __builtin_bit_cast(float4_t, __builtin_bit_cast(u4, v) & u4{m, m, m, m});
+}
+
+struct NoShadow {
+  __device__ __forceinline__ void operator()() const {}
+};
+
 // sink(lr, acc): lr = row index inside the block (p * RB + wave * R + gr), acc = aggregated 4 floats
-template <int FIN, int NP, int RB, bool UNI, int GE = 8, int D = 1, typename Sink>
+template <int FIN, int NP, int RB, bool UNI, int GE = 8, int D = 1, typename Sink, typename Shadow = NoShadow>
 __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
                                      const int32_t *__restrict__ col,
                                      const float *__restrict__ val, const char *xb, int32_t N,
-                                     int b0, int wave, int gr, uint32_t lane_off, Sink &&sink) {
+                                     int b0, int wave, int gr, uint32_t lane_off, Sink &&sink,
+                                     Shadow &&shadow = Shadow{}) {
   constexpr int R = 64 / (FIN / 4);
+  constexpr bool kShadow = !std::is_same<std::decay_t<Shadow>, NoShadow>::value;
   static_assert(GE == 8 || UNI, "only the uniform layout bounds a row by one group");
   // group offset and row end of pass p (absent rows: the null group, which ends at once)
   auto locate = [&](int p, int32_t &s, int32_t &rb) {
@@ -125,7 +157,7 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
       b.is = b.s; b.irb = b.rb;
       b.w0 = *reinterpret_cast<const float4_u *>(val + b.s);
       b.w1 = *reinterpret_cast<const float4_u *>(val + b.s + 4);
-      issue_group<FIN, GE>(xb, lane_off, b.c0, b.c1, b.v);
+      issue_group<FIN, GE, true>(xb, lane_off, b.c0, b.c1, b.v);
       __builtin_amdgcn_sched_barrier(0);
     };
     auto consume = [&](int p, const Buf &b) {
@@ -146,6 +178,10 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
     request(0, A);
     request(1, B);
     issue(A);
+    if constexpr (kShadow) {
+      shadow();
+      __builtin_amdgcn_sched_barrier(0);
+    }
     // One step in the steady state: X holds the rows of pass q (in flight), Y the indices of pass q+1.
     auto step = [&](int q, Buf &X, Buf &Y) {
       request(q + 2, X);
@@ -176,10 +212,39 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
   locate(0, s, rb);
   int4_u c0 = *reinterpret_cast<const int4_u *>(col + s);
   int4_u c1 = *reinterpret_cast<const int4_u *>(col + s + 4);
+  if constexpr (kShadow) {
+    // pass 0 written out, in the loop's own order, with the shadow between its row loads and its FMAs
+    int4_u n0 = c0, n1 = c1;
+    int32_t ns = s, nrb = rb;
+    if constexpr (NP > 1) {
+      locate(1, ns, nrb);
+      n0 = *reinterpret_cast<const int4_u *>(col + ns);
+      n1 = *reinterpret_cast<const int4_u *>(col + ns + 4);
+    }
+    const float4_u w0 = *reinterpret_cast<const float4_u *>(val + s);
+    const float4_u w1 = *reinterpret_cast<const float4_u *>(val + s + 4);
+    float4_t v[GE];
+    issue_group<FIN, GE, (NP > 1)>(xb, lane_off, c0, c1, v);
+    __builtin_amdgcn_sched_barrier(0);
+    shadow();
+    __builtin_amdgcn_sched_barrier(0);
+    float4_t acc = fma_group<GE>(v, w0, w1, float4_t{0.f, 0.f, 0.f, 0.f});
+    if constexpr (!UNI) {
+      for (int32_t q = s + 8; q < rb; q += 8) {
+        const int4_u d0 = *reinterpret_cast<const int4_u *>(col + q);
+        const int4_u d1 = *reinterpret_cast<const int4_u *>(col + q + 4);
+        const float4_u x0 = *reinterpret_cast<const float4_u *>(val + q);
+        const float4_u x1 = *reinterpret_cast<const float4_u *>(val + q + 4);
+        acc = gather_group<FIN>(xb, lane_off, d0, d1, x0, x1, acc);
+      }
+    }
+    sink(wave * R + gr, acc);
+    c0 = n0; c1 = n1; s = ns; rb = nrb;
+  }
   // a rolled loop: fully unrolled, hipcc hoists several passes' gathers at once and the register
   // count (172 VGPRs at Fin = 128) costs more occupancy than the extra overlap returns
 #pragma unroll 1
-  for (int p = 0; p < NP; ++p) {
+  for (int p = kShadow ? 1 : 0; p < NP; ++p) {
     int4_u n0 = c0, n1 = c1;
     int32_t ns = s, nrb = rb;
     if (p + 1 < NP) {                                    // next pass's source rows, one pass ahead

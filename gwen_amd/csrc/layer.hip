@@ -16,7 +16,17 @@
 //            at most 7 entries (GE = 7, gather_rows.h) the 8th slot -- padding on every row -- is not
 //            gathered at all.  The aggregated rows go to the block's
 //            LDS tile.  Meanwhile each wave fetches ITS slice of W^T -- the B fragments of its 16
-//            output columns -- straight from global memory (16 KB, L1/L2-resident) into registers;
+//            output columns -- straight from global memory (16 KB, L1/L2-resident) into registers.
+//            "Meanwhile" is made true by hand in the narrow forward kernels (one chunk per block): the raw
+//            W loads and the bias load (unconditional: from W itself and masked when there is no bias)
+//            are issued first and nothing waits for them; the first column indices are requested right
+//            behind them; W is split into its bf16 images in the shadow of the first pass's row loads
+//            (gather_rows.h, shadow; pinned there: split.h, pin_here).  A block is then two dependent
+//            round trips -- indices, rows -- where hipcc's own order was three: W and bias (vmcnt(0)),
+//            the split, and only then the first index load, because the split is invariant in the chunk
+//            loop that the narrow kernels shared with the persistent wide form and so sat above its
+//            header.  The narrow forward now leaves that loop after its one chunk (no back edge); the
+//            wide form and the backward compile to the code they had;
 //   barrier;
 //   phase 2  wave w owns output-column tile j = w % NJ of every (NWB/NJ)-th 16-row tile: A fragments
 //            from LDS, MFMAs with W as the A operand (so the D tile comes out transposed: one lane =
@@ -65,6 +75,13 @@ struct Cfg {
   static_assert(BR % RB == 0 && BR % kTile == 0, "a block is whole gather passes and whole row tiles");
 };
 
+// Which narrow forward shapes (Fin, Fout, images) run the two-round-trip prologue of the header: straight-line body,
+// unconditional bias load, W split pinned in the shadow of the first row loads.  false keeps the order the kernel had
+// (W and bias waited for and W split in front of the first index request), instruction for instruction.
+// 16 -> 32 on bf16x6 stays as it was: the new order needs 61 VGPRs (+ 4 AGPRs) against 58, which is 7 waves per SIMD
+// instead of 8, and measured no gain for it (9.19 -> 9.30 us, inside its spread; W is 4 floats per lane there).
+constexpr bool layer_prologue(int fin, int fout, int ns) { return !(fin == 16 && fout == 32 && ns == 3); }
+
 // BWD (the layer's backward, gwen_gcn_layer_bwd_f32): the aggregated rows are also stored (agg_out: the
 // operand of grad_W) and the result is masked by mask > 0 (the ReLU of the layer below), so the launch
 // returns the gradient the next backward launch starts from.
@@ -99,11 +116,25 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   const uint32_t lane_off = gl * 16;                       // x rows are contiguous (ldx == Fin)
 
   // ---- this wave's B fragments (its 16 output columns of W^T), issued before the gathers ---------
+  // Narrow forward kernels (one chunk per block, kShadow): only the RAW loads are issued here -- W, then bias, with no
+  // wait behind them -- and the split into bf16 images waits for gather_passes' shadow, after the first pass's row
+  // loads have left.  W then costs the block no round trip of its own: a block is indices, then rows.  The persistent
+  // wide form and the backward keep the prologue they had: W split at once, above the chunk loop.
+  constexpr bool kPersist = FIN * FOUT >= 128 * 128;
+  constexpr bool kOnce = !kPersist && !BWD && layer_prologue(FIN, FOUT, NS);   // the narrow forward: one chunk per block
+  constexpr bool kShadow = kOnce && SPLIT;
   const int j = wave % C::NJ;
   const float *wrow = W + (int64_t)(j * 16 + mi) * FIN;
   float2_t bfr[SPLIT ? 1 : C::NQ];
   typename BF<C::KF>::T bw[SPLIT ? C::KS : 1][NI];                       // W images per k-step
-  if constexpr (SPLIT) {
+  float4_t wraw[kShadow ? C::KS : 1][kShadow ? C::KF / 4 : 1];   // kShadow: W as loaded
+  if constexpr (kShadow) {
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks)
+#pragma unroll
+      for (int i = 0; i < C::KF; i += 4)
+        wraw[ks][i / 4] = *reinterpret_cast<const float4_t *>(wrow + C::KF * (4 * ks + mh) + i);
+  } else if constexpr (SPLIT) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks) {
       float wv[C::KF];
@@ -122,19 +153,43 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
       bfr[q] = *reinterpret_cast<const float2_t *>(wrow + 8 * q + 2 * mh);
   }
   float4_t bv4 = {0.f, 0.f, 0.f, 0.f};
-  if (bias) bv4 = *reinterpret_cast<const float4_t *>(bias + j * 16 + 4 * mh);
+  if constexpr (!kOnce) {
+    if (bias) bv4 = *reinterpret_cast<const float4_t *>(bias + j * 16 + 4 * mh);
+  } else {
+    // never a load under a condition (gather_rows.h): without a bias the same 16 bytes of W are read (W holds
+    // Fout * Fin >= Fout floats) and masked to +0 -- the value bv4 has always had then -- in the shadow callable:
+    // masked here, the mask would wait for the load in front of the first index request
+    bv4 = *reinterpret_cast<const float4_t *>((bias ? bias : W) + j * 16 + 4 * mh);
+    __builtin_amdgcn_sched_barrier(0);                     // the raw loads stay in front of the first index request
+  }
+  auto split_w = [&]() {                                   // in the first row loads' shadow (kOnce)
+    bv4 = gwen::masked_f4(bv4, bias != nullptr);
+    gwen::pin_here(bv4);                                   // or mask and load sink to the epilogue
+    if constexpr (kShadow) {                               // raw W -> images
+#pragma unroll
+      for (int ks = 0; ks < C::KS; ++ks) {
+        float wv[C::KF];
+#pragma unroll
+        for (int i = 0; i < C::KF; i += 4)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) wv[i + e] = wraw[ks][i / 4][e];
+        gwen::split_images<C::KF, NI>(wv, bw[ks]);
+#pragma unroll
+        for (int s_ = 0; s_ < NI; ++s_) gwen::pin_here(bw[ks][s_]);   // or the optimiser sinks the split, and W's loads, to phase 2
+      }
+    }
+  };
 
-  // A block walks chunks lb, lb + grid, ... of BR rows: with one chunk per block (narrow layers) the
-  // loop runs once; wide layers launch one resident set of blocks so that W -- fetched and split into
-  // this wave's registers once, above -- serves many chunks (at 256 channels W is half as many bytes
-  // as a 64-row chunk gathers)
-  constexpr bool kPersist = FIN * FOUT >= 128 * 128;
+  // A block of the persistent wide form walks chunks lb, lb + grid, ... of BR rows: one resident set of blocks, so
+  // that W -- fetched and split into this wave's registers once, above -- serves many chunks (at 256 channels W is
+  // half as many bytes as a 64-row chunk gathers).  A narrow layer has one chunk per block; its forward leaves the
+  // loop at the end of the body (if constexpr, below), so it is straight-line code: with a back edge the
+  // (loop-invariant) W split had to sit above the loop header, in front of the gather.
   const int nchunks = kPersist ? (N + C::BR - 1) / C::BR : lb + 1;
   for (int chunk = lb; chunk < nchunks; chunk += nb) {
   const int b0 = chunk * C::BR;
   // ---- phase 1: gather + aggregate into the LDS tile (gather_rows.h) ------------------------------
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(
-      rowptr, col, val, xb, N, b0, wave, gr, lane_off, [&](int lr, float4_t acc) {
+  auto sink = [&](int lr, float4_t acc) {
         if constexpr (BWD) {
           if (agg_out && b0 + lr < N)
             *reinterpret_cast<float4_t *>(agg_out + (int64_t)blockIdx.y * mstride_x +
@@ -150,7 +205,11 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
         } else {
           *reinterpret_cast<float4_t *>(tile + lr * C::PF + gl * 4) = acc;
         }
-      });
+      };
+  if constexpr (kOnce)
+    gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink, split_w);
+  else
+    gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink);
   __syncthreads();
 
   // ---- phase 2: (tile) x (this wave's 16 columns of W^T), bias, ReLU, store ----------------------
@@ -224,6 +283,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
     }
   }
   if constexpr (kPersist) __syncthreads();     // the tile is free for the next chunk
+  if constexpr (kOnce) break;                  // one chunk per block: no back edge
   }
 }
 

@@ -35,6 +35,14 @@ __device__ inline void split_images(const float (&x)[K], typename BFv<K>::T (&im
   }
 }
 
+// Keeps the instructions that computed `v` where the source has them: an empty volatile asm that "rewrites" the
+// register.  sched_barrier pins the machine scheduler only; without this the optimiser sinks a split whose images
+// are first read behind a barrier down to that first use.
+template <typename T>
+__device__ __forceinline__ void pin_here(T &v) {
+  asm volatile("" : "+v"(v));
+}
+
 // d += W-images (the MFMA A operand) x row-images (the B operand): KF = 8 -> 16x16x32, KF = 4 -> 16x16x16.
 // Term order for NS = 2: (w0,a1) (w1,a0) (w0,a0) -- the order K4 has always used, bit for bit.
 template <int KF, int NS>
