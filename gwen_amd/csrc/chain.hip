@@ -22,6 +22,7 @@
 // k_gather loads its bias above the gather as well (from x when there is none; nothing is added then), not in the sink,
 // where it was a dependent round trip at the tail of every wave.
 #include "common.h"
+#include "dispatch.h"
 #include "gather_rows.h"
 #include "split.h"
 
@@ -83,26 +84,41 @@ struct Frag {
   }
 };
 
-// FIN: gathered width.  F1: width after the first contraction.  F2: width after the second (0: none).
-// BRQ: rows per block asked for below 128 channels (64; 96 / 112 where they are whole gather passes: chain_rows_ok)
-template <int FIN, int F1, int F2, bool PRE, int NS, int BRQ = 64>
-struct Cfg {
-  static constexpr int G = FIN / 4, R = 64 / G;
-  static constexpr int NJ1 = F1 / 16, NJ2 = F2 / 16;
-  static constexpr int NWB = NJ1 > 4 ? 8 : 4;
-  static constexpr int RB = NWB * R;
-  static constexpr int BRMIN = FIN >= 128 ? 128 : BRQ;
-  static constexpr int BR = RB > BRMIN ? RB : BRMIN;
-  static constexpr int NP = BR / RB, NT = BR / kTile;
-  static_assert(BR % RB == 0 && BR % kTile == 0, "a block is whole gather passes and whole row tiles");
-  static constexpr int PB0 = pitch_bf16(FIN), PB1 = pitch_bf16(F1);
-  static constexpr int FW = F2 > 0 ? F2 : F1;              // stored width
+// The block geometry of K5 -- the one copy of the rule.  Plain ints in, so the kernels read it at compile time (Cfg) and
+// the extern "C" checks at run time (rows_valid, gwen_gcn_chain_supported).  brq: Cfg's BRQ.
+struct Geom {
+  int G, R;                                                // lanes per gathered row, rows per wave pass
+  int NWB, RB;                                             // waves per block, rows gathered per block pass
+  int BRMIN, BR;                                           // rows per block: asked for, and had (whole gather passes)
+  int PB0, PB1;                                            // row pitch (bf16) of the aggregated rows', the first product's images
   // bf16x6 (three images): the first product's images take the place of the aggregated rows' (one more barrier,
   // the product waits in registers meanwhile) -- with both sets resident 64 -> 64 -> 32 kept two blocks per CU
   // instead of three and ran 30.5 us against 22.9 for bf16x3
-  static constexpr bool ALIAS = NS == 3 && F2 > 0;
-  static constexpr size_t img0 = (size_t)NS * BR * PB0, img1 = F2 > 0 ? (size_t)NS * BR * PB1 : 0;
-  static constexpr size_t lds_elems = ALIAS ? (img0 > img1 ? img0 : img1) : img0 + img1;
+  bool ALIAS;
+  size_t img0, img1, lds_elems;                            // bf16 elements: either set of images, one block
+  constexpr Geom(int fin, int f1, int f2, int ns, int brq)
+      : G(fin / 4), R(64 / (fin / 4)), NWB(f1 / 16 > 4 ? 8 : 4), RB(NWB * R), BRMIN(fin >= 128 ? 128 : brq),
+        BR(RB > BRMIN ? RB : BRMIN), PB0(pitch_bf16(fin)), PB1(pitch_bf16(f1)), ALIAS(ns == 3 && f2 > 0),
+        img0((size_t)ns * BR * PB0), img1(f2 > 0 ? (size_t)ns * BR * PB1 : 0),
+        lds_elems(ALIAS ? (img0 > img1 ? img0 : img1) : img0 + img1) {}
+  constexpr bool fits(size_t lds_bytes) const { return lds_elems * 2 <= lds_bytes; }
+};
+constexpr size_t kLdsCU = 160 * 1024;                      // LDS of a CU
+
+// FIN: gathered width.  F1: width after the first contraction.  F2: width after the second (0: none).
+// BRQ: rows per block asked for below 128 channels (64; 96 / 112 where they are whole gather passes: rows_ok)
+template <int FIN, int F1, int F2, bool PRE, int NS, int BRQ = 64>
+struct Cfg {
+  static constexpr Geom geo = Geom(FIN, F1, F2, NS, BRQ);
+  static constexpr int G = geo.G, R = geo.R;
+  static constexpr int NJ1 = F1 / 16, NJ2 = F2 / 16;
+  static constexpr int NWB = geo.NWB, RB = geo.RB, BRMIN = geo.BRMIN, BR = geo.BR;
+  static constexpr int NP = BR / RB, NT = BR / kTile;
+  static_assert(BR % RB == 0 && BR % kTile == 0, "a block is whole gather passes and whole row tiles");
+  static constexpr int PB0 = geo.PB0, PB1 = geo.PB1;
+  static constexpr int FW = F2 > 0 ? F2 : F1;              // stored width
+  static constexpr bool ALIAS = geo.ALIAS;
+  static constexpr size_t img0 = geo.img0, img1 = geo.img1, lds_elems = geo.lds_elems;
   static_assert(!(PRE && F2 > 0), "activation-first has one contraction");
   static_assert(NWB % NJ1 == 0 && (F2 == 0 || NWB % NJ2 == 0), "waves must tile the columns");
 };
@@ -285,77 +301,83 @@ __global__ __launch_bounds__(256) void k_gather(
       });
 }
 
-template <int FIN, int D = 1>
-int launch_gather(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
-                  const float *bias, float *out, int64_t N, int64_t members, int64_t msx,
-                  int64_t mso, int relu, int entries, int block_rows, hipStream_t st) {
-  constexpr int BR = 4 * (64 / (FIN / 4));
-  if (block_rows != 0 && block_rows != BR) return GWEN_EINVAL;      // one pass per wave: one block size
-  dim3 grid((unsigned)((N + BR - 1) / BR), (unsigned)members);
-  if constexpr (FIN <= 64) {
-    if (!rowptr && entries == 7) {
-      k_gather<FIN, true, 7, D><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
-      GWEN_LAUNCH_CHECK();
-      return GWEN_OK;
-    }
-  }
-  if (!rowptr)
-    k_gather<FIN, true, 8, D><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
-  else
-    k_gather<FIN, false, 8, D><<<grid, 256, 0, st>>>(rowptr, col, val, x, bias, out, (int32_t)N, msx, mso, relu);
-  GWEN_LAUNCH_CHECK();
-  return GWEN_OK;
+// What one K5 launch (k_chain or k_gather) works on; gwen_gcn_chain_tuned_f32 fills it once.
+struct ChainArgs {
+  const int32_t *rowptr, *col;                             // rowptr NULL = uniform layout
+  const float *val, *x, *W1, *W2, *bias;
+  float *out;
+  int64_t N, members, msx, mso;
+  int relu, entries;
+  hipStream_t st;
+};
+
+constexpr bool narrow(int fin, int f1) { return fin <= 64 && f1 <= 64; }
+constexpr int gather_rows(int fin) { return 4 * Geom(fin, 0, 0, 2, 64).R; }   // k_gather's block: one pass of four waves
+
+// rows per block that the narrow kernels (Fin, F1 <= 64) can be asked for: whole gather passes; at 112 rows the largest
+// of them, 64 -> 64 -> 32 on bf16x3, holds 70 KiB of LDS.  Decides which launch_br are instantiated and, with the kernel's
+// own size, what block_rows a caller may force.
+constexpr bool rows_ok(int fin, int f1, int br) {
+  return narrow(fin, f1) && (br == 64 || br == 96 || br == 112) && br % Geom(fin, f1, 0, 2, 64).RB == 0;
 }
 
-// rows per block that the narrow kernels (Fin, F1 <= 64) can be asked for: whole gather passes (chain_rows_valid
-// is the same rule at run time); at 112 rows the largest of them, 64 -> 64 -> 32 on bf16x3, holds 70 KiB of LDS
-template <int FIN, int F1, int F2, bool PRE, int NS>
-constexpr bool chain_rows_ok(int br) {
-  return FIN <= 64 && F1 <= 64 && (br == 64 || br == 96 || br == 112) && br % Cfg<FIN, F1, F2, PRE, NS>::RB == 0;
+// block_rows of gwen_gcn_chain_tuned_f32: 0, the kernel's own size, or 96 / 112 on the narrow kernels.  plain: k_gather
+constexpr bool rows_valid(int fin, int f1, bool plain, int br) {
+  if (br == 0) return true;
+  if (plain) return br == gather_rows(fin);
+  return br == Geom(fin, f1, 0, 2, 64).BR || rows_ok(fin, f1, br);
+}
+
+// gathered entries: 7 only on the uniform layout, when the caller promises it, on widths up to 64
+template <int FIN, int D>
+int launch_gather(const ChainArgs &a) {
+  constexpr int BR = gather_rows(FIN);
+  dim3 grid((unsigned)((a.N + BR - 1) / BR), (unsigned)a.members);
+  auto run = [&](auto kernel) {
+    kernel<<<grid, 256, 0, a.st>>>(a.rowptr, a.col, a.val, a.x, a.bias, a.out, (int32_t)a.N, a.msx, a.mso, a.relu);
+    GWEN_LAUNCH_CHECK();
+    return (int)GWEN_OK;
+  };
+  if (a.rowptr) return run(&k_gather<FIN, false, 8, D>);
+  if constexpr (FIN <= 64) {
+    if (a.entries == 7) return run(&k_gather<FIN, true, 7, D>);
+  }
+  return run(&k_gather<FIN, true, 8, D>);
 }
 
 template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ>
-int launch_br(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
-              const float *W1, const float *W2, const float *bias, float *out, int64_t N,
-              int64_t members, int64_t msx, int64_t mso, int relu, int entries, hipStream_t st) {
+int launch_br(const ChainArgs &a) {
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
-  static_assert(C::lds_elems * 2 <= 160 * 1024, "one block must fit a CU's LDS");
-  const int64_t blocks = (N + C::BR - 1) / C::BR;
-  dim3 grid((unsigned)blocks, (unsigned)members);
-  if constexpr (FIN <= 64 && F1 <= 64) {           // 7 gathered entries: the narrow kernels only
-    if (!rowptr && entries == 7) {
-      k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
-                                                                                   out, (int32_t)N, msx, mso, relu);
-      GWEN_LAUNCH_CHECK();
-      return GWEN_OK;
-    }
+  static_assert(C::geo.fits(kLdsCU), "one block must fit a CU's LDS");
+  dim3 grid((unsigned)((a.N + C::BR - 1) / C::BR), (unsigned)a.members);
+  auto run = [&](auto kernel) {
+    kernel<<<grid, C::NWB * 64, 0, a.st>>>(a.rowptr, a.col, a.val, a.x, a.W1, a.W2, a.bias, a.out, (int32_t)a.N, a.msx,
+                                           a.mso, a.relu);
+    GWEN_LAUNCH_CHECK();
+    return (int)GWEN_OK;
+  };
+  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, NS>);
+  if constexpr (narrow(FIN, F1)) {
+    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, NS>);
   }
-  if (!rowptr)
-    k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias, out,
-                                                                                 (int32_t)N, msx, mso, relu);
-  else
-    k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, NS><<<grid, C::NWB * 64, 0, st>>>(rowptr, col, val, x, W1, W2, bias,
-                                                                                  out, (int32_t)N, msx, mso, relu);
-  GWEN_LAUNCH_CHECK();
-  return GWEN_OK;
+  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, NS>);
 }
 
-// block_rows: 0 = the library's choice; 96 / 112 where chain_rows_ok says.
+// block_rows: 0 = the library's choice; else the kernel's own size or 96 / 112 (rows_ok; checked by the extern "C" caller).
 // The library's choice is 64 rows (128 from 128 channels on).  K4's "smallest size whose grid is co-resident" finds no
 // such size for the c2 mesh here (64 -> 64 -> 32: 4, 3 and 2 blocks per CU at 64 / 96 / 112 rows against 1 563 / 1 042 /
 // 893 blocks) and 96 / 112 rows measured SLOWER at depth 1 (23.3 / 23.5 against 22.2 us), so depth 1 keeps 64.  At depth
 // 2 one member whose 64-row grid is more than one resident round runs 112-row blocks where the width allows it: the
 // two-deep gather fills and drains once per block (20.1 against 20.8 us).
 template <int FIN, int F1, int F2, bool PRE, int NS, int D>
-int launch_ns(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
-              const float *W1, const float *W2, const float *bias, float *out, int64_t N,
-              int64_t members, int64_t msx, int64_t mso, int relu, int entries, int block_rows, hipStream_t st) {
-#define GWEN_BR(BRV)                                                                                \
-  launch_br<FIN, F1, F2, PRE, NS, D, BRV>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, st)
-  if constexpr (D == 2 && chain_rows_ok<FIN, F1, F2, PRE, NS>(112)) {
-    if (block_rows == 0 && members == 1) {
-      static int per_cu[3] = {0, 0, 0};                // of the 64-row kernel this call would launch otherwise
-      const int v = rowptr ? 2 : (entries == 7 ? 0 : 1);
+int launch_ns(const ChainArgs &a, int block_rows) {
+  int brq = block_rows == 0 || block_rows == Cfg<FIN, F1, F2, PRE, NS>::BR ? 64 : block_rows;   // BRQ 64 = the own size
+  if constexpr (D == 2 && rows_ok(FIN, F1, 112)) {
+    if (block_rows == 0 && a.members == 1) {
+      // blocks per CU of the 64-row kernel this call would launch otherwise; probed once per kernel (function-local
+      // static): a warm call makes no HIP query, so the launcher stays capturable
+      static int per_cu[3] = {0, 0, 0};
+      const int v = a.rowptr ? 2 : (a.entries == 7 ? 0 : 1);
       if (per_cu[v] == 0) {
         const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, NS>)
                         : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, NS>)
@@ -364,81 +386,40 @@ int launch_ns(const int32_t *rowptr, const int32_t *col, const float *val, const
         GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k, Cfg<FIN, F1, F2, PRE, NS>::NWB * 64, 0));
         per_cu[v] = nbk < 1 ? 1 : nbk;
       }
-      if ((N + 63) / 64 > (int64_t)256 * per_cu[v]) return GWEN_BR(112);
+      if ((a.N + 63) / 64 > (int64_t)256 * per_cu[v]) brq = 112;
     }
   }
-  if (block_rows == 0 || block_rows == Cfg<FIN, F1, F2, PRE, NS>::BR) return GWEN_BR(64);
-  if constexpr (chain_rows_ok<FIN, F1, F2, PRE, NS>(96)) { if (block_rows == 96) return GWEN_BR(96); }
-  if constexpr (chain_rows_ok<FIN, F1, F2, PRE, NS>(112)) { if (block_rows == 112) return GWEN_BR(112); }
-#undef GWEN_BR
-  return GWEN_EINVAL;
-}
-
-template <int FIN, int F1, int F2, bool PRE>
-int launch(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
-           const float *W1, const float *W2, const float *bias, float *out, int64_t N,
-           int64_t members, int64_t msx, int64_t mso, int relu, int contract, int entries, int depth, int block_rows,
-           hipStream_t st) {
-#define GWEN_NS(NSV, DV)                                                                            \
-  launch_ns<FIN, F1, F2, PRE, NSV, DV>(rowptr, col, val, x, W1, W2, bias, out, N, members, msx, mso, relu, entries, \
-                                       block_rows, st)
-  constexpr bool narrow = FIN <= 64 && F1 <= 64;   // gather depth 2: the narrow kernels only
-  if (contract == GWEN_CONTRACT_BF16X6) {
-    // width triples whose three images do not fit a CU's LDS are refused by gwen_gcn_chain_supported already
-    if constexpr (Cfg<FIN, F1, F2, PRE, 3>::lds_elems * 2 <= 160 * 1024) {
-      if constexpr (narrow) { if (depth == 2) return GWEN_NS(3, 2); }
-      return GWEN_NS(3, 1);
-    } else {
-      return GWEN_EINVAL;
-    }
-  }
-  if constexpr (narrow) { if (depth == 2) return GWEN_NS(2, 2); }
-  return GWEN_NS(2, 1);
-#undef GWEN_NS
+  return gwen::dispatch(gwen::ints<64, 96, 112>{}, brq, [&](auto brv) {
+    constexpr int BRQ = decltype(brv)::value;
+    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ>(a);
+    else return (int)GWEN_EINVAL;
+  });
 }
 
 constexpr bool width_ok(int64_t f) { return f == 16 || f == 32 || f == 64 || f == 128; }
 
 }  // namespace
 
-// LDS of one block (bytes), as Cfg computes it; the chained form keeps two sets of NS images
-inline int64_t chain_lds_bytes(int64_t Fin, int64_t F1, int64_t F2, int ns) {
-  const int64_t R = 64 / (Fin / 4), nwb = F1 / 16 > 4 ? 8 : 4, rb = nwb * R;
-  const int64_t brmin = Fin >= 128 ? 128 : 64, br = rb > brmin ? rb : brmin;
-  const int64_t i0 = ns * br * pitch_bf16((int)Fin) * 2, i1 = F2 > 0 ? ns * br * pitch_bf16((int)F1) * 2 : 0;
-  return ns == 3 && F2 > 0 ? (i0 > i1 ? i0 : i1) : i0 + i1;        // bf16x6: the second set replaces the first
-}
-
 extern "C" int gwen_gcn_chain_supported(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract) {
   if (contract != GWEN_CONTRACT_BF16X3 && contract != GWEN_CONTRACT_BF16X6) return 0;
   const int ns = gwen::images_of(contract);
   if (pre && F1 == 0 && F2 == 0) return width_ok(Fin) ? 1 : 0;      // activation-first, nothing chained
   if (!width_ok(Fin) || !width_ok(F1)) return 0;
-  if (pre) return F2 == 0 && chain_lds_bytes(Fin, F1, 0, ns) <= 150 * 1024 ? 1 : 0;   // one block must fit the CU
+  if (pre) return F2 == 0 && Geom(Fin, F1, 0, ns, 64).fits(150 * 1024) ? 1 : 0;   // one block must fit the CU
   if (!(width_ok(F2) && F2 < F1)) return 0;          // chained projection of a SHRINKING next layer
-  // worth it only while two blocks still fit a CU's 160 KiB of LDS (otherwise K4, then K3 + K2)
-  return chain_lds_bytes(Fin, F1, F2, ns) <= 80 * 1024 ? 1 : 0;
+  // worth it only while two blocks still fit a CU's LDS (otherwise K4, then K3 + K2)
+  return Geom(Fin, F1, F2, ns, 64).fits(kLdsCU / 2) ? 1 : 0;
 }
 
 // The library's gather depth per (Fin, F1, F2, images) on the uniform layout: 2 only where the kernel measured faster
-// on the MI355X (profiles/depth_*); the non-uniform layout and widths above 64 run depth 1.
+// on the MI355X ("Gather depth"; profiles/depth_*); the non-uniform layout and widths above 64 run depth 1.
 static constexpr int chain_depth(int64_t fin, int64_t f1, int64_t f2, int ns) {
-  return fin == 64 && f1 == 64 && f2 == 32 && ns == 3 ? 2 : 1;     // 64 -> 64 -> 32, bf16x6: 23.1 -> 20.3 us on the c2 mesh
-}
-
-// block_rows of gwen_gcn_chain_tuned_f32: 0, the kernel's own size, or 96 / 112 on the narrow kernels (chain_rows_ok)
-static bool chain_rows_valid(int64_t Fin, int64_t F1, int pre, int br) {
-  if (br == 0) return true;
-  const int64_t R = 64 / (Fin / 4);
-  if (pre && F1 == 0) return br == 4 * R;
-  const int64_t rb = (F1 / 16 > 4 ? 8 : 4) * R, brmin = Fin >= 128 ? 128 : 64;
-  if (br == (rb > brmin ? rb : brmin)) return true;
-  return Fin <= 64 && F1 <= 64 && (br == 96 || br == 112) && br % rb == 0;
+  return fin == 64 && f1 == 64 && f2 == 32 && ns == 3 ? 2 : 1;     // 64 -> 64 -> 32 on bf16x6
 }
 
 extern "C" int gwen_gcn_chain_depth(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract) {
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return 0;
-  if (Fin > 64 || F1 > 64) return 1;
+  if (!narrow(Fin, F1)) return 1;
   return chain_depth(Fin, F1, F2, gwen::images_of(contract));
 }
 
@@ -454,7 +435,8 @@ extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *co
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0) return GWEN_EINVAL;
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return GWEN_EINVAL;
-  if (!chain_rows_valid(Fin, F1, pre, block_rows)) return GWEN_EINVAL;
+  const bool plain = pre && F1 == 0;                       // activation-first, nothing chained: k_gather
+  if (!rows_valid(Fin, F1, plain, block_rows)) return GWEN_EINVAL;             // the one check of block_rows
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || (F1 > 0 && !W1) || !out || x == out || (F2 > 0 && !W2))
     return GWEN_EINVAL;                                    // rowptr NULL = uniform layout
@@ -463,34 +445,43 @@ extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *co
       (W2 && !gwen_aligned(W2, 16)) || (bias && !gwen_aligned(bias, 16)) || mstride_x % 4)
     return GWEN_EINVAL;
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
-  hipStream_t st = gwen_stream(stream_);
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_chain_depth(Fin, F1, F2, pre, contract);
-  if (pre && F1 == 0) {
-#define GWEN_G(FI, DV)                                                                              \
-  if (Fin == FI)                                                                                    \
-    return launch_gather<FI, DV>(rowptr, col, val, x, bias, out, N, members, mstride_x, mstride_o, relu, entries, \
-                                 block_rows, st)
-    if (depth == 2) { GWEN_G(16, 2); GWEN_G(32, 2); GWEN_G(64, 2); }
-    GWEN_G(16, 1); GWEN_G(32, 1); GWEN_G(64, 1); GWEN_G(128, 1);
-#undef GWEN_G
-  }
-#define GWEN_P(FI, FA)                                                                              \
-  if (pre && Fin == FI && F1 == FA)                                                                 \
-    return launch<FI, FA, 0, true>(rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x,   \
-                                   mstride_o, relu, contract, entries, depth, block_rows, st)
-#define GWEN_C(FI, FA, FB)                                                                          \
-  if (!pre && Fin == FI && F1 == FA && F2 == FB)                                                    \
-    return launch<FI, FA, FB, false>(rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, \
-                                     mstride_o, relu, contract, entries, depth, block_rows, st)
-#define GWEN_ROW(FI)                                                                                \
-  GWEN_P(FI, 16); GWEN_P(FI, 32); GWEN_P(FI, 64); GWEN_P(FI, 128);                                  \
-  GWEN_C(FI, 32, 16); GWEN_C(FI, 64, 16); GWEN_C(FI, 64, 32);                                       \
-  GWEN_C(FI, 128, 16); GWEN_C(FI, 128, 32); GWEN_C(FI, 128, 64)
-  GWEN_ROW(16); GWEN_ROW(32); GWEN_ROW(64); GWEN_ROW(128);
-#undef GWEN_ROW
-#undef GWEN_C
-#undef GWEN_P
-  return GWEN_EINVAL;
+  const ChainArgs a{rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, mstride_o, relu, entries,
+                    gwen_stream(stream_)};
+  using Widths = gwen::ints<16, 32, 64, 128>;
+  using Depths = gwen::ints<1, 2>;
+  return gwen::dispatch(Widths{}, Fin, [&](auto fi) {
+    constexpr int FI = decltype(fi)::value;
+    if (plain) {
+      return gwen::dispatch(Depths{}, FI <= 64 ? depth : 1, [&](auto dv) {         // gather depth 2: up to 64 channels
+        if constexpr (FI <= 64 || decltype(dv)::value == 1) return launch_gather<FI, decltype(dv)::value>(a);
+        else return (int)GWEN_EINVAL;
+      });
+    }
+    return gwen::dispatch(Widths{}, F1, [&](auto fa) {
+      return gwen::dispatch(gwen::ints<0, 16, 32, 64>{}, F2, [&](auto fb) {
+        return gwen::dispatch(gwen::ints<0, 1>{}, pre != 0, [&](auto pv) {
+          constexpr int FA = decltype(fa)::value, FB = decltype(fb)::value;
+          constexpr bool PRE = decltype(pv)::value != 0;
+          // activation-first has one contraction; a chained projection is the SHRINKING next layer's
+          if constexpr (PRE ? FB == 0 : (FB > 0 && FB < FA)) {
+            return gwen::dispatch(gwen::ints<2, 3>{}, gwen::images_of(contract), [&](auto nsv) {
+              return gwen::dispatch(Depths{}, narrow(FI, FA) ? depth : 1, [&](auto dv) {   // depth 2: narrow only
+                constexpr int NS = decltype(nsv)::value, D = decltype(dv)::value;
+                // bf16x6 only where its three images fit a CU's LDS (gwen_gcn_chain_supported refuses the others)
+                if constexpr (Geom(FI, FA, FB, NS, 64).fits(kLdsCU) && (D == 1 || narrow(FI, FA)))
+                  return launch_ns<FI, FA, FB, PRE, NS, D>(a, block_rows);
+                else
+                  return (int)GWEN_EINVAL;
+              });
+            });
+          } else {
+            return (int)GWEN_EINVAL;
+          }
+        });
+      });
+    });
+  });
 }
 
 extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,

@@ -43,6 +43,7 @@
 //   row pitch Fin+4 floats => conflict-free 8-B reads): bit-exact fp32 fmaf chains.
 // Blocks are remapped so that the blocks sharing an XCD (blockIdx % 8) own neighbouring rows.
 #include "common.h"
+#include "dispatch.h"
 #include "gather_rows.h"
 #include "split.h"
 
@@ -53,24 +54,35 @@ using gwen::bf16x4;
 using gwen::bf16x8;
 template <int K> using BF = gwen::BFv<K>;
 
-// NS: bf16 images per operand (2: bf16x3, 3: bf16x6, split.h); 0: the fp32-input MFMA
+// The block geometry of K4 -- the one copy of the rule.  Plain ints in, so the kernels read it at compile time (Cfg)
+// and the extern "C" checks at run time (rows_ok).  ns: bf16 images per operand (2: bf16x3, 3: bf16x6, split.h); 0: the
+// fp32-input MFMA.  brmin: rows per block asked for; a block is never less than one gather pass.
+struct Geom {
+  int G, R;                                                // lanes per gathered row, rows per wave pass
+  int NJ, NWB;                                             // 16-column output tiles; waves per block: one per column tile
+  int RB, BR;                                              // rows gathered per block pass, rows per block
+  int PF, PB;                                              // tile row pitch: exact (floats), split (bf16)
+  size_t lds_bytes;
+  bool wide;                                               // the persistent form: one resident set of blocks walks the chunks
+  constexpr Geom(int fin, int fout, int ns, int brmin)
+      : G(fin / 4), R(64 / (fin / 4)), NJ(fout / 16), NWB(NJ > 8 ? 16 : (NJ > 4 ? 8 : 4)), RB(NWB * R),
+        BR(RB > brmin ? RB : brmin), PF(fin + 4), PB(((fin / 2) % 16 == 8 ? fin / 2 : fin / 2 + 8) * 2),
+        lds_bytes(ns > 0 ? (size_t)ns * BR * PB * 2 : (size_t)BR * PF * 4), wide(fin * fout >= 128 * 128) {}
+};
+
 template <int FIN, int FOUT, int NS, int BRMIN = 32>
 struct Cfg {
+  static constexpr Geom geo = Geom(FIN, FOUT, NS, BRMIN);
   static constexpr bool SPLIT = NS > 0;
-  static constexpr int G = FIN / 4, R = 64 / G;            // lanes per gathered row, rows per wave pass
-  static constexpr int NJ = FOUT / 16;                     // 16-column output tiles
-  static constexpr int NWB = NJ > 8 ? 16 : (NJ > 4 ? 8 : 4);   // waves per block: one per column tile
-  static constexpr int RB = NWB * R;                       // rows gathered per block pass
-  static constexpr int BR = RB > BRMIN ? RB : BRMIN;       // rows per block
+  static constexpr int G = geo.G, R = geo.R, NJ = geo.NJ, NWB = geo.NWB, RB = geo.RB, BR = geo.BR;
   static constexpr int NP = BR / RB;                       // gather passes per wave
   static constexpr int NT = BR / kTile;                    // 16-row tiles per block
   static constexpr int TSTEP = NWB / NJ;                   // row tiles are strided over the waves
   static constexpr int NQ = FIN / 8;                       // exact: k-steps of 8
   static constexpr int KF = FIN >= 32 ? 8 : 4;             // split: bf16 per fragment (K = 32 or 16)
   static constexpr int KS = FIN / (4 * KF);                // split: MFMA k-steps
-  static constexpr int PF = FIN + 4;                       // exact: tile row pitch (floats)
-  static constexpr int PB = ((FIN / 2) % 16 == 8 ? FIN / 2 : FIN / 2 + 8) * 2;   // split: pitch (bf16)
-  static constexpr size_t lds_bytes = SPLIT ? (size_t)NS * BR * PB * 2 : (size_t)BR * PF * 4;
+  static constexpr int PF = geo.PF, PB = geo.PB;
+  static constexpr size_t lds_bytes = geo.lds_bytes;
   static_assert(NWB % NJ == 0, "waves must tile the output columns");
   static_assert(BR % RB == 0 && BR % kTile == 0, "a block is whole gather passes and whole row tiles");
 };
@@ -287,110 +299,130 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   }
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN, int GE = 8, int D = 1>
-int launch_rows(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
-                const float *W, const float *bias, float *out, int64_t N, int64_t ldo, int64_t members,
-                int64_t msx, int64_t mso, int relu, hipStream_t st, bool probe, int64_t *resident_out,
-                float *agg_out = nullptr, const float *mask = nullptr, bool bwd = false, float *bsum_out = nullptr,
-                int64_t *chunks_out = nullptr) {
-  using C = Cfg<FIN, FOUT, NS, BRMIN>;
+// What one K4 launch works on; the forward and the backward entry points fill it once.
+struct LayerArgs {
+  const int32_t *rowptr, *col;                             // rowptr NULL = uniform layout
+  const float *val, *x, *W, *bias;
+  float *out;
+  int64_t N, ldo, members, msx, mso;
+  int relu;
+  hipStream_t st;
+  float *agg_out; const float *mask; float *bsum_out; int64_t *chunks_out; bool bwd;   // the backward's: see k_layer
+};
+
+constexpr bool narrow(int fin, int fout) { return fin <= 64 && fout <= 64; }
+
+// rows per block asked of the wide kernels: enough that W (read once per block) stays a small fraction of the gathered
+// bytes; 256: 64 rows keep two blocks per CU in LDS (bf16x3), and 64 rows at 256 channels on bf16x6 as well
+constexpr int wide_brmin(int fin) { return fin == 128 ? 128 : 64; }
+
+// Which rows per block exist for a shape: narrow layers 64 / 96 / 112 / 128 that are whole gather passes, wide layers
+// the kernel's one size.  Decides which launch_rows are instantiated and what block_rows a caller may force.
+constexpr bool rows_ok(int fin, int fout, int br) {
+  if (!narrow(fin, fout)) return br == Geom(fin, fout, 0, wide_brmin(fin)).BR;
+  return (br == 64 || br == 96 || br == 112 || br == 128) && br % Geom(fin, fout, 0, br).RB == 0;
+}
+
+// Blocks of this instantiation that are resident at once.  Probed once per instantiation (function-local static): a warm
+// call makes no HIP query, so the launchers stay capturable.  The UNIFORM kernel is probed whichever layout is launched:
+// the block-rows choice of launch() on a non-uniform layout has always been made with the uniform kernel's occupancy.
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D>
+int resident_blocks(int64_t &resident) {
   static int per_cu = 0;
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D>), C::NWB * 64, 0));
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D>),
+        Cfg<FIN, FOUT, NS, BRMIN>::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
-  const int64_t resident = (int64_t)256 * per_cu;
-  if (resident_out) *resident_out = resident;
-  if (probe) return GWEN_OK;
-  int64_t blocks = (N + C::BR - 1) / C::BR;
-  const int64_t chunks_pm = blocks;                        // chunks of BR rows per member (bsum_out: one partial row each)
-  constexpr bool kWide = FIN * FOUT >= 128 * 128;          // the persistent form: no fused column sums (see the kernel)
-  if (kWide) bsum_out = nullptr;
-  if (chunks_out) *chunks_out = kWide ? 0 : chunks_pm * members;
-  if (FIN * FOUT >= 128 * 128 && blocks > resident) blocks = resident;   // wide layer: one resident set
-  dim3 grid((unsigned)blocks, (unsigned)members);
-  if constexpr (NS == 2 || NS == 3) {          // the backward runs on the layer's own split (bf16x3 / bf16x6)
-    if (bwd) {
-      if (!rowptr)
-        k_layer<FIN, FOUT, NS, BRMIN, true, true><<<grid, C::NWB * 64, 0, st>>>(
-            rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu, agg_out, mask, bsum_out, (int32_t)chunks_pm);
-      else
-        k_layer<FIN, FOUT, NS, BRMIN, false, true><<<grid, C::NWB * 64, 0, st>>>(
-            rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu, agg_out, mask, bsum_out, (int32_t)chunks_pm);
-      GWEN_LAUNCH_CHECK();
-      return GWEN_OK;
-    }
-  }
-  if (!rowptr)      // uniform layout: row r is the group at 8 r
-    k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D><<<grid, C::NWB * 64, 0, st>>>(
-        rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu);
-  else
-    k_layer<FIN, FOUT, NS, BRMIN, false, false, 8, D><<<grid, C::NWB * 64, 0, st>>>(
-        rowptr, col, val, x, W, bias, out, (int32_t)N, ldo, msx, mso, relu);
-  GWEN_LAUNCH_CHECK();
+  resident = (int64_t)256 * per_cu;
   return GWEN_OK;
 }
 
-// block_rows: 0 = the choice below; 64 / 96 / 112 / 128 (narrow layers, whole gather passes only) forces it
-template <int FIN, int FOUT, int NS, int GE = 8, int D = 1>
-int launch(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
-           const float *W, const float *bias, float *out, int64_t N, int64_t ldo, int64_t members,
-           int64_t msx, int64_t mso, int relu, hipStream_t st, float *agg_out = nullptr,
-           const float *mask = nullptr, bool bwd = false, float *bsum_out = nullptr, int64_t *chunks_out = nullptr,
-           int block_rows = 0) {
-#define GWEN_ROWS(BRV, PROBE, RES)                                                                  \
-  launch_rows<FIN, FOUT, NS, BRV, GE, D>(rowptr, col, val, x, W, bias, out, N, ldo, members, msx, mso, \
-                                         relu, st, PROBE, RES, agg_out, mask, bwd, bsum_out, chunks_out)
-  static_assert(GE == 8 || (FIN <= 64 && FOUT <= 64), "7 gathered entries: narrow layers only");
-  static_assert(D == 1 || (FIN <= 64 && FOUT <= 64), "gather depth 2: narrow layers only");
-  if constexpr (FIN <= 64 && FOUT <= 64) {
-    if (block_rows != 0) {
-      constexpr int RBF = Cfg<FIN, FOUT, NS, 64>::RB;
-      if (block_rows == 64) return GWEN_ROWS(64, false, nullptr);
-      if constexpr (96 % RBF == 0) { if (block_rows == 96) return GWEN_ROWS(96, false, nullptr); }
-      if constexpr (112 % RBF == 0) { if (block_rows == 112) return GWEN_ROWS(112, false, nullptr); }
-      if constexpr (128 % RBF == 0) { if (block_rows == 128) return GWEN_ROWS(128, false, nullptr); }
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D>
+int launch_rows(const LayerArgs &a) {
+  using C = Cfg<FIN, FOUT, NS, BRMIN>;
+  int64_t resident = 0;
+  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D>(resident); if (rc != GWEN_OK) return rc; }
+  int64_t blocks = (a.N + C::BR - 1) / C::BR;
+  const int64_t chunks_pm = blocks;                        // chunks of BR rows per member (bsum_out: one partial row each)
+  float *bsum_out = C::geo.wide ? nullptr : a.bsum_out;    // the persistent form: no fused column sums (see the kernel)
+  if (a.chunks_out) *a.chunks_out = C::geo.wide ? 0 : chunks_pm * a.members;
+  if (C::geo.wide && blocks > resident) blocks = resident; // wide layer: one resident set
+  dim3 grid((unsigned)blocks, (unsigned)a.members);
+  auto run = [&](auto kernel) {
+    kernel<<<grid, C::NWB * 64, 0, a.st>>>(a.rowptr, a.col, a.val, a.x, a.W, a.bias, a.out, (int32_t)a.N, a.ldo, a.msx,
+                                           a.mso, a.relu, a.agg_out, a.mask, bsum_out, (int32_t)chunks_pm);
+    GWEN_LAUNCH_CHECK();
+    return (int)GWEN_OK;
+  };
+  if (a.bwd) {                                 // the backward runs on the layer's own split (bf16x3 / bf16x6), GE = 8, D = 1
+    if constexpr ((NS == 2 || NS == 3) && GE == 8 && D == 1)
+      return a.rowptr ? run(&k_layer<FIN, FOUT, NS, BRMIN, false, true>) : run(&k_layer<FIN, FOUT, NS, BRMIN, true, true>);
+    else
       return GWEN_EINVAL;
-    }
+  }
+  // uniform layout (no rowptr): row r is the group at 8 r; only there may the 8th slot go ungathered (GE = 7)
+  return a.rowptr ? run(&k_layer<FIN, FOUT, NS, BRMIN, false, false, 8, D>)
+                  : run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D>);
+}
+
+// block_rows: 0 = the choice below; else forced (rows_ok, checked by the extern "C" caller)
+template <int FIN, int FOUT, int NS, int GE, int D>
+int launch(const LayerArgs &a, int block_rows) {
+  static_assert(GE == 8 || narrow(FIN, FOUT), "7 gathered entries: narrow layers only");
+  static_assert(D == 1 || narrow(FIN, FOUT), "gather depth 2: narrow layers only");
+  if constexpr (!narrow(FIN, FOUT)) {
+    return launch_rows<FIN, FOUT, NS, wide_brmin(FIN), GE, D>(a);
+  } else {
+    // f(BRV) for the block size br, where that size exists for this shape
+    auto with_rows = [&](int br, auto &&f) {
+      return gwen::dispatch(gwen::ints<64, 96, 112, 128>{}, br, [&](auto brv) {
+        if constexpr (rows_ok(FIN, FOUT, decltype(brv)::value)) return f(brv);
+        else return (int)GWEN_EINVAL;
+      });
+    };
     // Narrow layers run as ONE round of co-resident blocks when a block size makes that possible: with
     // 64-row blocks the c2 mesh needs 1 563 blocks against 1 024 resident ones (4 per CU at 64 -> 64),
     // i.e. a full round plus a half-empty one of ~10 us each; 112-row blocks (893 of them) fit one round.
-    // Rows per block: the smallest of 64 / 96 / 112 / 128 (whole gather passes only) whose grid is
-    // co-resident, else 64 -- at gather depth 2 else 112 where the width allows it: several rounds of blocks either
-    // way, and the two-deep gather fills and drains once per block, so the longest run of passes is the cheapest
-    // (64 -> 64 on the c2 mesh, bf16x6: 18.2 us against 18.9 at 64 rows; depth 1 the other way round, 19.8 / 19.2).
-    int64_t res = 0;
-    const int64_t work = N * members;
-    { const int rc_ = GWEN_ROWS(64, true, &res); if (rc_ != GWEN_OK) return rc_; }
-    if ((work + 63) / 64 <= res || members > 1) return GWEN_ROWS(64, false, nullptr);
-    constexpr int RB = Cfg<FIN, FOUT, NS, 64>::RB;      // a block is whole gather passes of RB rows
-    if constexpr (96 % RB == 0) {
-      { const int rc_ = GWEN_ROWS(96, true, &res); if (rc_ != GWEN_OK) return rc_; }
-      if ((N + 95) / 96 <= res) return GWEN_ROWS(96, false, nullptr);
+    // Rows per block: 64 when that grid is co-resident or there are several members; else the smallest of 96 / 112 /
+    // 128 (whole gather passes only) whose grid is co-resident; else 64 -- at gather depth 2 else 112 where the width
+    // allows it: several rounds of blocks either way, and the two-deep gather fills and drains once per block, so the
+    // longest run of passes is the cheapest (64 -> 64 on the c2 mesh, bf16x6: 18.2 us against 18.9 at 64 rows; depth 1
+    // the other way round, 19.8 / 19.2).
+    int rc = GWEN_OK, br = block_rows;
+    auto fits = [&](int c, int64_t work) {                 // the grid of c-row blocks is co-resident (or rc says why not)
+      int64_t res = 0;
+      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D>(res); });
+      return rc != GWEN_OK || (work + c - 1) / c <= res;
+    };
+    if (br == 0) {
+      br = D == 2 && rows_ok(FIN, FOUT, 112) ? 112 : 64;   // what is left when no size is co-resident
+      if (fits(64, a.N * a.members) || a.members > 1) {
+        br = 64;
+      } else {
+        for (int c : {96, 112, 128})
+          if (rows_ok(FIN, FOUT, c) && fits(c, a.N)) { br = c; break; }
+      }
+      if (rc != GWEN_OK) return rc;
     }
-    if constexpr (112 % RB == 0) {
-      { const int rc_ = GWEN_ROWS(112, true, &res); if (rc_ != GWEN_OK) return rc_; }
-      if ((N + 111) / 112 <= res) return GWEN_ROWS(112, false, nullptr);
-    }
-    if constexpr (128 % RB == 0) {
-      { const int rc_ = GWEN_ROWS(128, true, &res); if (rc_ != GWEN_OK) return rc_; }
-      if ((N + 127) / 128 <= res) return GWEN_ROWS(128, false, nullptr);
-    }
-    if constexpr (D == 2 && 112 % RB == 0) return GWEN_ROWS(112, false, nullptr);
-    return GWEN_ROWS(64, false, nullptr);
-  } else {
-    // rows per block: enough that W (read once per block) stays a small fraction of the gathered bytes
-    // 256: 64 rows keep two blocks per CU in LDS (bf16x3), and 64 rows at 256 channels on bf16x6 as well
-    constexpr int BRMIN = FIN == 128 ? 128 : 64;
-    if (block_rows != 0 && block_rows != Cfg<FIN, FOUT, NS, BRMIN>::BR) return GWEN_EINVAL;
-    return GWEN_ROWS(BRMIN, false, nullptr);
+    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D>(a); });
   }
-#undef GWEN_ROWS
 }
 
 constexpr bool width_ok(int64_t f) { return f == 16 || f == 32 || f == 64 || f == 128 || f == 256; }
+
+// f(FIN, FOUT, NS) as integral constants for a supported width pair and an image count of the list
+template <int... NSs, class F>
+int with_shape(int64_t Fin, int64_t Fout, gwen::ints<NSs...> images, int ns, F &&f) {
+  using Widths = gwen::ints<16, 32, 64, 128, 256>;
+  return gwen::dispatch(Widths{}, Fin, [&](auto fi) {
+    return gwen::dispatch(Widths{}, Fout, [&](auto fo) {
+      return gwen::dispatch(images, ns, [&](auto nsv) { return f(fi, fo, nsv); });
+    });
+  });
+}
 
 }  // namespace
 
@@ -399,25 +431,16 @@ extern "C" int gwen_gcn_layer_supported(int64_t Fin, int64_t Fout) {
 }
 
 // The library's gather depth per (Fin, Fout, images) on the uniform layout: 2 only where the kernel measured
-// faster on the MI355X (profiles/depth_*); the non-uniform layout and widths above 64 run depth 1.
+// faster on the MI355X ("Gather depth"; profiles/depth_*); the non-uniform layout and widths above 64 run
+// depth 1.
 static constexpr int layer_depth(int64_t fin, int64_t fout, int ns) {
-  return fin == 64 && fout == 64 && ns == 3 ? 2 : 1;     // 64 -> 64, bf16x6: 19.3 -> 18.3 us on the c2 mesh
-}
-
-// block_rows of gwen_gcn_layer_tuned_f32: 0; narrow layers: 64 / 96 / 112 / 128 that are whole gather passes; wide
-// layers: the kernel's one size (launch())
-static bool layer_rows_valid(int64_t Fin, int64_t Fout, int br) {
-  if (br == 0) return true;
-  const int64_t nj = Fout / 16, rb = (nj > 8 ? 16 : (nj > 4 ? 8 : 4)) * (64 / (Fin / 4));
-  if (Fin <= 64 && Fout <= 64) return (br == 64 || br == 96 || br == 112 || br == 128) && br % rb == 0;
-  const int64_t brmin = Fin == 128 ? 128 : 64;
-  return br == (rb > brmin ? rb : brmin);
+  return fin == 64 && fout == 64 && ns == 3 ? 2 : 1;     // 64 -> 64 on bf16x6
 }
 
 extern "C" int gwen_gcn_layer_depth(int64_t Fin, int64_t Fout, int exact) {
   if (!gwen_gcn_layer_supported(Fin, Fout) || exact < 0 || exact > 2) return 0;
-  if (Fin > 64 || Fout > 64) return 1;
-  return layer_depth(Fin, Fout, exact == GWEN_CONTRACT_F32 ? 0 : (exact == GWEN_CONTRACT_BF16X6 ? 3 : 2));
+  if (!narrow(Fin, Fout)) return 1;
+  return layer_depth(Fin, Fout, gwen::images_of(exact));
 }
 
 // entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
@@ -431,7 +454,8 @@ extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *co
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
-  if (!gwen_gcn_layer_supported(Fin, Fout) || !layer_rows_valid(Fin, Fout, block_rows)) return GWEN_EINVAL;
+  if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
+  if (block_rows != 0 && !rows_ok(Fin, Fout, block_rows)) return GWEN_EINVAL;   // the one check of block_rows
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || !W || !out || x == out) return GWEN_EINVAL;   // rowptr NULL = uniform
   if (N >= (int64_t(1) << 28) || members > 65535) return GWEN_ERANGE;     // 8 N must fit int32
@@ -439,54 +463,22 @@ extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *co
       mstride_x % 4 || ldo % 4 || mstride_o % 4 || (bias && !gwen_aligned(bias, 16)))
     return GWEN_EINVAL;                       // x rows must be contiguous (32-bit row offsets)
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
-  hipStream_t st = gwen_stream(stream_);
-  const bool narrow = Fin <= 64 && Fout <= 64;
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_layer_depth(Fin, Fout, exact);
-  if (!narrow) depth = 1;                     // the wide kernels have one depth
-  // narrow layers: GE (7 on the uniform layout when the caller promises it) x D
-#define GWEN_LN(FI, FO, GEV, DV)                                                                 \
-  if (Fin == FI && Fout == FO)                                                                   \
-    return exact == GWEN_CONTRACT_F32                                                            \
-               ? launch<FI, FO, 0, GEV, DV>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, mstride_o, \
-                                            relu, st, nullptr, nullptr, false, nullptr, nullptr, block_rows) \
-               : (exact == GWEN_CONTRACT_BF16X6                                                  \
-                      ? launch<FI, FO, 3, GEV, DV>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x,   \
-                                                   mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr,  \
-                                                   block_rows)                                   \
-                      : launch<FI, FO, 2, GEV, DV>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x,   \
-                                                   mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr,  \
-                                                   block_rows))
-#define GWEN_LNN(GEV, DV)                                                                        \
-  GWEN_LN(16, 16, GEV, DV); GWEN_LN(16, 32, GEV, DV); GWEN_LN(16, 64, GEV, DV);                  \
-  GWEN_LN(32, 16, GEV, DV); GWEN_LN(32, 32, GEV, DV); GWEN_LN(32, 64, GEV, DV);                  \
-  GWEN_LN(64, 16, GEV, DV); GWEN_LN(64, 32, GEV, DV); GWEN_LN(64, 64, GEV, DV)
-  if (narrow) {
-    const bool seven = entries == 7 && !rowptr;
-    if (seven && depth == 2) { GWEN_LNN(7, 2); }
-    if (seven) { GWEN_LNN(7, 1); }
-    if (depth == 2) { GWEN_LNN(8, 2); }
-    GWEN_LNN(8, 1);
-  }
-#undef GWEN_LNN
-#undef GWEN_LN
-#define GWEN_L(FI, FO)                                                                           \
-  if (Fin == FI && Fout == FO)                                                                   \
-    return exact == GWEN_CONTRACT_F32                                                            \
-               ? launch<FI, FO, 0>(rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, \
-                                   mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr, block_rows) \
-               : (exact == GWEN_CONTRACT_BF16X6                                                  \
-                      ? launch<FI, FO, 3>(rowptr, col, val, x, W, bias, out, N, ldo, members,    \
-                                          mstride_x, mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr, \
-                                          block_rows)                                            \
-                      : launch<FI, FO, 2>(rowptr, col, val, x, W, bias, out, N, ldo, members,    \
-                                          mstride_x, mstride_o, relu, st, nullptr, nullptr, false, nullptr, nullptr, \
-                                          block_rows))
-  GWEN_L(16, 128); GWEN_L(32, 128); GWEN_L(64, 128);
-  GWEN_L(128, 16); GWEN_L(128, 32); GWEN_L(128, 64); GWEN_L(128, 128);
-  GWEN_L(16, 256); GWEN_L(32, 256); GWEN_L(64, 256); GWEN_L(128, 256);
-  GWEN_L(256, 16); GWEN_L(256, 32); GWEN_L(256, 64); GWEN_L(256, 128); GWEN_L(256, 256);
-#undef GWEN_L
-  return GWEN_EINVAL;
+  const int ge = entries == 7 && !rowptr ? 7 : 8;          // 7 on the uniform layout when the caller promises it
+  const LayerArgs a{rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, mstride_o, relu, gwen_stream(stream_),
+                    nullptr, nullptr, nullptr, nullptr, false};
+  return with_shape(Fin, Fout, gwen::ints<0, 2, 3>{}, gwen::images_of(exact), [&](auto fi, auto fo, auto nsv) {
+    constexpr int FI = decltype(fi)::value, FO = decltype(fo)::value, NS = decltype(nsv)::value;
+    if constexpr (narrow(FI, FO)) {            // narrow layers: GE x D
+      return gwen::dispatch(gwen::ints<7, 8>{}, ge, [&](auto gev) {
+        return gwen::dispatch(gwen::ints<1, 2>{}, depth, [&](auto dv) {
+          return launch<FI, FO, NS, decltype(gev)::value, decltype(dv)::value>(a, block_rows);
+        });
+      });
+    } else {                                   // the wide kernels gather whole groups at one depth
+      return launch<FI, FO, NS, 8, 1>(a, block_rows);
+    }
+  });
 }
 
 extern "C" int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -532,22 +524,11 @@ extern "C" int gwen_gcn_layer_bwd_bias_f32(const int32_t *t_rowptr, const int32_
     return GWEN_EINVAL;
   if (N * Fg * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   if ((bias_partial != nullptr) != (bias_chunks != nullptr) || (bias_partial && !gwen_aligned(bias_partial, 16))) return GWEN_EINVAL;
-  hipStream_t st = gwen_stream(stream_);
-#define GWEN_L(FI, FO)                                                                           \
-  if (Fg == FI && Fx == FO)                                                                      \
-    return contract == GWEN_CONTRACT_BF16X6                                                      \
-               ? launch<FI, FO, 3>(t_rowptr, t_col, t_val, g, Wt, nullptr, gx, N, Fx, members,  \
-                                   N * Fg, N * Fx, 0, st, gh, mask, true, bias_partial, bias_chunks) \
-               : launch<FI, FO, 2>(t_rowptr, t_col, t_val, g, Wt, nullptr, gx, N, Fx, members,  \
-                                   N * Fg, N * Fx, 0, st, gh, mask, true, bias_partial, bias_chunks)
-  GWEN_L(16, 16); GWEN_L(16, 32); GWEN_L(16, 64); GWEN_L(16, 128);
-  GWEN_L(32, 16); GWEN_L(32, 32); GWEN_L(32, 64); GWEN_L(32, 128);
-  GWEN_L(64, 16); GWEN_L(64, 32); GWEN_L(64, 64); GWEN_L(64, 128);
-  GWEN_L(128, 16); GWEN_L(128, 32); GWEN_L(128, 64); GWEN_L(128, 128);
-  GWEN_L(16, 256); GWEN_L(32, 256); GWEN_L(64, 256); GWEN_L(128, 256);
-  GWEN_L(256, 16); GWEN_L(256, 32); GWEN_L(256, 64); GWEN_L(256, 128); GWEN_L(256, 256);
-#undef GWEN_L
-  return GWEN_EINVAL;
+  const LayerArgs a{t_rowptr, t_col, t_val, g, Wt, nullptr, gx, N, Fx, members, N * Fg, N * Fx, 0, gwen_stream(stream_),
+                    gh, mask, bias_partial, bias_chunks, true};
+  return with_shape(Fg, Fx, gwen::ints<2, 3>{}, gwen::images_of(contract), [&](auto fi, auto fo, auto nsv) {
+    return launch<decltype(fi)::value, decltype(fo)::value, decltype(nsv)::value, 8, 1>(a, 0);
+  });
 }
 
 extern "C" int gwen_gcn_layer_bwd_f32(const int32_t *t_rowptr, const int32_t *t_col, const float *t_val,
