@@ -5,7 +5,7 @@ UpConvLayers, GCNConvLayers, GNNModel, loss_func) plus the ``GCNConv`` layer it 
 torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); build it with
 ``python -m gwen_amd.build``.
 """
-from . import attention, checkpoint, forcings, forecaster, g2m, gridgraph, interaction, losses, noise, ops
+from . import attention, checkpoint, forcings, forecaster, g2m, gridgraph, interaction, loss_functions, losses, noise, ops
 from . import products, regrid
 from .attention import GraphTransformer, edge_attention, edge_attention_kv
 from .checkpoint import checkpointed_step
@@ -14,6 +14,7 @@ from .gcn_conv import GCNConv, Linear
 from .forecaster import InteractionForecaster
 from .interaction import EdgeGraph, InteractionNet, interaction_graph
 from .losses import EnsembleCRPSLoss, ensemble_crps, ensemble_scores
+from .loss_functions import CRPSLoss, EnsembleVarRegLoss, MaskedLoss
 from .noise import NoiseStream
 from .forcings import ForcingClock
 from .products import ensemble_products, ensemble_quantiles, exceedance_probability, rank_histogram
@@ -31,6 +32,6 @@ __all__ = [
     "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream", "GraphTransformer", "edge_attention", "edge_attention_kv",
     "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
     "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
-    "Regridder", "nearest_neighbours", "checkpointed_step",
+    "Regridder", "nearest_neighbours", "checkpointed_step", "CRPSLoss", "EnsembleVarRegLoss", "MaskedLoss",
 ]
 __version__ = "0.1.0"

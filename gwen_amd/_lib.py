@@ -88,6 +88,7 @@ KIND_PROPAGATE, KIND_LINEAR, KIND_LAYER, KIND_CHAIN, KIND_SMALL, KIND_WIDE = 2, 
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
 EW_MUL, EW_ADD = 0, 1
 MLP2_LN_EDGE, MLP2_LN_NODE = 0, 1                    # GWEN_MLP2_LN_* (include/gwen_hip.h)
+MASKED_L1, MASKED_MSE = 0, 1                         # GWEN_MASKED_* (include/gwen_hip.h)
 REGRID_NEAREST, REGRID_IDW = 0, 1                    # GWEN_REGRID_* (include/gwen_hip.h)
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
@@ -209,6 +210,13 @@ SIGNATURES = {
     "gwen_masked_l1_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "gwen_ens_crps_workspace_floats": (_i64, [_i64, _i64, _i64]),
     "gwen_ens_crps_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gwen_gauss_crps_workspace_floats": (_i64, [_i64, _i64, _i64, _i64]),
+    "gwen_gauss_crps_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "gwen_gauss_crps_bwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "gwen_varreg_l1_workspace_floats": (_i64, [_i64, _i64, _i64]),
+    "gwen_varreg_l1_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _int, _f32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "gwen_masked_mean_workspace_floats": (_i64, [_i64, _i64]),
+    "gwen_masked_mean_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "gwen_ens_products_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "gwen_ens_rank_hist_workspace_floats": (_i64, [_i64, _i64, _i64]),
     "gwen_ens_rank_hist_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp]),

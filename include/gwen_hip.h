@@ -732,6 +732,63 @@ int gwen_ens_crps_f32(const float *pred, const float *target, const float *node_
                       float *scores, float *workspace, int64_t workspace_floats, gwen_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The reference's ensemble losses (src/gwen/loss_functions.py), csrc/refloss.hip.  Everything is fp32, contiguous and
+ * 4-byte aligned; offsets are 64-bit; 16 bytes per lane when every tensor is 16-byte aligned and R (the masked mean:
+ * the element count, and inner for a row mask) is a multiple of 4, with the same bits as the 4-byte path.  No atomics,
+ * sums in a fixed order (two runs are bitwise equal); no allocation, no synchronisation (the launches capture into a
+ * hipGraph).  mu, sigma, z and the cdf stay in registers.  Errors come back before any HIP call: GWEN_EINVAL for a bad
+ * size, M outside its range, S not dividing R, a flag that is not 0 / 1, a missing or misaligned pointer, or a workspace
+ * shorter than the *_workspace_floats answer (0 for bad arguments); GWEN_ERANGE for more than 2^33 points A R (or
+ * elements outer inner) or more than 2^40 elements A M R.
+ *
+ * Gaussian CRPS (CRPSLoss): pred [A, M, R], members in the middle (A = 1: the reference's dim = 0), target [A, R],
+ * 2 <= M <= 256.  The A R points form consecutive samples of S points, S dividing R.  Per point, members x_1..x_M:
+ *     mu = (1/M) sum_i x_i,   s = sqrt(sum_i (x_i - mu)^2 / (M - 1)),   sigma = s + 1e-6,
+ *     z = (t - mu) / (sigma sqrt 2),   q = erf(z) / 2            (the normal cdf at t, minus 1/2)
+ *     loss[sample] = (1/S) sum over its points of q^2                                         loss: [A R / S]
+ * mu is evaluated as x_1 + (1/M) sum_i (x_i - x_1) (exact for identical members, no rounding of a common offset), and
+ * deviations are formed about mu in a second sweep, never as E[x^2] - mu^2.  The backward takes grad_loss [A R / S]:
+ *     c = grad_loss[sample] (2 q / S) exp(-z^2) / sqrt(pi)                                    (dL/dz)
+ *     grad_target = c / (sigma sqrt 2)
+ *     grad_pred_i = -c / (M sigma sqrt 2) - c (z / sigma) ds/dx_i,   ds/dx_i = (x_i - mu) / ((M - 1) s)
+ * and ds/dx_i = 0 WHERE s == 0 (identical members), as torch's std backward.  grad_pred or grad_target may be NULL, not
+ * both.  A NaN or Inf
+ * member or target makes its own sample non-finite and no other.  workspace: 2 ceil(A R / 1024) floats.  The forward
+ * reads pred once (above 32 members the second sweep reads the block's tile again), the backward reads it once and
+ * writes grad_pred once.
+ *
+ * Variance-regularised L1 (EnsembleVarRegLoss): pred [A, M, R], target [A, M, R] (target_broadcast = 0) or [A, 1, R]
+ * (1), M >= 1, value and gradients from one pass and a one-block finish:
+ *     loss[0] = sum |x - t| / (A M R) - alpha sum_points var(x) / (A R),   var unbiased over the members
+ *     grad_pred = sign(x - t) / (A M R) - alpha 2 (x_i - mu) / ((M - 1) A R)                  (sign(0) = 0)
+ *     grad_target = -sign(x - t) / (A M R), summed over the members when the target is broadcast
+ * grad_pred and grad_target may be NULL.  M = 1 gives NaN (value and grad_pred), as the expression does.
+ * workspace: 2 ceil(A R / 1024) floats.
+ *
+ * Masked mean (MaskedLoss): out, target [outer, inner]; mask [inner] (mask_full = 0) or [outer, inner] (1), fp32;
+ * kind GWEN_MASKED_L1: l = |out - target|, GWEN_MASKED_MSE: l = (out - target)^2:
+ *     loss[0] = sum l mask / sum mask,     grad_out = l' mask / sum mask,     grad_target = -grad_out
+ * where sum mask is the sum of the mask AS GIVEN ([inner] values when mask_full = 0), not of its broadcast: the
+ * reference's expression.  An all-zero mask gives NaN, value and gradients.  grad_out and grad_target may be NULL.
+ * workspace: 1025 + ceil(outer inner / 1024) floats.
+ * ------------------------------------------------------------------------------------------- */
+#define GWEN_MASKED_L1 0
+#define GWEN_MASKED_MSE 1
+int64_t gwen_gauss_crps_workspace_floats(int64_t A, int64_t M, int64_t R, int64_t S);
+int gwen_gauss_crps_f32(const float *pred, const float *target, int64_t A, int64_t M, int64_t R, int64_t S,
+                        float *loss, float *workspace, int64_t workspace_floats, gwen_stream_t stream);
+int gwen_gauss_crps_bwd_f32(const float *grad_loss, const float *pred, const float *target, int64_t A, int64_t M,
+                            int64_t R, int64_t S, float *grad_pred, float *grad_target, gwen_stream_t stream);
+int64_t gwen_varreg_l1_workspace_floats(int64_t A, int64_t M, int64_t R);
+int gwen_varreg_l1_f32(const float *pred, const float *target, int64_t A, int64_t M, int64_t R, int target_broadcast,
+                       float alpha, float *grad_pred, float *grad_target, float *loss, float *workspace,
+                       int64_t workspace_floats, gwen_stream_t stream);
+int64_t gwen_masked_mean_workspace_floats(int64_t outer, int64_t inner);
+int gwen_masked_mean_f32(const float *out, const float *target, const float *mask, int64_t outer, int64_t inner,
+                         int mask_full, int kind, float *grad_out, float *grad_target, float *loss, float *workspace,
+                         int64_t workspace_floats, gwen_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ensemble products over the members axis (csrc/products.hip): per-point mean, spread, quantiles and exceedance
  * probabilities in ONE launch that reads every point once.  BUILD-DEFINED (the reference has none of these).
  * pred fp32 [M, N, C] (members first, contiguous), 1 <= M <= 64, N >= 1, C >= 1.  Every output is optional (NULL = not
