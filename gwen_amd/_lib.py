@@ -124,6 +124,9 @@ SIGNATURES = {
     "gwen_gcn_layer_tuned_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                         _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp]),
     "gwen_gcn_layer_depth": (_int, [_i64, _i64, _int]),
+    "gwen_gcn_layer_tuned2_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp]),
+    "gwen_gcn_layer_index_mode": (_int, [_i64, _i64, _int]),
     "gwen_gcn_layer_supported": (_int, [_i64, _i64]),
     "gwen_gcn_chain_supported": (_int, [_i64, _i64, _i64, _int, _int]),
     "gwen_gcn_chain_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
@@ -133,6 +136,9 @@ SIGNATURES = {
     "gwen_gcn_chain_tuned_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                         _int, _i64, _i64, _i64, _int, _int, _int, _int, _vp]),
     "gwen_gcn_chain_depth": (_int, [_i64, _i64, _i64, _int, _int]),
+    "gwen_gcn_chain_tuned2_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
+                                         _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp]),
+    "gwen_gcn_chain_index_mode": (_int, [_i64, _i64, _i64, _int, _int]),
     "gwen_gcn_tiles64_count": (_i64, [_i64]),
     "gwen_gcn_tiles64": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gwen_cluster_rows64_host": (_int, [_vp, _vp, _i64, _i64, _vp]),

@@ -134,15 +134,16 @@ constexpr bool chain_pin(int fin, int f1, int f2, int ns, int ge) {
 }
 
 // GE: gathered entries per group (gather_rows.h; 7 only on the uniform layout).  D: gather depth (gather_rows.h).
-// BRQ: Cfg's.  They sit before NS because profile tooling keys this kernel's name on its first and its last
-// template argument.
-template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int NS>
+// BRQ: Cfg's.  IM: index mode (gather_rows.h; 2 = index records: narrow kernels on the uniform layout only).  They sit
+// before NS because profile tooling keys this kernel's name on its first and its last template argument.
+template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int IM, int NS>
 __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W1,
     const float *__restrict__ W2, const float *__restrict__ bias, float *__restrict__ out, int32_t N,
     int64_t mstride_x, int64_t mstride_o, int relu) {
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
+  static_assert(IM == 1 || (IM == 2 && UNI && FIN <= 64 && F1 <= 64), "index records: narrow kernels, uniform layout");
   __shared__ __attribute__((aligned(16))) __bf16 lds[C::lds_elems];
   constexpr int kImg0 = C::BR * C::PB0, kImg1 = C::BR * C::PB1;
   __bf16 *t0 = lds;                                                      // aggregated rows: NS x [BR][PB0]
@@ -201,7 +202,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
 #pragma unroll
         for (int s = 0; s < NS; ++s) *reinterpret_cast<bf16x4 *>(t0 + s * kImg0 + lr * C::PB0 + gl * 4) = im[s];
       };
-  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink, split_w);
+  gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D, IM>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink, split_w);
   __syncthreads();
 
   // ---- phase 2: first contraction; result to global (F2 == 0) or to the second LDS image ----------
@@ -269,7 +270,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
 // Activation-first layer with nothing chained: out = act(A~ h + bias) on the grouped layout (the
 // fma form of K2; K2 itself keeps the rounded-product order that is bit-identical to the CPU path).
 // D: accepted for symmetry with K4 / K5 -- a wave gathers ONE pass here, so both depths are the same code
-template <int FIN, bool UNI, int GE = 8, int D = 1>
+template <int FIN, bool UNI, int GE = 8, int D = 1, int IM = 1>
 __global__ __launch_bounds__(256) void k_gather(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ bias,
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(256) void k_gather(
   const float4_t braw = *reinterpret_cast<const float4_t *>(bias ? reinterpret_cast<const char *>(bias) + lane_off
                                                                  : xb + lane_off);
   __builtin_amdgcn_sched_barrier(0);
-  gwen::gather_passes<FIN, 1, BR, UNI, GE, D>(
+  gwen::gather_passes<FIN, 1, BR, UNI, GE, D, IM>(
       rowptr, col, val, xb, N, lb * BR, wave, gr, lane_off, [&](int lr, float4_t acc) {
         if (bias) acc = acc + braw;
         if (relu) {
@@ -329,7 +330,7 @@ constexpr bool rows_valid(int fin, int f1, bool plain, int br) {
 }
 
 // gathered entries: 7 only on the uniform layout, when the caller promises it, on widths up to 64
-template <int FIN, int D>
+template <int FIN, int D, int IM>
 int launch_gather(const ChainArgs &a) {
   constexpr int BR = gather_rows(FIN);
   dim3 grid((unsigned)((a.N + BR - 1) / BR), (unsigned)a.members);
@@ -338,6 +339,10 @@ int launch_gather(const ChainArgs &a) {
     GWEN_LAUNCH_CHECK();
     return (int)GWEN_OK;
   };
+  if constexpr (IM == 2) {                     // index records: the uniform layout, up to 64 channels
+    if (a.rowptr) return GWEN_EINVAL;
+    return a.entries == 7 ? run(&k_gather<FIN, true, 7, D, 2>) : run(&k_gather<FIN, true, 8, D, 2>);
+  }
   if (a.rowptr) return run(&k_gather<FIN, false, 8, D>);
   if constexpr (FIN <= 64) {
     if (a.entries == 7) return run(&k_gather<FIN, true, 7, D>);
@@ -345,7 +350,7 @@ int launch_gather(const ChainArgs &a) {
   return run(&k_gather<FIN, true, 8, D>);
 }
 
-template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ>
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ, int IM>
 int launch_br(const ChainArgs &a) {
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
   static_assert(C::geo.fits(kLdsCU), "one block must fit a CU's LDS");
@@ -356,11 +361,16 @@ int launch_br(const ChainArgs &a) {
     GWEN_LAUNCH_CHECK();
     return (int)GWEN_OK;
   };
-  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, NS>);
-  if constexpr (narrow(FIN, F1)) {
-    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, NS>);
+  if constexpr (IM == 2) {                     // index records: the uniform layout, narrow kernels
+    if (a.rowptr) return GWEN_EINVAL;
+    return a.entries == 7 ? run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 2, NS>)
+                          : run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 2, NS>);
   }
-  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, NS>);
+  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, 1, NS>);
+  if constexpr (narrow(FIN, F1)) {
+    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 1, NS>);
+  }
+  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 1, NS>);
 }
 
 // block_rows: 0 = the library's choice; else the kernel's own size or 96 / 112 (rows_ok; checked by the extern "C" caller).
@@ -369,19 +379,21 @@ int launch_br(const ChainArgs &a) {
 // 893 blocks) and 96 / 112 rows measured SLOWER at depth 1 (23.3 / 23.5 against 22.2 us), so depth 1 keeps 64.  At depth
 // 2 one member whose 64-row grid is more than one resident round runs 112-row blocks where the width allows it: the
 // two-deep gather fills and drains once per block (20.1 against 20.8 us).
-template <int FIN, int F1, int F2, bool PRE, int NS, int D>
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int IM>
 int launch_ns(const ChainArgs &a, int block_rows) {
+  static_assert(IM == 1 || narrow(FIN, F1), "index records: narrow kernels only");
   int brq = block_rows == 0 || block_rows == Cfg<FIN, F1, F2, PRE, NS>::BR ? 64 : block_rows;   // BRQ 64 = the own size
   if constexpr (D == 2 && rows_ok(FIN, F1, 112)) {
     if (block_rows == 0 && a.members == 1) {
       // blocks per CU of the 64-row kernel this call would launch otherwise; probed once per kernel (function-local
-      // static): a warm call makes no HIP query, so the launcher stays capturable
+      // static): a warm call makes no HIP query, so the launcher stays capturable.  The index mode is part of the
+      // kernel (IM = 2 exists on the uniform layout only; launch_br refuses a row pointer)
       static int per_cu[3] = {0, 0, 0};
       const int v = a.rowptr ? 2 : (a.entries == 7 ? 0 : 1);
       if (per_cu[v] == 0) {
-        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, NS>)
-                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, NS>)
-                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, NS>);
+        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, 1, NS>)
+                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, IM, NS>)
+                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, IM, NS>);
         int nbk = 0;
         GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k, Cfg<FIN, F1, F2, PRE, NS>::NWB * 64, 0));
         per_cu[v] = nbk < 1 ? 1 : nbk;
@@ -391,7 +403,7 @@ int launch_ns(const ChainArgs &a, int block_rows) {
   }
   return gwen::dispatch(gwen::ints<64, 96, 112>{}, brq, [&](auto brv) {
     constexpr int BRQ = decltype(brv)::value;
-    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ>(a);
+    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ, IM>(a);
     else return (int)GWEN_EINVAL;
   });
 }
@@ -423,20 +435,37 @@ extern "C" int gwen_gcn_chain_depth(int64_t Fin, int64_t F1, int64_t F2, int pre
   return chain_depth(Fin, F1, F2, gwen::images_of(contract));
 }
 
+// The library's index mode per (Fin, F1, F2, pre, images) on the uniform layout (gather_rows.h, IM): 2, one record load
+// per row and pass, only where the kernel measured faster on the MI355X ("Index records";
+// profiles/index_*); the non-uniform layout and widths above 64 have mode 1 only.
+static constexpr int chain_index_mode(int64_t fin, int64_t f1, int64_t f2, int pre, int ns) {
+  return fin == 32 && f1 == 16 && f2 == 0 && pre && ns == 3 ? 2 : 1;   // activation-first 32 -> 16 on bf16x6
+}
+
+extern "C" int gwen_gcn_chain_index_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract) {
+  if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return 0;
+  if (!narrow(Fin, F1)) return 1;
+  return chain_index_mode(Fin, F1, F2, pre, gwen::images_of(contract));
+}
+
 // entries = 7: the caller's promise (uniform layout, every row at most 7 stored entries), see gwen_gcn_layer_entries_f32
-// depth, block_rows: 0 = the library's choice (chain_depth; launch_ns); neither changes a value
-extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                        const float *x, const float *W1, const float *W2,
-                                        const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
-                                        int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
-                                        int64_t mstride_o, int contract, int entries, int depth, int block_rows,
-                                        gwen_stream_t stream_) {
+// depth, block_rows, index_mode: 0 = the library's choice (chain_depth; launch_ns; chain_index_mode); none changes a
+// value.  index_mode 1: every lane loads its row's group; 2: index records -- narrow kernels (Fin, F1 <= 64) on the
+// uniform layout only, GWEN_EINVAL elsewhere
+extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W1, const float *W2,
+                                         const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                         int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                         int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                         int index_mode, gwen_stream_t stream_) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
+  if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0) return GWEN_EINVAL;
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return GWEN_EINVAL;
   const bool plain = pre && F1 == 0;                       // activation-first, nothing chained: k_gather
   if (!rows_valid(Fin, F1, plain, block_rows)) return GWEN_EINVAL;             // the one check of block_rows
+  if (index_mode == 2 && (rowptr || !narrow(Fin, F1))) return GWEN_EINVAL;     // records: uniform layout, narrow kernels
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || (F1 > 0 && !W1) || !out || x == out || (F2 > 0 && !W2))
     return GWEN_EINVAL;                                    // rowptr NULL = uniform layout
@@ -446,16 +475,21 @@ extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *co
     return GWEN_EINVAL;
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_chain_depth(Fin, F1, F2, pre, contract);
+  if (index_mode == 0) index_mode = rowptr ? 1 : gwen_gcn_chain_index_mode(Fin, F1, F2, pre, contract);
   const ChainArgs a{rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, mstride_o, relu, entries,
                     gwen_stream(stream_)};
   using Widths = gwen::ints<16, 32, 64, 128>;
   using Depths = gwen::ints<1, 2>;
+  using Modes = gwen::ints<1, 2>;
   return gwen::dispatch(Widths{}, Fin, [&](auto fi) {
     constexpr int FI = decltype(fi)::value;
     if (plain) {
       return gwen::dispatch(Depths{}, FI <= 64 ? depth : 1, [&](auto dv) {         // gather depth 2: up to 64 channels
-        if constexpr (FI <= 64 || decltype(dv)::value == 1) return launch_gather<FI, decltype(dv)::value>(a);
-        else return (int)GWEN_EINVAL;
+        return gwen::dispatch(Modes{}, index_mode, [&](auto iv) {
+          constexpr int D = decltype(dv)::value, IM = decltype(iv)::value;
+          if constexpr (FI <= 64 || (D == 1 && IM == 1)) return launch_gather<FI, D, IM>(a);
+          else return (int)GWEN_EINVAL;
+        });
       });
     }
     return gwen::dispatch(Widths{}, F1, [&](auto fa) {
@@ -467,12 +501,14 @@ extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *co
           if constexpr (PRE ? FB == 0 : (FB > 0 && FB < FA)) {
             return gwen::dispatch(gwen::ints<2, 3>{}, gwen::images_of(contract), [&](auto nsv) {
               return gwen::dispatch(Depths{}, narrow(FI, FA) ? depth : 1, [&](auto dv) {   // depth 2: narrow only
-                constexpr int NS = decltype(nsv)::value, D = decltype(dv)::value;
-                // bf16x6 only where its three images fit a CU's LDS (gwen_gcn_chain_supported refuses the others)
-                if constexpr (Geom(FI, FA, FB, NS, 64).fits(kLdsCU) && (D == 1 || narrow(FI, FA)))
-                  return launch_ns<FI, FA, FB, PRE, NS, D>(a, block_rows);
-                else
-                  return (int)GWEN_EINVAL;
+                return gwen::dispatch(Modes{}, index_mode, [&](auto iv) {                  // records: narrow only
+                  constexpr int NS = decltype(nsv)::value, D = decltype(dv)::value, IM = decltype(iv)::value;
+                  // bf16x6 only where its three images fit a CU's LDS (gwen_gcn_chain_supported refuses the others)
+                  if constexpr (Geom(FI, FA, FB, NS, 64).fits(kLdsCU) && ((D == 1 && IM == 1) || narrow(FI, FA)))
+                    return launch_ns<FI, FA, FB, PRE, NS, D, IM>(a, block_rows);
+                  else
+                    return (int)GWEN_EINVAL;
+                });
               });
             });
           } else {
@@ -482,6 +518,16 @@ extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *co
       });
     });
   });
+}
+
+extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                        const float *x, const float *W1, const float *W2,
+                                        const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                        int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                        int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                        gwen_stream_t stream_) {
+  return gwen_gcn_chain_tuned2_f32(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members,
+                                   mstride_x, mstride_o, contract, entries, depth, block_rows, 0, stream_);
 }
 
 extern "C" int gwen_gcn_chain_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,

@@ -33,8 +33,19 @@
 // The order is pinned with sched_barrier.  With a shadow the depth-1 loop has its first pass peeled (the callable
 // must not sit under a condition inside the rolled loop); NoShadow keeps the loop exactly as it was -- the persistent
 // wide kernels and the backward compile to the code they had.
+// IM: how a pass's indices and weights reach its lanes (index mode).  1: every lane of the FIN/4 that share a destination
+// row loads the row's whole group itself -- 32 B of col and 32 B of val, four 16-B loads per lane and pass for 64 unique
+// bytes per row.  2 (uniform layout only): the "record" form.  The row's record is [col[s .. s+7] | val[s .. s+7]]; lane
+// gl of the row's G = FIN/4 lanes loads only its 64/G-byte share of it with ONE load per pass (dword / dwordx2 /
+// dwordx4 at G = 16 / 8 / 4; the lower half of the lanes from col + s, the upper half from val + s: the base pointer is
+// selected per lane, the load stays unconditional, absent rows read the null group), and the indices and weights are
+// broadcast inside the lane group without memory (group_bcast).  The weights are broadcast at consume time from the
+// kept record, so a pass in flight holds the record (1, 2 or 4 registers), not 8 registers of weights.  Issue order,
+// vmcnt order, the shadow's place and the arithmetic -- the same fma chain over the slots in slot order -- are those of
+// IM = 1 with "record" for "indices": every value is bitwise the same.  IM = 1 compiles to the code it had.
 #pragma once
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 
@@ -117,12 +128,76 @@ __device__ __forceinline__ float4_t masked_f4(float4_t v, bool keep) {
   return __builtin_bit_cast(float4_t, __builtin_bit_cast(u4, v) & u4{m, m, m, m});
 }
 
+// The record form (IM = 2): a lane's share of its row's record, DW = 16 / G dwords
+typedef uint32_t uint2_u __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t uint4_u __attribute__((ext_vector_type(4), aligned(4)));
+template <int DW> struct Record;
+template <> struct Record<1> {
+  using T = uint32_t;
+  static __device__ __forceinline__ uint32_t get(const T &r, int) { return r; }
+};
+template <> struct Record<2> {
+  using T = uint2_u;
+  static __device__ __forceinline__ uint32_t get(const T &r, int i) { return r[i]; }
+};
+template <> struct Record<4> {
+  using T = uint4_u;
+  static __device__ __forceinline__ uint32_t get(const T &r, int i) { return r[i]; }
+};
+
+// v of lane SRC of this lane's group of G consecutive lanes (G = 4, 8, 16: inside the 32 lanes of a swizzle), in
+// every lane of the group: ds_swizzle in bit-mask mode, lane' = (lane & ~(G - 1)) | SRC.  No LDS memory is touched.
+template <int G, int SRC>
+__device__ __forceinline__ uint32_t group_bcast(uint32_t v) {
+  static_assert((G == 4 || G == 8 || G == 16) && SRC >= 0 && SRC < G, "a lane group inside a swizzle group");
+  return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (~(G - 1) & 31) | (SRC << 5));
+}
+
+// slots 0 .. GE-1 of one half of the record (FIRST = 0: the column indices, G / 2: the weights), broadcast to the group
+template <int G, int FIRST, int... U>
+__device__ __forceinline__ void record_slots(const typename Record<16 / G>::T &rec, uint32_t (&o)[sizeof...(U)],
+                                             std::integer_sequence<int, U...>) {
+  constexpr int DW = 16 / G;
+  ((o[U] = group_bcast<G, FIRST + U / DW>(Record<DW>::get(rec, U % DW))), ...);
+}
+
+// the row loads of a pass from its record, and -- later -- its FMAs with the weights of the kept record: issue_group and
+// fma_group of the record form, slot for slot
+template <int FIN, int GE>
+__device__ __forceinline__ void issue_record(const char *xb, uint32_t lane_off,
+                                             const typename Record<64 / FIN>::T &rec, float4_t (&v)[GE]) {
+  constexpr uint32_t kRowBytes = FIN * 4;
+  static_assert(GE == 7 || GE == 8, "a group is gathered whole or without its last slot");
+  uint32_t c[GE];
+  record_slots<FIN / 4, 0>(rec, c, std::make_integer_sequence<int, GE>{});
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {                            // issue_group's order of slots: 0, 4, 1, 5, ...
+    v[u] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)(c[u] * kRowBytes + lane_off));
+    if (u + 4 < GE)
+      v[u + 4] = *reinterpret_cast<const float4_t *>(xb + (uint64_t)(c[u + 4] * kRowBytes + lane_off));
+  }
+}
+
+template <int FIN, int GE>
+__device__ __forceinline__ float4_t fma_record(const float4_t (&v)[GE], const typename Record<64 / FIN>::T &rec,
+                                               float4_t acc) {
+  uint32_t wb[GE];
+  record_slots<FIN / 4, FIN / 8>(rec, wb, std::make_integer_sequence<int, GE>{});
+#pragma unroll
+  for (int u = 0; u < GE; ++u) {
+    const float w = __builtin_bit_cast(float, wb[u]);
+    acc = __builtin_elementwise_fma(float4_t{w, w, w, w}, v[u], acc);
+  }
+  return acc;
+}
+
 struct NoShadow {
   __device__ __forceinline__ void operator()() const {}
 };
 
 // sink(lr, acc): lr = row index inside the block (p * RB + wave * R + gr), acc = aggregated 4 floats
-template <int FIN, int NP, int RB, bool UNI, int GE = 8, int D = 1, typename Sink, typename Shadow = NoShadow>
+template <int FIN, int NP, int RB, bool UNI, int GE = 8, int D = 1, int IM = 1, typename Sink,
+          typename Shadow = NoShadow>
 __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
                                      const int32_t *__restrict__ col,
                                      const float *__restrict__ val, const char *xb, int32_t N,
@@ -145,6 +220,87 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
     }
   };
   static_assert(D == 1 || D == 2, "one or two passes of row loads in flight");
+  static_assert(IM == 1 || (IM == 2 && UNI && FIN <= 64), "the record form: uniform layout, up to 64 channels");
+  if constexpr (IM == 2) {
+    constexpr int G = FIN / 4, DW = 16 / G;
+    using Rec = typename Record<DW>::T;
+    // this lane's share of the record of pass p: lanes 0 .. G/2-1 of the row read col + s, the others val + s
+    const uint32_t gl = lane_off / 16;
+    const char *half = (gl < G / 2 ? reinterpret_cast<const char *>(col) : reinterpret_cast<const char *>(val)) +
+                       (gl % (G / 2)) * (4 * DW);
+    auto request = [&](int p) {
+      int32_t s, rb;
+      locate(p, s, rb);
+      const Rec r = *reinterpret_cast<const Rec *>(half + (int64_t)s * 4);
+      __builtin_amdgcn_sched_barrier(0);
+      return r;
+    };
+    if constexpr (D == 2 && NP > 1) {
+      struct Buf {
+        Rec rec, irec;                                     // requested; of the pass whose rows are in v
+        float4_t v[GE];
+      };
+      auto issue = [&](Buf &b) {
+        b.irec = b.rec;
+        issue_record<FIN, GE>(xb, lane_off, b.rec, b.v);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      auto consume = [&](int p, const Buf &b) {
+        sink(p * RB + wave * R + gr, fma_record<FIN, GE>(b.v, b.irec, float4_t{0.f, 0.f, 0.f, 0.f}));
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      Buf A, B;                                            // the loop of IM = 1 below, step for step
+      A.rec = request(0);
+      B.rec = request(1);
+      issue(A);
+      if constexpr (kShadow) {
+        shadow();
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      auto step = [&](int q, Buf &X, Buf &Y) {
+        X.rec = request(q + 2);
+        issue(Y);
+        consume(q, X);
+      };
+#pragma unroll 1
+      for (int p = 0; p + 3 < NP; p += 2) {
+        step(p, A, B);
+        step(p + 1, B, A);
+      }
+      if constexpr (NP % 2 == 1) {
+        step(NP - 3, A, B);
+        issue(A);
+        consume(NP - 2, B);
+        consume(NP - 1, A);
+      } else {
+        issue(B);
+        consume(NP - 2, A);
+        consume(NP - 1, B);
+      }
+    } else {
+      // depth 1: the next pass's record is requested before this pass's row loads are waited for
+      Rec rec = request(0);
+      auto pass = [&](int p, bool more, auto &&between) {
+        Rec nrec = rec;
+        if (more) nrec = request(p + 1);
+        float4_t v[GE];
+        issue_record<FIN, GE>(xb, lane_off, rec, v);
+        __builtin_amdgcn_sched_barrier(0);
+        between();
+        sink(p * RB + wave * R + gr, fma_record<FIN, GE>(v, rec, float4_t{0.f, 0.f, 0.f, 0.f}));
+        rec = nrec;
+      };
+      if constexpr (kShadow) {
+        pass(0, NP > 1, [&]() {
+          shadow();
+          __builtin_amdgcn_sched_barrier(0);
+        });
+      }
+#pragma unroll 1
+      for (int p = kShadow ? 1 : 0; p < NP; ++p) pass(p, p + 1 < NP, []() {});
+    }
+    return;
+  }
   if constexpr (D == 2 && NP > 1) {
     using Buf = GatherBuf<GE>;
     auto request = [&](int p, Buf &b) {                    // indices of pass p

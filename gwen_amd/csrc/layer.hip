@@ -99,7 +99,9 @@ constexpr bool layer_prologue(int fin, int fout, int ns) { return !(fin == 16 &&
 // returns the gradient the next backward launch starts from.
 // GE: gathered entries per group (gather_rows.h); 7 only on the uniform layout.
 // D: gather depth (gather_rows.h): passes of row loads a wave keeps in flight; the backward runs D = 1.
-template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1>
+// IM: index mode (gather_rows.h): 2 = one record load per row and pass, broadcast in the lane group; narrow forward
+// kernels on the uniform layout only.  The last argument, so that every other kernel keeps its name but for a ", 1".
+template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1, int IM = 1>
 __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void k_layer(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W,
@@ -107,6 +109,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
     int64_t mstride_x, int64_t mstride_o, int relu, float *__restrict__ agg_out = nullptr,
     const float *__restrict__ mask = nullptr, float *__restrict__ bsum_out = nullptr, int32_t chunks_per_member = 0) {
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
+  static_assert(IM == 1 || (IM == 2 && UNI && !BWD && FIN <= 64 && FOUT <= 64), "index records: narrow forward, uniform layout");
   constexpr bool SPLIT = NS > 0;
   constexpr int NI = SPLIT ? NS : 1;
   __shared__ __attribute__((aligned(16))) char lds_raw[C::lds_bytes];
@@ -219,9 +222,9 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
         }
       };
   if constexpr (kOnce)
-    gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink, split_w);
+    gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D, IM>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink, split_w);
   else
-    gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink);
+    gwen::gather_passes<FIN, C::NP, C::RB, UNI, GE, D, IM>(rowptr, col, val, xb, N, b0, wave, gr, lane_off, sink);
   __syncthreads();
 
   // ---- phase 2: (tile) x (this wave's 16 columns of W^T), bias, ReLU, store ----------------------
@@ -326,13 +329,14 @@ constexpr bool rows_ok(int fin, int fout, int br) {
 // Blocks of this instantiation that are resident at once.  Probed once per instantiation (function-local static): a warm
 // call makes no HIP query, so the launchers stay capturable.  The UNIFORM kernel is probed whichever layout is launched:
 // the block-rows choice of launch() on a non-uniform layout has always been made with the uniform kernel's occupancy.
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D>
+// The index mode is part of the instantiation: a record kernel holds fewer registers.
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM>
 int resident_blocks(int64_t &resident) {
   static int per_cu = 0;
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D>),
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM>),
         Cfg<FIN, FOUT, NS, BRMIN>::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
@@ -340,11 +344,11 @@ int resident_blocks(int64_t &resident) {
   return GWEN_OK;
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM>
 int launch_rows(const LayerArgs &a) {
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
   int64_t resident = 0;
-  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D>(resident); if (rc != GWEN_OK) return rc; }
+  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM>(resident); if (rc != GWEN_OK) return rc; }
   int64_t blocks = (a.N + C::BR - 1) / C::BR;
   const int64_t chunks_pm = blocks;                        // chunks of BR rows per member (bsum_out: one partial row each)
   float *bsum_out = C::geo.wide ? nullptr : a.bsum_out;    // the persistent form: no fused column sums (see the kernel)
@@ -357,6 +361,10 @@ int launch_rows(const LayerArgs &a) {
     GWEN_LAUNCH_CHECK();
     return (int)GWEN_OK;
   };
+  if constexpr (IM == 2) {                     // index records: the forward on the uniform layout, nothing else
+    if (a.bwd || a.rowptr) return GWEN_EINVAL;
+    return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, 2>);
+  }
   if (a.bwd) {                                 // the backward runs on the layer's own split (bf16x3 / bf16x6), GE = 8, D = 1
     if constexpr ((NS == 2 || NS == 3) && GE == 8 && D == 1)
       return a.rowptr ? run(&k_layer<FIN, FOUT, NS, BRMIN, false, true>) : run(&k_layer<FIN, FOUT, NS, BRMIN, true, true>);
@@ -369,12 +377,13 @@ int launch_rows(const LayerArgs &a) {
 }
 
 // block_rows: 0 = the choice below; else forced (rows_ok, checked by the extern "C" caller)
-template <int FIN, int FOUT, int NS, int GE, int D>
+template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1>
 int launch(const LayerArgs &a, int block_rows) {
   static_assert(GE == 8 || narrow(FIN, FOUT), "7 gathered entries: narrow layers only");
+  static_assert(IM == 1 || narrow(FIN, FOUT), "index records: narrow layers only");
   static_assert(D == 1 || narrow(FIN, FOUT), "gather depth 2: narrow layers only");
   if constexpr (!narrow(FIN, FOUT)) {
-    return launch_rows<FIN, FOUT, NS, wide_brmin(FIN), GE, D>(a);
+    return launch_rows<FIN, FOUT, NS, wide_brmin(FIN), GE, D, 1>(a);
   } else {
     // f(BRV) for the block size br, where that size exists for this shape
     auto with_rows = [&](int br, auto &&f) {
@@ -394,7 +403,7 @@ int launch(const LayerArgs &a, int block_rows) {
     int rc = GWEN_OK, br = block_rows;
     auto fits = [&](int c, int64_t work) {                 // the grid of c-row blocks is co-resident (or rc says why not)
       int64_t res = 0;
-      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D>(res); });
+      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM>(res); });
       return rc != GWEN_OK || (work + c - 1) / c <= res;
     };
     if (br == 0) {
@@ -407,7 +416,7 @@ int launch(const LayerArgs &a, int block_rows) {
       }
       if (rc != GWEN_OK) return rc;
     }
-    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D>(a); });
+    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM>(a); });
   }
 }
 
@@ -443,19 +452,37 @@ extern "C" int gwen_gcn_layer_depth(int64_t Fin, int64_t Fout, int exact) {
   return layer_depth(Fin, Fout, gwen::images_of(exact));
 }
 
+// The library's index mode per (Fin, Fout, images) on the uniform layout (gather_rows.h, IM): 2, one record load per row
+// and pass, only where the kernel measured faster on the MI355X ("Index records"; profiles/index_*); the
+// non-uniform layout, the backward and widths above 64 have mode 1 only.
+static constexpr int layer_index_mode(int64_t fin, int64_t fout, int ns) {
+  return (fin == 64 || fin == 32) && fout == 64 && ns == 3 ? 2 : 1;   // 64 -> 64 and 32 -> 64 on bf16x6
+}
+
+extern "C" int gwen_gcn_layer_index_mode(int64_t Fin, int64_t Fout, int exact) {
+  if (!gwen_gcn_layer_supported(Fin, Fout) || exact < 0 || exact > 2) return 0;
+  if (!narrow(Fin, Fout)) return 1;
+  return layer_index_mode(Fin, Fout, gwen::images_of(exact));
+}
+
 // entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
 // kernels turn into one gather less per row; every other shape and layout gathers whole groups.
-// depth, block_rows: 0 = the library's choice (layer_depth; the co-resident grid of launch()); neither changes a value
-extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                        const float *x, const float *W, const float *bias, float *out,
-                                        int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
-                                        int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
-                                        int exact, int entries, int depth, int block_rows, gwen_stream_t stream_) {
+// depth, block_rows, index_mode: 0 = the library's choice (layer_depth; the co-resident grid of launch();
+// layer_index_mode); none changes a value.  index_mode 1: every lane loads its row's group; 2: index records -- narrow
+// layers on the uniform layout only, GWEN_EINVAL elsewhere
+extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W, const float *bias, float *out,
+                                         int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                         int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                         int exact, int entries, int depth, int block_rows, int index_mode,
+                                         gwen_stream_t stream_) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
+  if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
   if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
   if (block_rows != 0 && !rows_ok(Fin, Fout, block_rows)) return GWEN_EINVAL;   // the one check of block_rows
+  if (index_mode == 2 && (rowptr || !narrow(Fin, Fout))) return GWEN_EINVAL;    // records: uniform layout, narrow layers
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || !W || !out || x == out) return GWEN_EINVAL;   // rowptr NULL = uniform
   if (N >= (int64_t(1) << 28) || members > 65535) return GWEN_ERANGE;     // 8 N must fit int32
@@ -464,21 +491,33 @@ extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *co
     return GWEN_EINVAL;                       // x rows must be contiguous (32-bit row offsets)
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_layer_depth(Fin, Fout, exact);
+  if (index_mode == 0) index_mode = rowptr ? 1 : gwen_gcn_layer_index_mode(Fin, Fout, exact);
   const int ge = entries == 7 && !rowptr ? 7 : 8;          // 7 on the uniform layout when the caller promises it
   const LayerArgs a{rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, mstride_o, relu, gwen_stream(stream_),
                     nullptr, nullptr, nullptr, nullptr, false};
   return with_shape(Fin, Fout, gwen::ints<0, 2, 3>{}, gwen::images_of(exact), [&](auto fi, auto fo, auto nsv) {
     constexpr int FI = decltype(fi)::value, FO = decltype(fo)::value, NS = decltype(nsv)::value;
-    if constexpr (narrow(FI, FO)) {            // narrow layers: GE x D
+    if constexpr (narrow(FI, FO)) {            // narrow layers: GE x D x index mode
       return gwen::dispatch(gwen::ints<7, 8>{}, ge, [&](auto gev) {
         return gwen::dispatch(gwen::ints<1, 2>{}, depth, [&](auto dv) {
-          return launch<FI, FO, NS, decltype(gev)::value, decltype(dv)::value>(a, block_rows);
+          return gwen::dispatch(gwen::ints<1, 2>{}, index_mode, [&](auto iv) {
+            return launch<FI, FO, NS, decltype(gev)::value, decltype(dv)::value, decltype(iv)::value>(a, block_rows);
+          });
         });
       });
     } else {                                   // the wide kernels gather whole groups at one depth
       return launch<FI, FO, NS, 8, 1>(a, block_rows);
     }
   });
+}
+
+extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                        const float *x, const float *W, const float *bias, float *out,
+                                        int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                        int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                        int exact, int entries, int depth, int block_rows, gwen_stream_t stream_) {
+  return gwen_gcn_layer_tuned2_f32(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x,
+                                   mstride_o, relu, exact, entries, depth, block_rows, 0, stream_);
 }
 
 extern "C" int gwen_gcn_layer_entries_f32(const int32_t *rowptr, const int32_t *col, const float *val,

@@ -230,6 +230,20 @@ int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *col, const fl
                              gwen_stream_t stream);
 /* the depth gwen_gcn_layer_f32 runs on a uniform layout: 1 or 2 (0: unsupported widths / exact) */
 int gwen_gcn_layer_depth(int64_t Fin, int64_t Fout, int exact);
+/* gwen_gcn_layer_tuned_f32 with a third scheduling choice that CHANGES NO VALUE (every output is bitwise the same,
+ * signed zeros included); gwen_gcn_layer_tuned_f32 forwards with 0.
+ * index_mode: how the lanes that share a destination row get its column indices and weights -- 1 = every lane loads
+ *   the row's whole group of 8 + 8; 2 = "index records": each lane loads its share of the 64 bytes once per row and the
+ *   values are broadcast inside the lane group (Fin, Fout <= 64 on the uniform layout only: with a row pointer or at
+ *   other widths GWEN_EINVAL); 0 = the library's choice (gwen_gcn_layer_index_mode on a uniform layout, else 1).
+ * index_mode outside {0, 1, 2}: GWEN_EINVAL. */
+int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                              int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                              int64_t mstride_o, int relu, int exact, int entries, int depth, int block_rows,
+                              int index_mode, gwen_stream_t stream);
+/* the index mode gwen_gcn_layer_f32 runs on a uniform layout: 1 or 2 (0: unsupported widths / exact) */
+int gwen_gcn_layer_index_mode(int64_t Fin, int64_t Fout, int exact);
 
 /* ---------------------------------------------------------------------------------------------
  * K8  K4's contract for WIDE layers on locality-ordered bounded-degree graphs (meshes), tile-staged:
@@ -313,6 +327,15 @@ int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *col, const fl
                              int block_rows, gwen_stream_t stream);
 /* the depth gwen_gcn_chain_f32 runs on a uniform layout: 1 or 2 (0: gwen_gcn_chain_supported says no) */
 int gwen_gcn_chain_depth(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
+/* index_mode: as gwen_gcn_layer_tuned2_f32 -- it changes no value; gwen_gcn_chain_tuned_f32 forwards with 0.  Mode 2
+ * acts at Fin, F1 <= 64 on the uniform layout (the form without a contraction included); elsewhere GWEN_EINVAL. */
+int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+                              int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
+                              int64_t mstride_x, int64_t mstride_o, int contract, int entries, int depth,
+                              int block_rows, int index_mode, gwen_stream_t stream);
+/* the index mode gwen_gcn_chain_f32 runs on a uniform layout: 1 or 2 (0: gwen_gcn_chain_supported says no) */
+int gwen_gcn_chain_index_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-stack forward == GNNModel.forward (/root/reference/src/gwen/models_gnn.py:292-303 ->
