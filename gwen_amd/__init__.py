@@ -19,7 +19,8 @@ from .noise import NoiseStream
 from .forcings import ForcingClock
 from .products import ensemble_products, ensemble_quantiles, exceedance_probability, rank_histogram
 from .gridgraph import containing_faces, grid_graphs, latlon_grid, radius_edges, sphere_points
-from .regrid import Regridder, nearest_neighbours
+from .regrid import (Regridder, cell_areas, cell_overlaps, latlon_cells, mesh_cells, mesh_dual_cells,
+                     nearest_neighbours)
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
 from .models_gnn import (DownConvLayers, GCNConvLayers, GNNConfig, GNNModel, UpConvLayers,
@@ -32,6 +33,6 @@ __all__ = [
     "EnsembleCRPSLoss", "ensemble_crps", "ensemble_scores", "NoiseStream", "GraphTransformer", "edge_attention", "edge_attention_kv",
     "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
     "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
-    "Regridder", "nearest_neighbours", "checkpointed_step", "CRPSLoss", "EnsembleVarRegLoss", "MaskedLoss",
+    "Regridder", "nearest_neighbours", "mesh_cells", "mesh_dual_cells", "latlon_cells", "cell_areas", "cell_overlaps", "checkpointed_step", "CRPSLoss", "EnsembleVarRegLoss", "MaskedLoss",
 ]
 __version__ = "0.1.0"

@@ -90,6 +90,7 @@ EW_MUL, EW_ADD = 0, 1
 MLP2_LN_EDGE, MLP2_LN_NODE = 0, 1                    # GWEN_MLP2_LN_* (include/gwen_hip.h)
 MASKED_L1, MASKED_MSE = 0, 1                         # GWEN_MASKED_* (include/gwen_hip.h)
 REGRID_NEAREST, REGRID_IDW = 0, 1                    # GWEN_REGRID_* (include/gwen_hip.h)
+CONSERVE_COVERED, CONSERVE_CELL = 0, 1               # GWEN_CONSERVE_*
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
 
@@ -248,6 +249,9 @@ SIGNATURES = {
     "gwen_knn_query": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp,
                               C.c_size_t, _vp]),
     "gwen_knn_weights": (_int, [_vp, _vp, _i64, _int, _int, _f64, _vp, _vp, _vp]),
+    "gwen_cell_areas": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
+    "gwen_cell_overlap_areas": (_int, [_vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gwen_cell_overlap_weights": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
 }
 
 

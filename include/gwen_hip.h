@@ -1043,6 +1043,53 @@ int gwen_knn_query(const double *src_pos, const int32_t *src_ids, int64_t num_sr
 int gwen_knn_weights(const double *d2, const int32_t *count, int64_t num_dst, int k, int method, double power,
                      float *weights, int32_t *entries, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Conservative regridding (csrc/conserve.hip): the overlap areas of two sets of cells on the unit sphere and the
+ * first-order conservative weights from them.  BUILD-DEFINED, PARITY UNPINNED (the reference regrids nothing); restated
+ * in numpy in tests/conserve_ref.py.  No launcher allocates, synchronises or uses atomics; two builds are bitwise equal.
+ * 3 <= V <= 8 and a valid mode (GWEN_EINVAL otherwise); sizes >= 2^31 - 1 are GWEN_ERANGE; bad arguments return before any
+ * HIP call; an empty problem returns 0.
+ *
+ *   GEOMETRY.  A cell is a CONVEX spherical polygon: V vertices, unit vectors, counter-clockwise seen from outside, joined
+ *         by GREAT-CIRCLE arcs, inside a cap of chord radius <= 1 about its normalised vertex mean.  A cell set is fp64
+ *         [N, V, 3] row-major.  A cell with fewer corners repeats a vertex (a lat-lon cell at a pole is a wedge whose two
+ *         polar corners coincide); an edge whose two ends are equal in every coordinate is SKIPPED, never clipped against.
+ *         A lat-lon box gets great-circle edges where the true box has parallels; neighbours share the same arc, so the
+ *         cells still tile the sphere exactly.  All of it is fp64 without fused multiply-add:
+ *             dot(a, b)     = (a0 b0 + a1 b1) + a2 b2
+ *             cross(a, b)   = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)
+ *             tri(a, b, c)  = 2 atan2(dot(a, cross(b, c)), ((1 + dot(a, b)) + dot(b, c)) + dot(c, a))
+ *             area(P)       = (tri(P0, P1, P2) + tri(P0, P2, P3)) + ...      0 with fewer than 3 vertices
+ *   OVERLAP of source cell S and target cell T: S, clipped in turn against the half-space dot(cross(a, b), p) >= 0 of every
+ *         non-degenerate edge (a, b) = (T_j, T_j+1) of T, j ascending (Sutherland-Hodgman in 3-D: walking the arcs (p, q)
+ *         of the polygon from vertex 0, an inside p is kept, and where p and q lie on different sides the crossing
+ *         |d_p| q + |d_q| p, divided by its length, follows); then area().  At most 16 vertices are held, which every
+ *         convex input respects; a 17th is dropped.
+ *   KEEP RULE (applied by the caller): a pair is an entry when area > 1e-12 min(A_S, A_T).  Cells that only share an edge
+ *         or a corner give slivers of relative size <= 4e-15; the cut sits far above them and far below any real overlap.
+ *
+ *   gwen_cell_areas: per cell, centre fp64 [n, 3] = s / sqrt(dot(s, s)) with s = ((v_0 + v_1) + v_2) + ..., radius fp64 [n]
+ *         = sqrt of the largest (dx dx + dy dy) + dz dz over d = v_k - centre, area fp64 [n] = area(cell).
+ *   gwen_cell_overlap_areas: one work item per candidate pair; pairs int64 [2, e] row-major (row 0 = source cell, row 1 =
+ *         target cell; an index out of range gives area 0).  A pair with (dx dx + dy dy) + dz dz > (r_S + r_T)(r_S + r_T)
+ *         on d = dst_centre - src_centre is rejected (the caps are disjoint, so are the cells), else clipped and measured.
+ *         area fp64 [e]: 0 for a rejected or empty pair (a sliver may come out as a tiny negative number).
+ *   gwen_cell_overlap_weights: rowptr int64 [num_dst + 1] over the kept pairs (sorted by target), area fp64 [e] their
+ *         areas, dst_area fp64 [num_dst].  One thread per target sums its row in stored order in fp64:
+ *         coverage fp64 [num_dst] = sum / A_t; weights fp32 [e] = A_ts / sum (GWEN_CONSERVE_COVERED: a constant stays
+ *         constant on a partially covered target) or A_ts / A_t (GWEN_CONSERVE_CELL: the integral is preserved), computed
+ *         in fp64 and rounded once.
+ * ------------------------------------------------------------------------------------------- */
+#define GWEN_CONSERVE_COVERED 0
+#define GWEN_CONSERVE_CELL 1
+int gwen_cell_areas(const double *cells, int64_t n, int v, double *centre, double *radius, double *area,
+                    gwen_stream_t stream);
+int gwen_cell_overlap_areas(const double *src_cells, int64_t num_src, int vs, const double *dst_cells, int64_t num_dst,
+                            int vt, const int64_t *pairs, int64_t e, const double *src_centre, const double *src_radius,
+                            const double *dst_centre, const double *dst_radius, double *area, gwen_stream_t stream);
+int gwen_cell_overlap_weights(const int64_t *rowptr, const double *area, const double *dst_area, int64_t num_dst,
+                              int64_t e, int mode, float *weights, double *coverage, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
