@@ -37,15 +37,15 @@
 //   [cT, (c+1)T), so every target row is summed by exactly one block; T = 64 - (max degree - 1) makes a
 //   tile one pass of 64 edges on bounded-degree graphs, and a row longer than a pass is carried
 //   through the block's own earlier partial sum (same thread, program order).
+#include <initializer_list>
 #include "common.h"
+#include "interact.h"
 #include "split.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMaxRows = 128;             // most rows a pass takes (MCfg<F>::ROWS; 128 at 256 channels)
 
 template <int F>
 struct MCfg {
@@ -224,9 +224,6 @@ __device__ inline float4_t activate(float4_t v, int act) {
   }
   return v;
 }
-
-// M1 / M2: how table G1 / G2 is addressed -- 0 absent, 1 row r itself, 2 row idx[r]
-constexpr int kNone = 0, kSelf = 1, kIdx = 2;
 
 // One PASS = up to 64 consecutive rows [w0, min(w0 + 64, e1)) of tile `tile` (target rows r0 .. r1-1).
 struct Pass {
@@ -576,16 +573,13 @@ __global__ void k_edge_tiles(const int32_t *__restrict__ rowptr, int32_t N, int3
   for (int32_t c = s / T + 1; c < n_tiles && (int64_t)c * T <= en; ++c) tile_row[c] = r + 1;
 }
 
+static_assert(MCfg<32>::ROWS <= kMaxRows && MCfg<128>::ROWS <= kMaxRows, "kMaxRows (interact.h) must cover a pass");
+
 template <int F, int M1, int M2, bool F16>
-int launch(const float *A, const float *W1, const float *G1, const int32_t *idx1, const float *G2,
-           const int32_t *idx2, const float *b1, const float *W2, const float *b2, const float *res,
-           float *out, int64_t R, int act, const int32_t *rowptr, const int32_t *tile_row,
-           int64_t n_tiles, float *agg, int mean, void *workspace, uint32_t ldb1, uint32_t ldb2,
-           hipStream_t st) {
+int launch(const Mlp2Args &a) {
   using C = MCfg<F>;
-  const bool seg = agg != nullptr;
-  (void)workspace;
-  const int64_t tiles = seg ? n_tiles : (R + C::ROWS - 1) / C::ROWS;
+  const bool seg = a.agg != nullptr;
+  const int64_t tiles = seg ? a.n_tiles : (a.R + C::ROWS - 1) / C::ROWS;
   // W1 and W2 (2 x 16 F^2 bytes per block) are fetched once per block: one resident set of blocks
   // walks the tiles, each prefetching its next pass while it computes the current one
   static int per_cu = 0;
@@ -597,46 +591,36 @@ int launch(const float *A, const float *W1, const float *G1, const int32_t *idx1
   }
   int64_t blocks = (int64_t)256 * per_cu;
   if (blocks > tiles) blocks = tiles;
-  if (seg)
-    k_mlp2<F, M1, M2, true, F16><<<(unsigned)blocks, C::NWB * 64, 0, st>>>(
-        A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, (int32_t)R, act, rowptr, tile_row,
-        (int32_t)tiles, agg, mean, ldb1, ldb2);
-  else
-    k_mlp2<F, M1, M2, false, F16><<<(unsigned)blocks, C::NWB * 64, 0, st>>>(
-        A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, (int32_t)R, act, nullptr, nullptr,
-        (int32_t)tiles, nullptr, 0, ldb1, ldb2);
-  GWEN_LAUNCH_CHECK();
-  return GWEN_OK;
+  return gwen::dispatch(gwen::ints<0, 1>{}, seg, [&](auto sv) {
+    constexpr bool SEG = decltype(sv)::value != 0;
+    k_mlp2<F, M1, M2, SEG, F16><<<(unsigned)blocks, C::NWB * 64, 0, a.st>>>(
+        a.A, a.W1, a.G1, a.idx1, a.G2, a.idx2, a.b1, a.W2, a.b2, a.res, a.out, (int32_t)a.R, a.act,
+        SEG ? a.rowptr : nullptr, SEG ? a.tile_row : nullptr, (int32_t)tiles, SEG ? a.agg : nullptr, SEG ? a.mean : 0,
+        a.ldb1, a.ldb2);
+    GWEN_LAUNCH_CHECK();
+    return (int)GWEN_OK;
+  });
 }
 
-template <int F>
-int launch_mode(int f16, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                const float *G2, const int32_t *idx2, const float *b1, const float *W2,
-                const float *b2, const float *res, float *out, int64_t R, int act,
-                const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg, int mean,
-                void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st) {
-#define GWEN_MODE(A1, A2, H)                                                                     \
-  if (m1 == A1 && m2 == A2 && (f16 != 0) == H)                                                   \
-    return launch<F, A1, A2, H>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
-                                tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st)
-  GWEN_MODE(kNone, kNone, false); GWEN_MODE(kSelf, kNone, false); GWEN_MODE(kIdx, kNone, false);
-  GWEN_MODE(kIdx, kIdx, false);
-  GWEN_MODE(kNone, kNone, true); GWEN_MODE(kSelf, kNone, true); GWEN_MODE(kIdx, kNone, true); GWEN_MODE(kIdx, kIdx, true);
-#undef GWEN_MODE
-  return GWEN_EINVAL;
+// 32 and 128 channels: width, table pair and tier of a validated call -> the k_mlp2 that serves it
+int launch_tiles(const Mlp2Mode &m, const Mlp2Args &a) {
+  return gwen::dispatch(gwen::ints<32, 128>{}, m.F, [&](auto fv) {
+    return gwen::dispatch(Mlp2Pairs{}, 3 * m.m1 + m.m2, [&](auto pv) {
+      return gwen::dispatch(gwen::ints<0, 1>{}, m.f16 != 0, [&](auto hv) {
+        constexpr int P = decltype(pv)::value;
+        return launch<decltype(fv)::value, P / 3, P % 3, decltype(hv)::value != 0>(a);
+      });
+    });
+  });
+}
+
+bool aligned16(std::initializer_list<const void *> ps) {       // NULL = not passed
+  for (const void *p : ps)
+    if (p && !gwen_aligned(p, 16)) return false;
+  return true;
 }
 
 }  // namespace
-
-// interact_rows.hip: the row-stationary kernel 256 channels run on
-int gwen_mlp2_rows_f();
-int64_t gwen_mlp2_rows_ws_bytes(int F, int f16);
-int gwen_mlp2_rows_launch(int F, int f16, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                          const float *G2, const int32_t *idx2, const float *b1, const float *W2,
-                          const float *b2, const float *res, float *out, int64_t R, int act,
-                          const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg,
-                          int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st, const float *ln_g,
-                          const float *ln_b, float ln_eps);
 
 extern "C" int gwen_mlp2_supported(int64_t F) {
   return F == 32 || F == 64 || F == 128 || F == 256 ? 1 : 0;
@@ -685,9 +669,6 @@ extern "C" int gwen_edge_tiles(const int32_t *rowptr, int64_t N, int64_t E, int6
 //     g_e    = ge + g_pre1 We
 // W2t = W2^T and Wet = We^T, [F, F] row-major (row = output column of the contraction); d1 = act'(pre1) [R, F];
 // g_pre1 has gwen_mlp2_bwd_rows(R) rows (whole passes: the kernel stores every lane), g_e has R.  F in {64, 256}.
-int gwen_mlp2_rows_bwd_launch(int F, int f16, const float *ge, const float *W2t, const float *d1, const float *T,
-                              const int32_t *dst, const float *Wet, float *hid, float *out, int64_t R, void *workspace,
-                              uint32_t ldbT, hipStream_t st);
 extern "C" int64_t gwen_mlp2_bwd_rows(int64_t R) {
   const int64_t rows = gwen_mlp2_rows_f();
   return R <= 0 ? 0 : (R + rows - 1) / rows * rows;
@@ -706,11 +687,10 @@ extern "C" int gwen_mlp2_bwd_contract_f32(const float *ge, const float *W2t, con
     return GWEN_ERANGE;              // 32-bit byte offsets into the tables (d1 is read as a table, row for row)
   const int64_t need = gwen_mlp2_contract_workspace_bytes(F, contract);
   if (need > 0 && (!workspace || (int64_t)workspace_bytes < need)) return GWEN_ENOSPACE;
-  const void *al[] = {ge, W2t, d1, T, Wet, g_pre1, g_e, need > 0 ? workspace : nullptr};
-  for (const void *p : al)
-    if (p && !gwen_aligned(p, 16)) return GWEN_EINVAL;
-  return gwen_mlp2_rows_bwd_launch((int)F, contract == GWEN_CONTRACT_F16X3, ge, W2t, d1, T, dst, Wet, g_pre1, g_e, R,
-                                   workspace, (uint32_t)(ldT * 4), gwen_stream(stream_));
+  if (!aligned16({ge, W2t, d1, T, Wet, g_pre1, g_e, need > 0 ? workspace : nullptr})) return GWEN_EINVAL;
+  return gwen_mlp2_rows_bwd_launch((int)F, contract == GWEN_CONTRACT_F16X3,
+                                   {ge, W2t, d1, T, dst, Wet, g_pre1, g_e, R, workspace, (uint32_t)(ldT * 4),
+                                    gwen_stream(stream_)});
 }
 
 extern "C" int gwen_mlp2_bwd_f32(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
@@ -727,15 +707,14 @@ extern "C" int gwen_mlp2_ln_supported(int64_t F, int contract, int shape) {
   return F == 64 && (shape == GWEN_MLP2_LN_EDGE || shape == GWEN_MLP2_LN_NODE) ? 1 : 0;
 }
 
-// gwen_mlp2_contract_f32 and gwen_mlp2_ln_f32 (ln_gamma / ln_beta NULL: the former, the same launch bit for bit)
-static int mlp2_run(const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                                      int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
-                                      int64_t G2_rows, int64_t ldg2,
-                                      const float *b1, const float *W2, const float *b2, const float *res,
-                                      float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
-                                      const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
-                                      int mean, int contract, void *workspace, size_t workspace_bytes,
-                                      gwen_stream_t stream_, const float *ln_g, const float *ln_b, float ln_eps) {
+// The forward entry point the other two forward to (ln_g / ln_b NULL: gwen_mlp2_contract_f32).  It validates, fills
+// Mlp2Mode and Mlp2Args once, and hands them to the launcher of the width.
+extern "C" int gwen_mlp2_ln_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1, int64_t G1_rows,
+                                int64_t ldg1, const float *G2, const int32_t *idx2, int64_t G2_rows, int64_t ldg2,
+                                const float *b1, const float *W2, const float *b2, const float *res, float *out, int64_t R,
+                                int64_t F, int act, const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles,
+                                float *agg, int64_t N_agg, int mean, int contract, const float *ln_g, const float *ln_b,
+                                float ln_eps, void *workspace, size_t workspace_bytes, gwen_stream_t stream_) {
   if (R < 0 || N_agg < 0 || n_tiles < 0 || G1_rows < 0 || G2_rows < 0) return GWEN_EINVAL;
   if (!gwen_mlp2_contract_supported(F, contract)) return GWEN_EINVAL;
   if ((ln_g != nullptr) != (ln_b != nullptr)) return GWEN_EINVAL;
@@ -746,7 +725,6 @@ static int mlp2_run(const float *A, const float *W1, const float *G1, const int3
         !(ln_eps >= 0.0f) || !gwen_aligned(ln_g, 16) || !gwen_aligned(ln_b, 16))
       return GWEN_EINVAL;
   }
-  const int f16 = contract == GWEN_CONTRACT_F16X3;
   if (act != GWEN_ACT_NONE && act != GWEN_ACT_RELU && act != GWEN_ACT_SILU) return GWEN_EINVAL;
   if (agg && (!rowptr || !tile_row || n_tiles < 1)) return GWEN_EINVAL;
   if (!agg && !out) return R == 0 ? GWEN_OK : GWEN_EINVAL;
@@ -758,64 +736,40 @@ static int mlp2_run(const float *A, const float *W1, const float *G1, const int3
   }
   if (!A || !W1 || !W2 || (idx1 && !G1) || (idx2 && !G2) || (G2 && !G1)) return GWEN_EINVAL;
   // a table without an index is read row for row; the supported pairs are listed in the header
-  const int m1 = !G1 ? kNone : (idx1 ? kIdx : kSelf), m2 = !G2 ? kNone : (idx2 ? kIdx : kSelf);
-  if ((m1 == kSelf && G1_rows < R) || (m2 == kSelf && G2_rows < R)) return GWEN_EINVAL;
+  const Mlp2Mode m{(int)F, !G1 ? kNone : (idx1 ? kIdx : kSelf), !G2 ? kNone : (idx2 ? kIdx : kSelf),
+                   contract == GWEN_CONTRACT_F16X3};
+  if ((m.m1 == kSelf && G1_rows < R) || (m.m2 == kSelf && G2_rows < R)) return GWEN_EINVAL;
   if ((G1 && (ldg1 < F || ldg1 % 4)) || (G2 && (ldg2 < F || ldg2 % 4))) return GWEN_EINVAL;
   if ((G1 && G1_rows * ldg1 * 4 >= (int64_t(1) << 32)) || (G2 && G2_rows * ldg2 * 4 >= (int64_t(1) << 32)))
     return GWEN_ERANGE;              // 32-bit byte offsets into the tables
   if (out && (out == G1 || out == G2)) return GWEN_EINVAL;      // out may alias A / res row for row
   const int64_t need = gwen_mlp2_contract_workspace_bytes(F, contract);
   if (need > 0 && (!workspace || (int64_t)workspace_bytes < need)) return GWEN_ENOSPACE;
-  const void *al[] = {A, W1, G1, G2, b1, W2, b2, res, out, agg, need > 0 ? workspace : nullptr};
-  for (const void *p : al)
-    if (p && !gwen_aligned(p, 16)) return GWEN_EINVAL;
-#define GWEN_M(FF)                                                                                \
-  if (F == FF)                                                                                    \
-    return launch_mode<FF>(f16, m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
-                           tile_row, n_tiles, agg, mean, workspace, (uint32_t)(ldg1 * 4),       \
-                           (uint32_t)(ldg2 * 4), st)
-  if (F == 256 || F == 64)
-    return gwen_mlp2_rows_launch((int)F, f16, m1, m2, A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, tile_row,
-                                 n_tiles, agg, mean, workspace, (uint32_t)(ldg1 * 4), (uint32_t)(ldg2 * 4), st, ln_g, ln_b,
-                                 ln_eps);
-  GWEN_M(32); GWEN_M(128);
-#undef GWEN_M
-  return GWEN_EINVAL;
+  if (!aligned16({A, W1, G1, G2, b1, W2, b2, res, out, agg, need > 0 ? workspace : nullptr})) return GWEN_EINVAL;
+  const Mlp2Args a{A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, tile_row, n_tiles, agg, mean,
+                   workspace, (uint32_t)(ldg1 * 4), (uint32_t)(ldg2 * 4), ln_g, ln_b, ln_eps, st};
+  return F == 64 || F == 256 ? gwen_mlp2_rows_launch(m, a) : launch_tiles(m, a);
 }
 
 extern "C" int gwen_mlp2_contract_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                                      int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
-                                      int64_t G2_rows, int64_t ldg2,
-                                      const float *b1, const float *W2, const float *b2, const float *res,
+                                      int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2, int64_t G2_rows,
+                                      int64_t ldg2, const float *b1, const float *W2, const float *b2, const float *res,
                                       float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
-                                      const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
-                                      int mean, int contract, void *workspace, size_t workspace_bytes,
-                                      gwen_stream_t stream_) {
-  return mlp2_run(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act, rowptr, tile_row,
-                  n_tiles, agg, N_agg, mean, contract, workspace, workspace_bytes, stream_, nullptr, nullptr, 0.0f);
+                                      const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg, int mean,
+                                      int contract, void *workspace, size_t workspace_bytes, gwen_stream_t stream_) {
+  return gwen_mlp2_ln_f32(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act, rowptr,
+                          tile_row, n_tiles, agg, N_agg, mean, contract, nullptr, nullptr, 0.0f, workspace, workspace_bytes,
+                          stream_);
 }
 
-extern "C" int gwen_mlp2_ln_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                                int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
-                                int64_t G2_rows, int64_t ldg2,
-                                const float *b1, const float *W2, const float *b2, const float *res,
-                                float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
-                                const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
-                                int mean, int contract, const float *ln_gamma, const float *ln_beta, float ln_eps,
-                                void *workspace, size_t workspace_bytes, gwen_stream_t stream_) {
-  return mlp2_run(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act, rowptr, tile_row,
-                  n_tiles, agg, N_agg, mean, contract, workspace, workspace_bytes, stream_, ln_gamma, ln_beta, ln_eps);
-}
-
-extern "C" int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                             int64_t G1_rows, int64_t ldg1, const float *G2, const int32_t *idx2,
-                             int64_t G2_rows, int64_t ldg2,
-                             const float *b1, const float *W2, const float *b2, const float *res,
-                             float *out, int64_t R, int64_t F, int act, const int32_t *rowptr,
-                             const int32_t *tile_row, int64_t n_tiles, float *agg, int64_t N_agg,
-                             int mean, void *workspace, size_t workspace_bytes,
+extern "C" int gwen_mlp2_f32(const float *A, const float *W1, const float *G1, const int32_t *idx1, int64_t G1_rows,
+                             int64_t ldg1, const float *G2, const int32_t *idx2, int64_t G2_rows, int64_t ldg2,
+                             const float *b1, const float *W2, const float *b2, const float *res, float *out, int64_t R,
+                             int64_t F, int act, const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles,
+                             float *agg, int64_t N_agg, int mean, void *workspace, size_t workspace_bytes,
                              gwen_stream_t stream_) {
   return gwen_mlp2_contract_f32(A, W1, G1, idx1, G1_rows, ldg1, G2, idx2, G2_rows, ldg2, b1, W2, b2, res, out, R, F, act,
                                 rowptr, tile_row, n_tiles, agg, N_agg, mean, GWEN_CONTRACT_BF16X3, workspace,
                                 workspace_bytes, stream_);
 }
+

@@ -34,6 +34,7 @@
 // contraction releases them, and the finished pass's A registers receive the next pass's gathered G2 rows
 // (the first contraction accumulates onto them), so the pass body exists twice with the two sets swapped.
 #include "common.h"
+#include "interact.h"
 #include "rows_common.h"
 #include "split.h"
 // (the lab version of this file -- timing ablations -DABL=1..7, per-phase s_memtime stamps -DGWEN_K6R_STAMPS, two row
@@ -41,9 +42,6 @@
 constexpr int K6R_RT = 1;      // 16-row tiles per wave (see RCfg)
 
 namespace {
-
-constexpr int kNone = 0, kSelf = 1, kIdx = 2;      // how a table is addressed (as interact.hip)
-constexpr int kResNone = 0, kResA = 1, kResOther = 2;
 
 // RT = 16-row tiles per wave: 1 -> 8 waves (two per SIMD, 256 registers each) -- what runs; 2 -> 4 waves (one per
 // SIMD, 512 registers, every W fragment read from LDS feeds two row tiles): hipcc spills 130-230 registers of the
@@ -815,18 +813,13 @@ const int32_t *split_weights(const float *W1, const float *W2, void *workspace, 
   return F16 ? wexp : nullptr;
 }
 
-template <int F, int M1, int M2, bool F16>
-int launch_rows(const float *A, const float *W1, const float *G1, const int32_t *idx1, const float *G2,
-                const int32_t *idx2, const float *b1, const float *W2, const float *b2, const float *res,
-                float *out, int64_t R, int act, const int32_t *rowptr, const int32_t *tile_row,
-                int64_t n_tiles, float *agg, int mean, void *workspace, uint32_t ldb1, uint32_t ldb2,
-                hipStream_t st, const float *ln_g = nullptr, const float *ln_b = nullptr, float ln_eps = 0.0f) {
-  using C = RCfg<F, K6R_RT>;
-  const bool seg = agg != nullptr;
-  bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);
-  const int32_t *wexp = split_weights<F, F16>(W1, W2, workspace, st);
-  if constexpr (!C::RESIDENT) GWEN_LAUNCH_CHECK();
-  const int64_t tiles = seg ? n_tiles : (R + C::ROWS - 1) / C::ROWS;
+static_assert(RCfg<64, K6R_RT>::ROWS <= kMaxRows && RCfg<256, K6R_RT>::ROWS <= kMaxRows &&
+              RCfg<64, K6R_RT>::ROWS == RCfg<256, K6R_RT>::ROWS, "kMaxRows (interact.h) must cover a pass; one pass size");
+
+// one resident set of blocks walks the tiles: a block per CU (the device is asked once; at least 8), two where the
+// weights are RESIDENT -- 130 KB of LDS at 256 channels, 68 KB at 64
+template <class C>
+int resident_blocks(int64_t tiles, int64_t *blocks) {
   static int cus = 0;
   if (cus == 0) {
     int dev = 0, n = 0;
@@ -834,11 +827,23 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
     GWEN_HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
     cus = n < 8 ? 8 : n;
   }
-  int64_t blocks = (int64_t)cus * (C::RESIDENT ? 2 : 1);              // 130 KB of LDS at 256 channels, 68 KB at 64
-  if (blocks > tiles) blocks = tiles;
-  const int r = !res ? kResNone : (res == A ? kResA : kResOther);
-  const char *im = reinterpret_cast<const char *>(img);
-  if (ln_g) {
+  *blocks = (int64_t)cus * (C::RESIDENT ? 2 : 1);
+  if (*blocks > tiles) *blocks = tiles;
+  return GWEN_OK;
+}
+
+template <int F, int M1, int M2, bool F16>
+int launch_rows(const Mlp2Args &a) {
+  using C = RCfg<F, K6R_RT>;
+  const bool seg = a.agg != nullptr;
+  const int32_t *wexp = split_weights<F, F16>(a.W1, a.W2, a.workspace, a.st);
+  if constexpr (!C::RESIDENT) GWEN_LAUNCH_CHECK();
+  const int64_t tiles = seg ? a.n_tiles : (a.R + C::ROWS - 1) / C::ROWS;
+  int64_t blocks = 0;
+  if (const int rc = resident_blocks<C>(tiles, &blocks)) return rc;
+  const int r = !a.res ? kResNone : (a.res == a.A ? kResA : kResOther);
+  const char *im = reinterpret_cast<const char *>(a.workspace);
+  if (a.ln_g) {
     // LN exists for the two shapes the block launches (gwen_mlp2_ln_supported): the edge MLP -- both tables indexed, per-
     // target sums, residual = A -- and the node MLP -- G1 row for row, no sums, a residual other than A
     // ... at 64 channels.  The 256-channel instantiations are NOT shipped: the kernel sits at 256 registers without LN and
@@ -846,54 +851,47 @@ int launch_rows(const float *A, const float *W1, const float *G1, const int32_t 
     constexpr bool kEdge = M1 == kIdx && M2 == kIdx, kNode = M1 == kSelf && M2 == kNone;
     if constexpr ((kEdge || kNode) && C::RESIDENT) {
       if (kEdge ? (!seg || r != kResA) : (seg || r != kResOther)) return GWEN_EINVAL;
-      k_mlp2r<F, K6R_RT, M1, M2, kEdge, kEdge ? kResA : kResOther, false, F16, true><<<(unsigned)blocks, C::NW * 64, 0, st>>>(
-          A, im, W1, W2, G1, idx1, G2, idx2, b1, b2, res, out, (int32_t)R, act, kEdge ? rowptr : nullptr,
-          kEdge ? tile_row : nullptr, (int32_t)tiles, kEdge ? agg : nullptr, kEdge ? mean : 0, ldb1, ldb2, nullptr, wexp,
-          ln_g, ln_b, ln_eps);
+      k_mlp2r<F, K6R_RT, M1, M2, kEdge, kEdge ? kResA : kResOther, false, F16, true><<<(unsigned)blocks, C::NW * 64, 0, a.st>>>(
+          a.A, im, a.W1, a.W2, a.G1, a.idx1, a.G2, a.idx2, a.b1, a.b2, a.res, a.out, (int32_t)a.R, a.act,
+          kEdge ? a.rowptr : nullptr, kEdge ? a.tile_row : nullptr, (int32_t)tiles, kEdge ? a.agg : nullptr,
+          kEdge ? a.mean : 0, a.ldb1, a.ldb2, nullptr, wexp, a.ln_g, a.ln_b, a.ln_eps);
       GWEN_LAUNCH_CHECK();
       return GWEN_OK;
     } else {
       return GWEN_EINVAL;
     }
   }
-#define GWEN_R(SEGV, RV)                                                                              \
-  k_mlp2r<F, K6R_RT, M1, M2, SEGV, RV, false, F16><<<(unsigned)blocks, C::NW * 64, 0, st>>>(                 \
-      A, im, W1, W2, G1, idx1, G2, idx2, b1, b2, res, out, (int32_t)R, act, SEGV ? rowptr : nullptr,  \
-      SEGV ? tile_row : nullptr, (int32_t)tiles, SEGV ? agg : nullptr, SEGV ? mean : 0, ldb1, ldb2, nullptr, wexp)
-  if (seg) {
-    if (r == kResNone) GWEN_R(true, kResNone); else if (r == kResA) GWEN_R(true, kResA); else GWEN_R(true, kResOther);
-  } else {
-    if (r == kResNone) GWEN_R(false, kResNone); else if (r == kResA) GWEN_R(false, kResA); else GWEN_R(false, kResOther);
-  }
-#undef GWEN_R
-  GWEN_LAUNCH_CHECK();
-  return GWEN_OK;
+  return gwen::dispatch(gwen::ints<0, 1>{}, seg, [&](auto sv) {
+    return gwen::dispatch(gwen::ints<kResNone, kResA, kResOther>{}, r, [&](auto rv) {
+      constexpr bool SEG = decltype(sv)::value != 0;
+      k_mlp2r<F, K6R_RT, M1, M2, SEG, decltype(rv)::value, false, F16><<<(unsigned)blocks, C::NW * 64, 0, a.st>>>(
+          a.A, im, a.W1, a.W2, a.G1, a.idx1, a.G2, a.idx2, a.b1, a.b2, a.res, a.out, (int32_t)a.R, a.act,
+          SEG ? a.rowptr : nullptr, SEG ? a.tile_row : nullptr, (int32_t)tiles, SEG ? a.agg : nullptr, SEG ? a.mean : 0,
+          a.ldb1, a.ldb2, nullptr, wexp);
+      GWEN_LAUNCH_CHECK();
+      return (int)GWEN_OK;
+    });
+  });
 }
 
 // the block's edge-level backward (see k_mlp2r, HID): hid = (ge W2t^T + T[dst]) * d1 ; out = ge + hid Wet^T
 template <int F, bool F16>
-int launch_rows_bwd(const float *ge, const float *W2t, const float *d1, const float *T, const int32_t *dst,
-                    const float *Wet, float *hid, float *out, int64_t R, void *workspace, uint32_t ldbT, hipStream_t st) {
+int launch_rows_bwd(const Mlp2BwdArgs &a) {
   using C = RCfg<F, K6R_RT>;
-  bf16x8 *img = reinterpret_cast<bf16x8 *>(workspace);
-  const int32_t *wexp = split_weights<F, F16>(W2t, Wet, workspace, st);
+  const int32_t *wexp = split_weights<F, F16>(a.W2t, a.Wet, a.workspace, a.st);
   if constexpr (!C::RESIDENT) GWEN_LAUNCH_CHECK();
-  const int64_t tiles = (R + C::ROWS - 1) / C::ROWS;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, n = 0;
-    GWEN_HIP_CHECK(hipGetDevice(&dev));
-    GWEN_HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    cus = n < 8 ? 8 : n;
-  }
-  int64_t blocks = (int64_t)cus * (C::RESIDENT ? 2 : 1);
-  if (blocks > tiles) blocks = tiles;
-  k_mlp2r<F, K6R_RT, kSelf, kIdx, false, kResA, true, F16><<<(unsigned)blocks, C::NW * 64, 0, st>>>(
-      ge, reinterpret_cast<const char *>(img), W2t, Wet, d1, nullptr, T, dst, nullptr, nullptr, ge, out, (int32_t)R,
-      GWEN_ACT_NONE, nullptr, nullptr, (int32_t)tiles, nullptr, 0, (uint32_t)(F * 4), ldbT, hid, wexp);
+  const int64_t tiles = (a.R + C::ROWS - 1) / C::ROWS;
+  int64_t blocks = 0;
+  if (const int rc = resident_blocks<C>(tiles, &blocks)) return rc;
+  k_mlp2r<F, K6R_RT, kSelf, kIdx, false, kResA, true, F16><<<(unsigned)blocks, C::NW * 64, 0, a.st>>>(
+      a.ge, reinterpret_cast<const char *>(a.workspace), a.W2t, a.Wet, a.d1, nullptr, a.T, a.dst, nullptr, nullptr, a.ge,
+      a.out, (int32_t)a.R, GWEN_ACT_NONE, nullptr, nullptr, (int32_t)tiles, nullptr, 0, (uint32_t)(F * 4), a.ldbT, a.hid,
+      wexp);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
 }
+
+using RowWidths = gwen::ints<64, 256>;
 
 }  // namespace
 
@@ -902,35 +900,24 @@ int64_t gwen_mlp2_rows_ws_bytes(int F, int f16) {
   return F == 256 ? rows_ws_bytes<256>(f16 != 0) : 0;
 }
 
-int gwen_mlp2_rows_bwd_launch(int F, int f16, const float *ge, const float *W2t, const float *d1, const float *T,
-                              const int32_t *dst, const float *Wet, float *hid, float *out, int64_t R, void *workspace,
-                              uint32_t ldbT, hipStream_t st) {
-#define GWEN_B(FF, H)                                                                                        \
-  if (F == FF && (f16 != 0) == H) return launch_rows_bwd<FF, H>(ge, W2t, d1, T, dst, Wet, hid, out, R, workspace, ldbT, st)
-  GWEN_B(64, false); GWEN_B(256, false); GWEN_B(64, true); GWEN_B(256, true);
-#undef GWEN_B
-  return GWEN_EINVAL;
+int gwen_mlp2_rows_bwd_launch(int F, int f16, const Mlp2BwdArgs &a) {
+  return gwen::dispatch(RowWidths{}, F, [&](auto fv) {
+    return gwen::dispatch(gwen::ints<0, 1>{}, f16 != 0, [&](auto hv) {
+      return launch_rows_bwd<decltype(fv)::value, decltype(hv)::value != 0>(a);
+    });
+  });
 }
 
-// interact.hip's dispatch for F = 256 (pointers validated there); m1 / m2 as interact.hip's kNone / kSelf / kIdx
-int gwen_mlp2_rows_launch(int F, int f16, int m1, int m2, const float *A, const float *W1, const float *G1, const int32_t *idx1,
-                          const float *G2, const int32_t *idx2, const float *b1, const float *W2,
-                          const float *b2, const float *res, float *out, int64_t R, int act,
-                          const int32_t *rowptr, const int32_t *tile_row, int64_t n_tiles, float *agg,
-                          int mean, void *workspace, uint32_t ldb1, uint32_t ldb2, hipStream_t st, const float *ln_g,
-                          const float *ln_b, float ln_eps) {
-#define GWEN_MODE(FF, A1, A2, H)                                                                      \
-  if (F == FF && m1 == A1 && m2 == A2 && (f16 != 0) == H)                                             \
-    return launch_rows<FF, A1, A2, H>(A, W1, G1, idx1, G2, idx2, b1, W2, b2, res, out, R, act, rowptr, \
-                                      tile_row, n_tiles, agg, mean, workspace, ldb1, ldb2, st, ln_g, ln_b, ln_eps)
-  GWEN_MODE(256, kNone, kNone, false); GWEN_MODE(256, kSelf, kNone, false); GWEN_MODE(256, kIdx, kNone, false);
-  GWEN_MODE(256, kIdx, kIdx, false);
-  GWEN_MODE(64, kNone, kNone, false); GWEN_MODE(64, kSelf, kNone, false); GWEN_MODE(64, kIdx, kNone, false);
-  GWEN_MODE(64, kIdx, kIdx, false);
-  GWEN_MODE(256, kNone, kNone, true); GWEN_MODE(256, kSelf, kNone, true); GWEN_MODE(256, kIdx, kNone, true);
-  GWEN_MODE(256, kIdx, kIdx, true);
-  GWEN_MODE(64, kNone, kNone, true); GWEN_MODE(64, kSelf, kNone, true); GWEN_MODE(64, kIdx, kNone, true);
-  GWEN_MODE(64, kIdx, kIdx, true);
-#undef GWEN_MODE
-  return GWEN_EINVAL;
+// interact.hip's forward launcher at 64 and 256 channels (the call is validated there): width, table pair and tier ->
+// launch_rows, which picks the aggregation, the residual kind and, where it is built, the LayerNorm form
+int gwen_mlp2_rows_launch(const Mlp2Mode &m, const Mlp2Args &a) {
+  return gwen::dispatch(RowWidths{}, m.F, [&](auto fv) {
+    return gwen::dispatch(Mlp2Pairs{}, 3 * m.m1 + m.m2, [&](auto pv) {
+      return gwen::dispatch(gwen::ints<0, 1>{}, m.f16 != 0, [&](auto hv) {
+        constexpr int P = decltype(pv)::value;
+        return launch_rows<decltype(fv)::value, P / 3, P % 3, decltype(hv)::value != 0>(a);
+      });
+    });
+  });
 }
+

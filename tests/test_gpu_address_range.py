@@ -76,7 +76,7 @@ def _err(contract, got, want):
                                          (32, 68_000_003, True)])
 def test_k6_row_mlp_past_4gib(ga, F, R, elems31, contract):
     """Cases 1-3.  out = a + act(a W1^T + tab[idx] + b1) W2^T + b2 with res = a, b1 and one indexed table, on the
-    row-stationary kernel (256 and 64 channels) and the ``launch_mode`` kernel (128 and 32): A and out cross 2^32 bytes
+    row-stationary kernel (256 and 64 channels) and the ``launch_tiles`` kernel (128 and 32): A and out cross 2^32 bytes
     (at 256, 128 and 32 channels also 2^31 elements: the pass offset ``(int64_t)w0 * F`` of either kernel is the product
     that would wrap there), the row count ends ragged against the 64- and 128-row passes."""
     from gwen_amd.interaction import mlp2
