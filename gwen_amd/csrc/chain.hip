@@ -471,8 +471,8 @@ extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *c
     return GWEN_EINVAL;                                    // rowptr NULL = uniform layout
   if (N >= (int64_t(1) << 28) || members > 65535) return GWEN_ERANGE;
   if (!gwen_aligned(x, 16) || !gwen_aligned(out, 16) || (W1 && !gwen_aligned(W1, 16)) ||
-      (W2 && !gwen_aligned(W2, 16)) || (bias && !gwen_aligned(bias, 16)) || mstride_x % 4)
-    return GWEN_EINVAL;
+      (W2 && !gwen_aligned(W2, 16)) || (bias && !gwen_aligned(bias, 16)) || mstride_x % 4 || mstride_o % 4)
+    return GWEN_EINVAL;                                    // 16-byte loads at x + m * mstride_x, stores at out + m * mstride_o
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_chain_depth(Fin, F1, F2, pre, contract);
   if (index_mode == 0) index_mode = rowptr ? 1 : gwen_gcn_chain_index_mode(Fin, F1, F2, pre, contract);

@@ -134,6 +134,15 @@ int gwen_gcn_segments(const int32_t *rowptr, int64_t N, int64_t S, int32_t *rowp
  * bias: fp32 [F] or NULL.  relu: 0/1.
  * Terms are added sequentially in stored order with a rounded product per term (no FMA), so the
  * result is bitwise reproducible and equals a sequential CPU scatter-add in edge order.
+ *
+ * PITCHES AND MEMBER STRIDES, here and in every entry point below that takes an ld* or an mstride_* (all in
+ * elements): cell (m, r, c) of an operand is at base + m * mstride + r * ld + c.  An operand of `rows` rows of F
+ * elements at pitch ld (>= F) needs (rows - 1) * ld + F elements, and (members - 1) * mstride more for its members:
+ * nothing behind the last logical cell is read into a result or written, and no output cell outside the logical ones
+ * is written (row padding, gaps between members).  Members may interleave (mstride < rows * ld, e.g. ld = members * F,
+ * mstride = F) as long as no two logical cells coincide.  Entry points without an ld take contiguous rows (ld = F).
+ * K2 takes any pitch and base (vectors of 4 / 2 / 1 floats by what divides F, the pitches, the strides and the
+ * addresses); the kernels that move 16-byte vectors (K4, K5, K7, K8) say so and refuse other values with GWEN_EINVAL.
  * ------------------------------------------------------------------------------------------- */
 int gwen_gcn_propagate_f32(const int32_t *rowptr, const int32_t *col, const float *val,
                            const float *h, const float *bias, float *out, int64_t N, int64_t F,
@@ -304,6 +313,8 @@ int gwen_gcn_wide_layer_f32(const int32_t *t_rows, const uint16_t *t_lid, const 
  *   pre = 1:  out = act( A~ h + bias ) W1^T            h [.,Fin] already projected, bias [Fin], F2 = 0
  * rowptr/col/val: GROUPED arrays (rowptr NULL = uniform layout); x, out contiguous rows; widths in {16, 32, 64, 128};
  * contract: GWEN_CONTRACT_BF16X3 or GWEN_CONTRACT_BF16X6, as K4.  The re-bracketing changes fp32 rounding order only.
+ * Alignment: x, out, W1, W2 and bias 16-byte aligned; mstride_x and mstride_o (elements) multiples of 4 -- the kernel
+ * loads 16-byte vectors at x + m * mstride_x and stores them at out + m * mstride_o -- otherwise GWEN_EINVAL, as K4.
  * ------------------------------------------------------------------------------------------- */
 int gwen_gcn_chain_supported(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
 int gwen_gcn_chain_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,

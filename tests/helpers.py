@@ -6,6 +6,12 @@ import torch
 
 SEED = 23   # the reference's seed: /root/reference/src/gwen/config.json:14
 REL_TOL = 1e-4   # BASELINE.json north_star: "within 1e-4 rel-fp32"
+# rel_err bounds against fp64 per contraction, shared by the parity tests (test_gpu_parity.py) and the stride tests
+# (test_gpu_strides.py) of the same entry points
+LINEAR_TOL = {"fp32": 1e-5, "3xbf16": 2e-5, "bf16x6": 2e-6}                      # K3, gwen_gcn_linear_f32
+LINEAR_NN_TOL = {"bf16x6": 2e-6, "f16x3": 2e-6, "3xbf16": 3e-5}                  # gwen_gcn_linear_nn_f32
+GRAD_W_TOL = {None: 2e-6, "fp32": 2e-6, "bf16x6": 4e-6, "f16x3": 4e-6, "3xbf16": 3e-5}   # gwen_gcn_grad_weight_*_f32
+GRAD_B_TOL = 2e-6                                                                # gwen_gcn_grad_bias_*_f32
 
 
 def rel_err(a, b) -> float:

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (REL_TOL, SEED, csr_from_oracle, graph_cases, make_params, random_multigraph,
-                     rel_err)
+from helpers import (GRAD_B_TOL, GRAD_W_TOL, LINEAR_NN_TOL, LINEAR_TOL, REL_TOL, SEED, csr_from_oracle, graph_cases,
+                     make_params, random_multigraph, rel_err)
 
 pytestmark = pytest.mark.gpu
 
@@ -166,7 +166,7 @@ def test_linear(ga, cref, rows, fin, fout):
     w, b = make_params(fin, fout)
     got = ops.linear(x.to(DEV), w.to(DEV)).cpu()
     ref64 = x.double() @ w.double().t()
-    assert rel_err(got, ref64) <= 1e-5
+    assert rel_err(got, ref64) <= LINEAR_TOL["fp32"]
     chain = cref.linear(x.numpy(), w.numpy(), fma=True)           # k-ordered fmaf chain
     assert got.numpy().tobytes() == chain.tobytes(), "fp32 MFMA is not the k-ordered fmaf chain"
     got2 = ops.linear(x.to(DEV), w.to(DEV), b.to(DEV), relu=True).cpu()
@@ -175,10 +175,10 @@ def test_linear(ga, cref, rows, fin, fout):
     # 3xbf16 split variant: fp32-class accuracy, not bitwise
     got3 = ops.linear(x.to(DEV), w.to(DEV), b.to(DEV), relu=True, exact=False).cpu()
     ref3 = torch.relu(ref64 + b.double())
-    assert rel_err(got3, ref3) <= 2e-5
+    assert rel_err(got3, ref3) <= LINEAR_TOL["3xbf16"]
     # bf16x6 split (three images per operand, six terms): as close to fp64 as the exact fp32 MFMA, not bitwise
     got6 = ops.linear(x.to(DEV), w.to(DEV), b.to(DEV), relu=True, contract="bf16x6").cpu()
-    assert rel_err(got6, ref3) <= 2e-6
+    assert rel_err(got6, ref3) <= LINEAR_TOL["bf16x6"]
     assert rel_err(got6, ref3) <= rel_err(got3, ref3) + 1e-7
 
 
@@ -196,7 +196,7 @@ def test_linear_tall(ga, rows, fin, fout):
     w, b = w.to(DEV), b.to(DEV)
     got = ops.linear(x, w, b, relu=True, exact=False)
     ref = torch.relu(x.double() @ w.double().t() + b.double())
-    assert rel_err(got.cpu(), ref.cpu()) <= 2e-5
+    assert rel_err(got.cpu(), ref.cpu()) <= LINEAR_TOL["3xbf16"]
     for lo in (0, rows - 8000):                                   # 8 000 rows at a time: the short kernel
         part = ops.linear(x[lo:lo + 8000].contiguous(), w, b, relu=True, exact=False)
         assert torch.equal(part, got[lo:lo + 8000])
@@ -655,7 +655,7 @@ def test_grad_weight_every_contraction_vs_fp64(ga, rows, fout, fin):
     x = torch.randn(rows, fin, generator=gen)
     want = g.double().t() @ x.double()
     gd, xd = g.to(DEV), x.to(DEV)
-    for contract, tol in ((None, 2e-6), ("fp32", 2e-6), ("bf16x6", 4e-6), ("f16x3", 4e-6), ("3xbf16", 3e-5)):
+    for contract, tol in GRAD_W_TOL.items():
         got = ops.grad_weight(gd, xd, contract)
         assert rel_err(got, want) <= tol, (contract, rel_err(got, want))
         assert torch.equal(got, ops.grad_weight(gd, xd, contract)), contract
@@ -714,8 +714,8 @@ def test_grad_weight_bias_one_launch(ga, rows, fout, fin):
         assert torch.equal(runs[0][0], runs[1][0]) and torch.equal(runs[0][1], runs[1][1])
         w, b = runs[0]
         assert torch.equal(w, ops.grad_weight(g, x, contract)) or rel_err(w, ops.grad_weight(g, x, contract)) <= 1e-6
-        assert rel_err(w, g.double().t() @ x.double()) <= (4e-6 if contract == "bf16x6" else 3e-5)
-        assert rel_err(b, g.double().sum(0)) <= 2e-6, rel_err(b, g.double().sum(0))
+        assert rel_err(w, g.double().t() @ x.double()) <= GRAD_W_TOL[contract]
+        assert rel_err(b, g.double().sum(0)) <= GRAD_B_TOL, rel_err(b, g.double().sum(0))
 
 
 @pytest.mark.parametrize("fg,fx,members", [(64, 64, 1), (32, 16, 3), (16, 32, 2), (64, 32, 1), (128, 64, 1), (256, 256, 1)])
@@ -774,7 +774,7 @@ def test_linear_nn_weight_as_stored(ga, rows, k, n):
     wt = (torch.randn(k, n, generator=gen) / k ** 0.5).to(DEV)
     want = x.double() @ wt.double()
     # ("fp32": the transposed exact kernel, a k-ordered fp32 fmaf chain -- its rounding grows with the 16 384-long sum)
-    for contract, tol in (("bf16x6", 2e-6), ("f16x3", 2e-6), ("3xbf16", 3e-5), ("fp32", 2e-6 if k <= 1024 else 1e-5)):
+    for contract, tol in (*LINEAR_NN_TOL.items(), ("fp32", 2e-6 if k <= 1024 else 1e-5)):
         got = ops.linear_nn(x, wt, contract)
         assert got.shape == (rows, n)
         assert rel_err(got, want) <= tol, (contract, rel_err(got, want))
