@@ -91,6 +91,7 @@ MLP2_LN_EDGE, MLP2_LN_NODE = 0, 1                    # GWEN_MLP2_LN_* (include/g
 MASKED_L1, MASKED_MSE = 0, 1                         # GWEN_MASKED_* (include/gwen_hip.h)
 REGRID_NEAREST, REGRID_IDW = 0, 1                    # GWEN_REGRID_* (include/gwen_hip.h)
 CONSERVE_COVERED, CONSERVE_CELL = 0, 1               # GWEN_CONSERVE_*
+SHT_GRIDS = {"equiangular": 0, "equiangular-centred": 1, "gauss": 2}     # GWEN_SHT_* (include/gwen_hip.h)
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
 
@@ -252,6 +253,10 @@ SIGNATURES = {
     "gwen_cell_areas": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp]),
     "gwen_cell_overlap_areas": (_int, [_vp, _i64, _int, _vp, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gwen_cell_overlap_weights": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp, _vp]),
+    "gwen_sht_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "gwen_sht_analysis": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5 + [_vp, C.c_size_t, _vp]),
+    "gwen_sht_synthesis": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5 + [_vp, C.c_size_t, _vp]),
+    "gwen_sht_power_f64": (_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
 }
 
 

@@ -1,0 +1,318 @@
+"""Spherical harmonic transforms and power spectra of fields on a latitude-longitude grid, on the device.
+
+Convention (include/gwen_hip.h, "Spherical harmonic transforms"; tests/sht_ref.py restates it in numpy):
+
+    grid      rows ``(lat, lon)`` row-major, south to north, longitudes ``2 pi i / nlon`` -- the layout of
+              ``gridgraph.latlon_grid``.  Three latitude sets, each with quadrature weights ``w_j`` that sum to 1; a grid
+              point weighs ``q = w_j / nlon``:
+                  "equiangular"          the rows of ``latlon_grid(nlat, nlon, poles=True)``, Clenshaw-Curtis,
+                                         exact for ``lmax <= (nlat - 1) // 2``
+                  "equiangular-centred"  the rows of ``latlon_grid(nlat, nlon, poles=False)``, Fejer's first rule,
+                                         exact for ``lmax <= (nlat - 1) // 2``
+                  "gauss"                the ``nlat`` Gauss-Legendre latitudes, exact for ``lmax <= nlat - 1``
+              Always ``nlon >= 2 lmax + 1``, ``lmax <= 1023`` and ``nlat <= 2048``; the default ``lmax`` is the largest
+              the grid and ``nlon`` allow.
+    basis     real, 4 pi-normalised: ``Y_{l,m} = Pbar_l^m(sin lat) cos(m lon)`` for ``m >= 0`` and
+              ``Y_{l,-m} = Pbar_l^m(sin lat) sin(m lon)`` for ``m > 0``; the sphere mean of ``Y^2`` is 1.
+              ``Pbar_0^0 = 1``, ``Pbar_1^1 = sqrt(3) cos lat``, ``Pbar_m^m = sqrt((2m+1)/(2m)) cos lat Pbar_{m-1}^{m-1}``,
+              ``Pbar_{m+1}^m = sqrt(2m+3) sin lat Pbar_m^m`` and ``Pbar_l^m = a (sin lat Pbar_{l-1}^m - b Pbar_{l-2}^m)``
+              with ``a = sqrt((4 l^2 - 1) / (l^2 - m^2))``, ``b = sqrt(((l-1)^2 - m^2) / (4 (l-1)^2 - 1))``.
+    rows      the coefficient of ``(l, m)`` is row ``l^2 + l + m`` of ``T = (lmax + 1)^2``.
+    analysis  ``c_lm = sum_p q_p Y_lm(p) x_p``;  synthesis ``x_p = sum_lm c_lm Y_lm(p)``;  power ``S_l = sum_m c_lm^2``
+              (for a band-limited field ``sum_l S_l = sum_p q_p x_p^2``).
+
+Everything is accumulated in fp64 by two HIP kernels a transform (csrc/sht.hip): direct sums along every latitude ring
+against an ``nlon``-entry twiddle table, and a contraction over the latitudes with ``Pbar_l^m`` generated on the fly.
+Results are bitwise reproducible, whatever the batch and the workspace.  Nodes, weights and tables are made on the host
+in fp64 at construction; after it nothing synchronises with the host, so a call can be captured into a hipGraph once it has
+run eagerly.  There is no CPU fallback: CPU tensors raise RuntimeError.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor
+
+GRIDS = ("equiangular", "equiangular-centred", "gauss")
+MAX_LMAX = 1023
+MAX_NLAT = 2048
+
+
+def quadrature(grid: str, nlat: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(lat_deg [nlat], w [nlat])`` of a latitude set, south to north, fp64: the nodes symmetric about the equator to
+    the last bit, the weights of ``int_{-1}^{1} f(sin lat) d(sin lat) / 2`` (they sum to 1)."""
+    if grid not in GRIDS:
+        raise ValueError(f"grid must be one of {GRIDS} (got {grid!r})")
+    nlat = int(nlat)
+    if nlat < (2 if grid == "equiangular" else 1):
+        raise ValueError(f"nlat must be >= {2 if grid == 'equiangular' else 1} on the {grid} grid (got {nlat})")
+    k = np.arange(nlat, dtype=np.float64)
+    if grid == "gauss":
+        x, w = np.polynomial.legendre.leggauss(nlat)
+        x = 0.5 * (x - x[::-1])
+        lat = np.rad2deg(np.arcsin(x))
+    elif grid == "equiangular":
+        n = nlat - 1
+        lat = -90.0 + (180.0 / n) * k
+        lat[-1] = 90.0
+        lat = 0.5 * (lat - lat[::-1])
+        theta = np.pi * k / n
+        w = np.ones(nlat)
+        for j in range(1, n // 2 + 1):
+            w -= (1.0 if 2 * j == n else 2.0) / (4.0 * j * j - 1.0) * np.cos(2.0 * j * theta)
+        w *= 2.0 / n
+        w[0] *= 0.5
+        w[-1] *= 0.5
+    else:
+        lat = -90.0 + (180.0 / nlat) * (k + 0.5)
+        lat = 0.5 * (lat - lat[::-1])
+        theta = np.pi * (k + 0.5) / nlat
+        w = np.ones(nlat)
+        for j in range(1, nlat // 2 + 1):
+            w -= 2.0 / (4.0 * j * j - 1.0) * np.cos(2.0 * j * theta)
+        w *= 2.0 / nlat
+    w = 0.5 * (w + w[::-1])
+    return lat, w / w.sum()
+
+
+def max_degree(grid: str, nlat: int, nlon: int) -> int:
+    """The largest ``lmax`` the quadrature of ``grid`` and ``nlon`` longitudes resolve exactly, at most 1023."""
+    if grid not in GRIDS:
+        raise ValueError(f"grid must be one of {GRIDS} (got {grid!r})")
+    by_lat = nlat - 1 if grid == "gauss" else (nlat - 1) // 2
+    return min(by_lat, (nlon - 1) // 2, MAX_LMAX)
+
+
+def check_sizes(grid: str, nlat: int, nlon: int, lmax: Optional[int]) -> int:
+    """``lmax`` (the default filled in) after every size check; ValueError otherwise.  No device is touched."""
+    if grid not in GRIDS:
+        raise ValueError(f"grid must be one of {GRIDS} (got {grid!r})")
+    nlat, nlon = int(nlat), int(nlon)
+    if nlat < (2 if grid == "equiangular" else 1) or nlon < 1:
+        raise ValueError(f"nlat and nlon must be >= 1 (nlat >= 2 with poles); got {nlat}, {nlon}")
+    if nlat > MAX_NLAT:
+        raise ValueError(f"nlat <= {MAX_NLAT} (got {nlat})")
+    if nlat * nlon > 2 ** 31 - 1:
+        raise ValueError(f"nlat * nlon = {nlat * nlon} does not fit int32")
+    limit = max_degree(grid, nlat, nlon)
+    if lmax is None:
+        return limit
+    lmax = int(lmax)
+    if lmax < 0:
+        raise ValueError(f"lmax must be >= 0 (got {lmax})")
+    if lmax > MAX_LMAX:
+        raise ValueError(f"lmax <= {MAX_LMAX}: beyond it the recurrence needs rescaling (got {lmax})")
+    if nlon < 2 * lmax + 1:
+        raise ValueError(f"nlon >= 2 lmax + 1 = {2 * lmax + 1} (got {nlon})")
+    if lmax > limit:
+        raise ValueError(f"the {grid} quadrature on {nlat} latitudes is exact up to lmax = "
+                         f"{nlat - 1 if grid == 'gauss' else (nlat - 1) // 2} (got {lmax})")
+    return lmax
+
+
+def degree_index(lmax: int) -> np.ndarray:
+    """int64 ``[(lmax + 1)^2]``: the degree ``l`` of every coefficient row."""
+    return np.repeat(np.arange(lmax + 1, dtype=np.int64), 2 * np.arange(lmax + 1) + 1)
+
+
+def sectoral_seeds(lmax: int) -> np.ndarray:
+    """fp64 ``[lmax + 1]``: ``Pbar_m^m = seed[m] cos^m lat`` -- 1, sqrt(3), then ``seed[m-1] sqrt((2m+1)/(2m))``."""
+    seed = np.ones(lmax + 1, dtype=np.float64)
+    for m in range(1, lmax + 1):
+        seed[m] = np.sqrt(3.0) if m == 1 else np.sqrt((2.0 * m + 1.0) / (2.0 * m)) * seed[m - 1]
+    return seed
+
+
+def check_rows(name: str, t, rows: int, what: str) -> None:
+    """ValueError unless ``t`` is a tensor ``[..., rows, C]`` with ``1 <= C < 2^31``."""
+    if not isinstance(t, Tensor):
+        raise ValueError(f"{name} must be a tensor")
+    if t.dim() < 2 or t.shape[-2] != rows:
+        raise ValueError(f"{name} must be [..., {what} = {rows}, C], got {tuple(t.shape)}")
+    if t.shape[-1] < 1:
+        raise ValueError(f"{name} needs at least one channel")
+    if t.shape[-1] > 2 ** 31 - 1:
+        raise ValueError(f"C = {t.shape[-1]} does not fit int32")
+
+
+def _check_out_dtype(dtype) -> None:
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"gwen_amd: dtype must be float32 or float64 (got {dtype})")
+
+
+class SphericalHarmonics:
+    """The transforms of one grid and truncation (module docstring).  ``workspace_bytes`` bounds the fp64 intermediate
+    ``[chunk, nlat, 2 lmax + 1, C]``: the leading axes of a call, flattened into one batch, are cut into chunks that fit
+    (one item must: ValueError otherwise); the results do not depend on it."""
+
+    def __init__(self, nlat: int, nlon: int, device, lmax: Optional[int] = None, grid: str = "equiangular",
+                 workspace_bytes: int = 1 << 30):
+        self.lmax = check_sizes(grid, nlat, nlon, lmax)
+        self.nlat, self.nlon, self.grid = int(nlat), int(nlon), grid
+        self.workspace_bytes = int(workspace_bytes)
+        if self.workspace_bytes < 1:
+            raise ValueError(f"workspace_bytes must be positive (got {workspace_bytes})")
+        from .gridgraph import _device
+        self.device = _device(device)
+        self.rows = self.nlat * self.nlon
+        self.num_coefficients = (self.lmax + 1) ** 2
+        lat, w = quadrature(grid, self.nlat)
+        self._lat_deg = lat
+        phi = np.deg2rad(lat)
+        nodes = np.stack([np.sin(phi), np.cos(phi)], axis=1)
+        i = np.arange(self.nlon, dtype=np.float64)
+        tw = np.stack([np.cos(2.0 * np.pi * i / self.nlon), np.sin(2.0 * np.pi * i / self.nlon)], axis=1)
+        seed = sectoral_seeds(self.lmax)
+        dev = self.device
+        self._nodes = torch.from_numpy(np.ascontiguousarray(nodes)).to(dev)
+        self._twiddle = torch.from_numpy(np.ascontiguousarray(tw)).to(dev)
+        self._seed = torch.from_numpy(np.ascontiguousarray(seed)).to(dev)
+        self._lat_w = torch.from_numpy(np.ascontiguousarray(w / self.nlon)).to(dev)
+        self._weights = torch.from_numpy(np.repeat(w / self.nlon, self.nlon).astype(np.float32)).to(dev)
+        self._degrees = torch.from_numpy(degree_index(self.lmax)).to(dev)
+
+    # ---- tables -----------------------------------------------------------------------------------------------------
+    @property
+    def weights(self) -> Tensor:
+        """fp32 ``[nlat * nlon]``: the quadrature weight ``q`` of every grid point (sums to 1) -- the ``node_weights`` of
+        ``gwen_amd.losses`` and ``gwen_amd.products``."""
+        return self._weights
+
+    @property
+    def degrees(self) -> Tensor:
+        """int64 ``[T]``: the degree ``l`` of every coefficient row (per-degree weights, filters)."""
+        return self._degrees
+
+    @property
+    def positions(self) -> np.ndarray:
+        """float64 ``[nlat * nlon, 3]`` unit vectors, the form of ``latlon_grid(...)[0]`` (a ``Regridder`` target)."""
+        from .gridgraph import sphere_points
+        lon = (360.0 / self.nlon) * np.arange(self.nlon, dtype=np.float64)
+        return sphere_points(self._lat_deg[:, None], lon[None, :])
+
+    def index(self, l: int, m: int) -> int:
+        """The coefficient row of ``(l, m)``, ``-l <= m <= l <= lmax``: ``l^2 + l + m``."""
+        l, m = int(l), int(m)
+        if not 0 <= l <= self.lmax or abs(m) > l:
+            raise ValueError(f"need 0 <= l <= {self.lmax} and |m| <= l (got l = {l}, m = {m})")
+        return l * l + l + m
+
+    # ---- launches ---------------------------------------------------------------------------------------------------
+    def _check(self, name: str, t, rows: int, what: str, dtypes) -> None:
+        """Shapes (ValueError), then dtypes (TypeError), then devices (RuntimeError), as ``losses._check``."""
+        check_rows(name, t, rows, what)
+        if t.dtype not in dtypes:
+            raise TypeError(f"gwen_amd: {name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)} "
+                            f"(got {t.dtype})")
+        if not t.is_cuda:
+            raise RuntimeError(f"gwen_amd: {name} must live on a HIP device (no CPU fallback)")
+        if t.device != self.device:
+            raise RuntimeError(f"gwen_amd: {name} is on {t.device}, the transform's tables on {self.device}")
+
+    def _workspace(self, batch: int, c: int) -> Tensor:
+        from . import _lib
+        item = int(_lib.lib().gwen_sht_workspace_bytes(_lib.SHT_GRIDS[self.grid], self.nlat, self.nlon, self.lmax, c))
+        if item > self.workspace_bytes:
+            raise ValueError(f"workspace_bytes = {self.workspace_bytes} is below one item's intermediate ({item} bytes)")
+        items = min(max(batch, 1), self.workspace_bytes // item)
+        return torch.empty(items * item // 8, dtype=torch.float64, device=self.device)
+
+    def _launch(self, inverse: bool, src: Tensor, out_rows: int, dtype, weighted: bool) -> Tensor:
+        """One transform of ``src [..., rows, C]`` (contiguous) into a new ``[..., out_rows, C]`` of ``dtype``."""
+        from . import _lib
+        from .graph import _ptr, _stream
+        lead, c = src.shape[:-2], src.shape[-1]
+        batch = 1
+        for s in lead:
+            batch *= int(s)
+        out = torch.empty(*lead, out_rows, c, dtype=dtype, device=self.device)
+        if batch == 0:
+            return out
+        ws = self._workspace(batch, c)
+        fn = _lib.lib().gwen_sht_synthesis if inverse else _lib.lib().gwen_sht_analysis
+        with torch.cuda.device(self.device):
+            rc = fn(_ptr(src), int(src.dtype == torch.float64), _ptr(out), int(dtype == torch.float64), _ptr(self._nodes),
+                    _ptr(self._lat_w) if weighted else None, _ptr(self._twiddle), _ptr(self._seed),
+                    _lib.SHT_GRIDS[self.grid], batch, self.nlat, self.nlon, self.lmax, c, _ptr(ws), ws.numel() * 8,
+                    _stream(self.device))
+        _lib.check(rc, "gwen_sht_synthesis" if inverse else "gwen_sht_analysis")
+        return out
+
+    def analysis_launch(self, x: Tensor, dtype=torch.float32, weighted: bool = True) -> Tensor:
+        """``gwen_sht_analysis`` on a contiguous device tensor, no autograd: with the quadrature weights the analysis,
+        without them the adjoint of the synthesis."""
+        return self._launch(False, x, self.num_coefficients, dtype, weighted)
+
+    def synthesis_launch(self, c: Tensor, dtype=torch.float32, weighted: bool = False) -> Tensor:
+        """``gwen_sht_synthesis`` on a contiguous device tensor, no autograd: without weights the synthesis, with the
+        quadrature weights the adjoint of the analysis."""
+        return self._launch(True, c, self.rows, dtype, weighted)
+
+    # ---- public transforms ------------------------------------------------------------------------------------------
+    def analysis(self, x: Tensor, dtype=torch.float32) -> Tensor:
+        """``x [..., nlat * nlon, C]`` fp32 -> coefficients ``[..., T, C]`` in ``dtype`` (float32 or float64, rounded once
+        from the fp64 sums).  Differentiable in ``x``."""
+        self._check("x", x, self.rows, "nlat * nlon", (torch.float32,))
+        _check_out_dtype(dtype)
+        return _Analysis.apply(x, self, dtype)
+
+    def synthesis(self, c: Tensor, dtype=torch.float32) -> Tensor:
+        """Coefficients ``c [..., T, C]`` fp32 or fp64 -> the field ``[..., nlat * nlon, C]`` in ``dtype``.
+        Differentiable in ``c``."""
+        self._check("c", c, self.num_coefficients, "T", (torch.float32, torch.float64))
+        _check_out_dtype(dtype)
+        return _Synthesis.apply(c, self, dtype)
+
+    def power_spectrum(self, x: Optional[Tensor] = None, coeffs: Optional[Tensor] = None,
+                       dtype=torch.float64) -> Tensor:
+        """``[..., lmax + 1, C]``: the power ``S_l`` per degree of the field ``x`` (its coefficients stay fp64 on the
+        way) or of given ``coeffs [..., T, C]``.  Not differentiable: the inputs are read detached."""
+        from . import _lib
+        from .graph import _ptr, _stream
+        if (x is None) == (coeffs is None):
+            raise ValueError("power_spectrum takes exactly one of x and coeffs")
+        if x is not None:
+            self._check("x", x, self.rows, "nlat * nlon", (torch.float32,))
+        else:
+            self._check("coeffs", coeffs, self.num_coefficients, "T", (torch.float32, torch.float64))
+        _check_out_dtype(dtype)
+        if x is not None:
+            c64 = self.analysis_launch(x.detach().contiguous(), torch.float64)
+        else:
+            c64 = coeffs.detach().to(torch.float64).contiguous()
+        lead, c = c64.shape[:-2], c64.shape[-1]
+        power = torch.empty(*lead, self.lmax + 1, c, dtype=torch.float64, device=self.device)
+        batch = power.numel() // ((self.lmax + 1) * c)
+        if batch:
+            with torch.cuda.device(self.device):
+                rc = _lib.lib().gwen_sht_power_f64(_ptr(c64), _ptr(power), batch, self.lmax, c, _stream(self.device))
+            _lib.check(rc, "gwen_sht_power_f64")
+        return power if dtype == torch.float64 else power.to(dtype)
+
+
+class _Analysis(torch.autograd.Function):
+    """c = A x; A^T g = q * synthesis(g): the synthesis kernels with the quadrature weights on the way out."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, sh: SphericalHarmonics, dtype) -> Tensor:
+        ctx.sh = sh
+        return sh.analysis_launch(x.detach().contiguous(), dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.sh.synthesis_launch(g.contiguous(), torch.float32, weighted=True), None, None
+
+
+class _Synthesis(torch.autograd.Function):
+    """x = S c; S^T h = the analysis kernels with unit weights."""
+
+    @staticmethod
+    def forward(ctx, c: Tensor, sh: SphericalHarmonics, dtype) -> Tensor:
+        ctx.sh, ctx.dtype = sh, c.dtype
+        return sh.synthesis_launch(c.detach().contiguous(), dtype)
+
+    @staticmethod
+    def backward(ctx, h):
+        return ctx.sh.analysis_launch(h.contiguous(), ctx.dtype, weighted=False), None, None

@@ -1101,6 +1101,49 @@ int gwen_cell_overlap_areas(const double *src_cells, int64_t num_src, int vs, co
 int gwen_cell_overlap_weights(const int64_t *rowptr, const double *area, const double *dst_area, int64_t num_dst,
                               int64_t e, int mode, float *weights, double *coverage, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Spherical harmonic transforms on a latitude-longitude grid (csrc/sht.hip, gwen_amd.spectral).
+ *
+ *   x [batch, nlat * nlon, C]: rows (lat, lon) row-major, south to north, longitude 2 pi i / nlon.
+ *   coef [batch, (lmax + 1)^2, C]: row l^2 + l + m holds (l, m); m >= 0 goes with cos m lon, m < 0 with sin |m| lon.
+ *   Basis: real, 4 pi-normalised, Y_lm = Pbar_l^|m|(sin lat) {cos, sin}(|m| lon), sphere mean of Y^2 = 1, with
+ *         Pbar_m^m = seed[m] cos^m lat,  Pbar_l^m = a (sin lat Pbar_{l-1}^m - b Pbar_{l-2}^m),
+ *         a = sqrt((4 l^2 - 1) / (l^2 - m^2)),  b = sqrt(((l - 1)^2 - m^2) / (4 (l - 1)^2 - 1)),
+ *         generated in the kernels; nothing of size [m, l, lat] is ever stored.
+ *   Tables, all fp64 on the device: nodes [nlat, 2] = (sin lat, cos lat), 16-byte aligned; twiddle [nlon, 2] =
+ *         (cos, sin)(2 pi i / nlon), 16-byte aligned (the kernels index it by (m i) mod nlon and never call cos);
+ *         seed [lmax + 1], seed[0] = 1, seed[1] = sqrt 3, seed[m] = seed[m - 1] sqrt((2m + 1) / (2m)) from m = 2;
+ *         lat_w [nlat] or NULL (= ones): the latitude weight.
+ *
+ *   gwen_sht_analysis:  coef_lm = sum_j lat_w[j] Pbar_l^m(j) sum_i x[j, i] {cos, sin}(m lon_i).  With lat_w = the
+ *         quadrature weight over nlon it is the analysis; with NULL it is the adjoint of the synthesis.
+ *   gwen_sht_synthesis: x[j, i] = lat_w[j] sum_lm coef_lm Y_lm(j, i).  With NULL it is the synthesis; with the
+ *         quadrature weights it is the adjoint of the analysis.
+ *   x and coef are fp32 (x_f64 / coef_f64 = 0) or fp64 (1), inputs and outputs alike.  Every sum is accumulated in fp64
+ *   by one thread in index order; no atomics; results are bitwise equal run to run, whatever the batch, an item's place
+ *   in it or the workspace size.  A non-finite input stays in its (item, channel).
+ *   workspace: the fp64 ring sums [chunk, nlat, 2 lmax + 1, C]; gwen_sht_workspace_bytes() is the size of ONE item
+ *         (0 for bad sizes) and the batch is cut into chunks of workspace_bytes / that many items (GWEN_ENOSPACE
+ *         below one item).  8-byte aligned.
+ *   grid: which quadrature the sizes are checked against -- lmax <= (nlat - 1) / 2 on the equiangular grids,
+ *         lmax <= nlat - 1 on the Gauss grid.  Always nlon >= 2 lmax + 1, lmax <= 1023, nlat <= 2048.  A bad grid, size
+ *         or flag, a missing or misaligned pointer: GWEN_EINVAL; nlat nlon or C >= 2^31: GWEN_ERANGE; both before any HIP
+ *         call.  batch == 0 returns 0.  Element offsets are 64-bit.
+ *   gwen_sht_power_f64: power [batch, lmax + 1, C] fp64, S_l = sum_m coef_lm^2 in the order m = -l ... l.
+ * ------------------------------------------------------------------------------------------- */
+#define GWEN_SHT_EQUIANGULAR 0
+#define GWEN_SHT_EQUIANGULAR_CENTRED 1
+#define GWEN_SHT_GAUSS 2
+int64_t gwen_sht_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C);
+int gwen_sht_analysis(const void *x, int x_f64, void *coef, int coef_f64, const double *nodes, const double *lat_w,
+                      const double *twiddle, const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon,
+                      int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream);
+int gwen_sht_synthesis(const void *coef, int coef_f64, void *x, int x_f64, const double *nodes, const double *lat_w,
+                       const double *twiddle, const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon,
+                       int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream);
+int gwen_sht_power_f64(const double *coef, double *power, int64_t batch, int64_t lmax, int64_t C,
+                       gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
