@@ -129,6 +129,14 @@ SIGNATURES = {
     "gwen_gcn_layer_tuned2_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp]),
     "gwen_gcn_layer_index_mode": (_int, [_i64, _i64, _int]),
+    "gwen_gcn_packw_bytes": (_i64, [_i64, _i64, _int]),
+    "gwen_gcn_packw_f32": (_int, [_vp, _i64, _i64, _int, _vp, _vp]),
+    "gwen_gcn_layer_tuned3_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int, _vp]),
+    "gwen_gcn_layer_packed_mode": (_int, [_i64, _i64, _int]),
+    "gwen_gcn_layer_blocks_per_cu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                            _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int,
+                                            C.POINTER(C.c_int)]),
     "gwen_gcn_layer_supported": (_int, [_i64, _i64]),
     "gwen_gcn_chain_supported": (_int, [_i64, _i64, _i64, _int, _int]),
     "gwen_gcn_chain_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
@@ -141,6 +149,12 @@ SIGNATURES = {
     "gwen_gcn_chain_tuned2_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                          _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp]),
     "gwen_gcn_chain_index_mode": (_int, [_i64, _i64, _i64, _int, _int]),
+    "gwen_gcn_chain_tuned3_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
+                                         _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int, _vp]),
+    "gwen_gcn_chain_packed_mode": (_int, [_i64, _i64, _i64, _int, _int]),
+    "gwen_gcn_chain_blocks_per_cu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
+                                            _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int,
+                                            C.POINTER(C.c_int)]),
     "gwen_gcn_tiles64_count": (_i64, [_i64]),
     "gwen_gcn_tiles64": (_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gwen_cluster_rows64_host": (_int, [_vp, _vp, _i64, _i64, _vp]),
@@ -157,6 +171,10 @@ SIGNATURES = {
                                             _vp, _i64, _i64, _vp, C.POINTER(C.c_void_p),
                                             C.POINTER(LaunchInfo), C.c_int32, C.POINTER(C.c_int32),
                                             C.POINTER(C.c_void_p), _int]),
+    "gwen_gnn_forward_packed_f32": (_int, [C.POINTER(GraphDesc), C.POINTER(LayerDesc), C.c_int32, _vp, _vp,
+                                           _vp, _i64, _i64, _vp, C.POINTER(C.c_void_p),
+                                           C.POINTER(LaunchInfo), C.c_int32, C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), _int]),
     "gwen_gcn_layer_bwd_f32": (_int, [_vp] * 8 + [_i64] * 4 + [_int, _vp]),
     "gwen_gcn_layer_bwd_bias_rows": (_i64, [_i64, _i64]),
     "gwen_gcn_layer_bwd_bias_f32": (_int, [_vp] * 8 + [_i64] * 4 + [_int, _vp, _vp, _vp]),

@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgwen_hip.so")
-SOURCES = ["api.hip", "prep.hip", "propagate.hip", "linear.hip", "layer.hip", "chain.hip", "forward.hip", "grad.hip",
+SOURCES = ["api.hip", "prep.hip", "propagate.hip", "linear.hip", "layer.hip", "chain.hip", "packw.hip", "forward.hip", "grad.hip",
            "interact.hip", "interact_rows.hip", "interact_bwd.hip", "small.hip", "tiles.hip", "cluster.hip", "wide.hip", "hash.hip", "backward.hip", "loss.hip", "ensemble.hip",
            "noise.hip", "forcing.hip", "layernorm.hip", "attention.hip", "products.hip", "gridgraph.hip", "regrid.hip", "refloss.hip", "conserve.hip",
            "sht.hip"]

@@ -36,13 +36,23 @@ template <int K> using BF = gwen::BFv<K>;
 constexpr int pitch_bf16(int f) { return ((f / 2) % 16 == 8 ? f / 2 : f / 2 + 8) * 2; }
 
 // B fragments (NS images) of output-column tile j of a [FO, FI] weight: W[16 j + mi][KF (4 ks + mh) .. +KF)
-template <int FI, int NS>
+// PK: the images come from the weight's packed form (packw.hip) -- load_packed, then pin in the shadow; no raw, no split
+template <int FI, int NS, bool PK = false>
 struct Frag {
   static constexpr int KF = FI >= 32 ? 8 : 4;
   static constexpr int KS = FI / (4 * KF);
   using T = typename BF<KF>::T;
   T im[KS][NS];
-  float4_t raw[KS][KF / 4];                                // load_raw .. split: W as loaded (dead afterwards)
+  struct NoRaw {};
+  std::conditional_t<PK, NoRaw, float4_t[KS][KF / 4]> raw;   // load_raw .. split: W as loaded (dead afterwards); packed: none
+  // packed: the images themselves, [j][ks][s][lane][KF] -- one contiguous run per fragment (issued at the top of the kernel)
+  __device__ __forceinline__ void load_packed(const float *W, int j, int lane) {
+    const __bf16 *wp = reinterpret_cast<const __bf16 *>(W) + ((int64_t)j * KS * NS * 64 + lane) * KF;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int s = 0; s < NS; ++s) im[ks][s] = *reinterpret_cast<const T *>(wp + (ks * NS + s) * 64 * KF);
+  }
   // load in two halves: the loads alone (issued at the top of the kernel), and the split into images (in the shadow
   // of the first row loads, gather_rows.h); together they are load()
   __device__ __forceinline__ void load_raw(const float *W, int j, int mi, int mh) {
@@ -136,7 +146,9 @@ constexpr bool chain_pin(int fin, int f1, int f2, int ns, int ge) {
 // GE: gathered entries per group (gather_rows.h; 7 only on the uniform layout).  D: gather depth (gather_rows.h).
 // BRQ: Cfg's.  IM: index mode (gather_rows.h; 2 = index records: narrow kernels on the uniform layout only).  They sit
 // before NS because profile tooling keys this kernel's name on its first and its last template argument.
-template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int IM, int NS>
+// PK: packed W (packw.hip; narrow kernels only): W1 and W2 point to the weights' bf16 images in fragment order and the B
+// fragments are plain loads at the top of the kernel.  false compiles to the code the kernel had.
+template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int IM, bool PK, int NS>
 __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W1,
@@ -144,6 +156,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     int64_t mstride_x, int64_t mstride_o, int relu) {
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
   static_assert(IM == 1 || (IM == 2 && UNI && FIN <= 64 && F1 <= 64), "index records: narrow kernels, uniform layout");
+  static_assert(!PK || (FIN <= 64 && F1 <= 64), "packed W: narrow kernels");
   __shared__ __attribute__((aligned(16))) __bf16 lds[C::lds_elems];
   constexpr int kImg0 = C::BR * C::PB0, kImg1 = C::BR * C::PB1;
   __bf16 *t0 = lds;                                                      // aggregated rows: NS x [BR][PB0]
@@ -167,20 +180,26 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
   // without one the same 16 bytes of W1 are read (F1 * FIN floats: at least FIN, at least F1) and masked to +0.
   constexpr bool kPin = chain_pin(FIN, F1, F2, NS, GE);
   const int j1 = wave % C::NJ1;
-  Frag<FIN, NS> b1;
-  b1.load_raw(W1, j1, mi, mh);
+  Frag<FIN, NS, PK> b1;
+  if constexpr (PK) b1.load_packed(W1, j1, lane);
+  else b1.load_raw(W1, j1, mi, mh);
   const int j2 = wave % (F2 > 0 ? C::NJ2 : 1);
-  Frag<(F2 > 0 ? F1 : 16), NS> b2;
-  if constexpr (F2 > 0) b2.load_raw(W2, j2, mi, mh);
+  Frag<(F2 > 0 ? F1 : 16), NS, PK> b2;
+  if constexpr (F2 > 0) {
+    if constexpr (PK) b2.load_packed(W2, j2, lane);
+    else b2.load_raw(W2, j2, mi, mh);
+  }
   float4_t bpre = {0.f, 0.f, 0.f, 0.f}, bpost = {0.f, 0.f, 0.f, 0.f};
   float4_t braw = *reinterpret_cast<const float4_t *>((bias ? bias : W1) + (PRE ? gl * 4 : j1 * 16 + 4 * mh));
   // the mask waits for the load, so it is applied in the shadow callable, not here
   auto split_w = [&]() {
     (PRE ? bpre : bpost) = gwen::masked_f4(braw, bias != nullptr);
     gwen::pin_here(PRE ? bpre : bpost);                    // or mask and load sink to the value's first use
-    b1.split();
-    if constexpr (F2 > 0) b2.split();
-    if constexpr (kPin) {
+    if constexpr (!PK) {
+      b1.split();
+      if constexpr (F2 > 0) b2.split();
+    }
+    if constexpr (kPin || PK) {                            // packed: the image loads stay at the top, their values are due here
       b1.pin();
       if constexpr (F2 > 0) b2.pin();
     }
@@ -305,11 +324,12 @@ __global__ __launch_bounds__(256) void k_gather(
 // What one K5 launch (k_chain or k_gather) works on; gwen_gcn_chain_tuned_f32 fills it once.
 struct ChainArgs {
   const int32_t *rowptr, *col;                             // rowptr NULL = uniform layout
-  const float *val, *x, *W1, *W2, *bias;
+  const float *val, *x, *W1, *W2, *bias;                   // W1, W2: the weights, or their packed images (launch_br<.., PK>)
   float *out;
   int64_t N, members, msx, mso;
   int relu, entries;
   hipStream_t st;
+  int *probe;                                              // not NULL: launch nothing, store the kernel's blocks per CU
 };
 
 constexpr bool narrow(int fin, int f1) { return fin <= 64 && f1 <= 64; }
@@ -318,15 +338,17 @@ constexpr int gather_rows(int fin) { return 4 * Geom(fin, 0, 0, 2, 64).R; }   //
 // rows per block that the narrow kernels (Fin, F1 <= 64) can be asked for: whole gather passes; at 112 rows the largest
 // of them, 64 -> 64 -> 32 on bf16x3, holds 70 KiB of LDS.  Decides which launch_br are instantiated and, with the kernel's
 // own size, what block_rows a caller may force.
-constexpr bool rows_ok(int fin, int f1, int br) {
-  return narrow(fin, f1) && (br == 64 || br == 96 || br == 112) && br % Geom(fin, f1, 0, 2, 64).RB == 0;
+// pk: the packed-W kernels also have 80 rows (Fin = 64: five passes), as K4's -- only through the entry points that take
+// images; every older entry point keeps refusing 80
+constexpr bool rows_ok(int fin, int f1, int br, bool pk = false) {
+  return narrow(fin, f1) && (br == 64 || (br == 80 && pk) || br == 96 || br == 112) && br % Geom(fin, f1, 0, 2, 64).RB == 0;
 }
 
 // block_rows of gwen_gcn_chain_tuned_f32: 0, the kernel's own size, or 96 / 112 on the narrow kernels.  plain: k_gather
-constexpr bool rows_valid(int fin, int f1, bool plain, int br) {
+constexpr bool rows_valid(int fin, int f1, bool plain, int br, bool pk = false) {
   if (br == 0) return true;
   if (plain) return br == gather_rows(fin);
-  return br == Geom(fin, f1, 0, 2, 64).BR || rows_ok(fin, f1, br);
+  return br == Geom(fin, f1, 0, 2, 64).BR || rows_ok(fin, f1, br, pk);
 }
 
 // gathered entries: 7 only on the uniform layout, when the caller promises it, on widths up to 64
@@ -350,12 +372,17 @@ int launch_gather(const ChainArgs &a) {
   return run(&k_gather<FIN, true, 8, D>);
 }
 
-template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ, int IM>
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ, int IM, bool PK>
 int launch_br(const ChainArgs &a) {
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
   static_assert(C::geo.fits(kLdsCU), "one block must fit a CU's LDS");
   dim3 grid((unsigned)((a.N + C::BR - 1) / C::BR), (unsigned)a.members);
   auto run = [&](auto kernel) {
+    if (a.probe) {
+      GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(a.probe, reinterpret_cast<const void *>(kernel),
+                                                                  C::NWB * 64, 0));
+      return (int)GWEN_OK;
+    }
     kernel<<<grid, C::NWB * 64, 0, a.st>>>(a.rowptr, a.col, a.val, a.x, a.W1, a.W2, a.bias, a.out, (int32_t)a.N, a.msx,
                                            a.mso, a.relu);
     GWEN_LAUNCH_CHECK();
@@ -363,15 +390,20 @@ int launch_br(const ChainArgs &a) {
   };
   if constexpr (IM == 2) {                     // index records: the uniform layout, narrow kernels
     if (a.rowptr) return GWEN_EINVAL;
-    return a.entries == 7 ? run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 2, NS>)
-                          : run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 2, NS>);
+    return a.entries == 7 ? run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 2, PK, NS>)
+                          : run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 2, PK, NS>);
   }
-  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, 1, NS>);
+  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, 1, PK, NS>);
   if constexpr (narrow(FIN, F1)) {
-    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 1, NS>);
+    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 1, PK, NS>);
   }
-  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 1, NS>);
+  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 1, PK, NS>);
 }
+
+// Rows per block of a packed-W kernel (PK) at gather depth 2 where launch_ns would take 112; 0: the same.  64 -> 64 -> 32
+// on bf16x6: 80 rows (five passes, 38 400 B of LDS) measured 16.3 us against 17.4 at 112 and at 64 rows
+// (profiles/packw_kernel_ab_*); at 156 VGPRs it is three blocks per CU at either size.
+constexpr int packed_rows(int fin, int f1, int f2, int ns) { return fin == 64 && f1 == 64 && f2 == 32 && ns == 3 ? 80 : 0; }
 
 // block_rows: 0 = the library's choice; else the kernel's own size or 96 / 112 (rows_ok; checked by the extern "C" caller).
 // The library's choice is 64 rows (128 from 128 channels on).  K4's "smallest size whose grid is co-resident" finds no
@@ -379,9 +411,10 @@ int launch_br(const ChainArgs &a) {
 // 893 blocks) and 96 / 112 rows measured SLOWER at depth 1 (23.3 / 23.5 against 22.2 us), so depth 1 keeps 64.  At depth
 // 2 one member whose 64-row grid is more than one resident round runs 112-row blocks where the width allows it: the
 // two-deep gather fills and drains once per block (20.1 against 20.8 us).
-template <int FIN, int F1, int F2, bool PRE, int NS, int D, int IM>
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int IM, bool PK = false>
 int launch_ns(const ChainArgs &a, int block_rows) {
   static_assert(IM == 1 || narrow(FIN, F1), "index records: narrow kernels only");
+  static_assert(!PK || narrow(FIN, F1), "packed W: narrow kernels only");
   int brq = block_rows == 0 || block_rows == Cfg<FIN, F1, F2, PRE, NS>::BR ? 64 : block_rows;   // BRQ 64 = the own size
   if constexpr (D == 2 && rows_ok(FIN, F1, 112)) {
     if (block_rows == 0 && a.members == 1) {
@@ -391,19 +424,20 @@ int launch_ns(const ChainArgs &a, int block_rows) {
       static int per_cu[3] = {0, 0, 0};
       const int v = a.rowptr ? 2 : (a.entries == 7 ? 0 : 1);
       if (per_cu[v] == 0) {
-        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, 1, NS>)
-                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, IM, NS>)
-                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, IM, NS>);
+        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, 1, PK, NS>)
+                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, IM, PK, NS>)
+                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, IM, PK, NS>);
         int nbk = 0;
         GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k, Cfg<FIN, F1, F2, PRE, NS>::NWB * 64, 0));
         per_cu[v] = nbk < 1 ? 1 : nbk;
       }
-      if ((a.N + 63) / 64 > (int64_t)256 * per_cu[v]) brq = 112;
+      // a packed-W kernel: 80 rows where that measured faster (packed_rows)
+      if ((a.N + 63) / 64 > (int64_t)256 * per_cu[v]) brq = PK && packed_rows(FIN, F1, F2, NS) != 0 ? packed_rows(FIN, F1, F2, NS) : 112;
     }
   }
-  return gwen::dispatch(gwen::ints<64, 96, 112>{}, brq, [&](auto brv) {
+  return gwen::dispatch(gwen::ints<64, 80, 96, 112>{}, brq, [&](auto brv) {
     constexpr int BRQ = decltype(brv)::value;
-    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ, IM>(a);
+    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ, PK)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ, IM, PK>(a);
     else return (int)GWEN_EINVAL;
   });
 }
@@ -448,24 +482,55 @@ extern "C" int gwen_gcn_chain_index_mode(int64_t Fin, int64_t F1, int64_t F2, in
   return chain_index_mode(Fin, F1, F2, pre, gwen::images_of(contract));
 }
 
+// Whether the library's forward reads W1 / W2 as packed images (packw.hip; k_chain's PK) when the caller hands them over,
+// per (Fin, F1, F2, pre, images): on only where the kernel measured faster on the MI355X by the rule of the depth and index
+// tables ("Packed W"; profiles/packw_*): 64 -> 64 -> 32 (19.7 -> 17.4 us at 112 rows) and activation-first
+// 32 -> 16 (8.0 -> 7.0 us), both on bf16x6 -- the two forms of the c2 step.
+static constexpr bool chain_packed(int64_t fin, int64_t f1, int64_t f2, int pre, int ns) {
+  return ns == 3 && ((fin == 64 && f1 == 64 && f2 == 32 && !pre) || (fin == 32 && f1 == 16 && f2 == 0 && pre));
+}
+
+extern "C" int gwen_gcn_chain_packed_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract) {
+  if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return 0;
+  if (!narrow(Fin, F1) || F1 == 0) return 1;              // the form without a contraction reads no W
+  return chain_packed(Fin, F1, F2, pre, gwen::images_of(contract)) ? 2 : 1;
+}
+
 // entries = 7: the caller's promise (uniform layout, every row at most 7 stored entries), see gwen_gcn_layer_entries_f32
 // depth, block_rows, index_mode: 0 = the library's choice (chain_depth; launch_ns; chain_index_mode); none changes a
 // value.  index_mode 1: every lane loads its row's group; 2: index records -- narrow kernels (Fin, F1 <= 64) on the
 // uniform layout only, GWEN_EINVAL elsewhere
-extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                         const float *x, const float *W1, const float *W2,
-                                         const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
-                                         int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
-                                         int64_t mstride_o, int contract, int entries, int depth, int block_rows,
-                                         int index_mode, gwen_stream_t stream_) {
+// W1p, W2p, packed: the gwen_gcn_packw_f32 images of W1 and W2 and whether they are read.  1: the weights are read and
+// split in the kernel; 2: the images are read (W1 / W2 may be NULL) -- narrow kernels with a contraction only, and an
+// image for every weight the form has, GWEN_EINVAL otherwise; 0: the library's choice -- the images where all of them are
+// given and gwen_gcn_chain_packed_mode says 2.  No value changes.
+// probe: not NULL = launch nothing and store the blocks per CU that hipOccupancyMaxActiveBlocksPerMultiprocessor reports for
+// the kernel this call would launch (forms with a contraction only)
+static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *val,
+                       const float *x, const float *W1, const float *W2,
+                       const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                       int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                       int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                       int index_mode, const void *W1p, const void *W2p, int packed,
+                       gwen_stream_t stream_, int *probe) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
+  if (packed < 0 || packed > 2) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0) return GWEN_EINVAL;
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return GWEN_EINVAL;
   const bool plain = pre && F1 == 0;                       // activation-first, nothing chained: k_gather
-  if (!rows_valid(Fin, F1, plain, block_rows)) return GWEN_EINVAL;             // the one check of block_rows
   if (index_mode == 2 && (rowptr || !narrow(Fin, F1))) return GWEN_EINVAL;     // records: uniform layout, narrow kernels
+  const bool can_pack = !plain && narrow(Fin, F1);                             // packed W: narrow kernels that contract
+  const bool have_images = W1p && (F2 == 0 || W2p);
+  if (packed == 2 && (!can_pack || !have_images)) return GWEN_EINVAL;
+  if (packed == 0) packed = can_pack && have_images && gwen_gcn_chain_packed_mode(Fin, F1, F2, pre, contract) == 2 ? 2 : 1;
+  if (packed == 2 && (!gwen_aligned(W1p, 16) || (F2 > 0 && !gwen_aligned(W2p, 16)))) return GWEN_EINVAL;
+  if (!rows_valid(Fin, F1, plain, block_rows, packed == 2)) return GWEN_EINVAL;   // the one check of block_rows
+  if (packed == 2) {                                       // the images take the weights' places; the checks below hold
+    W1 = static_cast<const float *>(W1p);
+    W2 = F2 > 0 ? static_cast<const float *>(W2p) : W2;
+  }
   if (N == 0 || members == 0) return GWEN_OK;
   if (!col || !val || !x || (F1 > 0 && !W1) || !out || x == out || (F2 > 0 && !W2))
     return GWEN_EINVAL;                                    // rowptr NULL = uniform layout
@@ -476,8 +541,9 @@ extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *c
   if (N * Fin * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_chain_depth(Fin, F1, F2, pre, contract);
   if (index_mode == 0) index_mode = rowptr ? 1 : gwen_gcn_chain_index_mode(Fin, F1, F2, pre, contract);
+  if (probe && plain) return GWEN_EINVAL;
   const ChainArgs a{rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, mstride_o, relu, entries,
-                    gwen_stream(stream_)};
+                    gwen_stream(stream_), probe};
   using Widths = gwen::ints<16, 32, 64, 128>;
   using Depths = gwen::ints<1, 2>;
   using Modes = gwen::ints<1, 2>;
@@ -504,10 +570,14 @@ extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *c
                 return gwen::dispatch(Modes{}, index_mode, [&](auto iv) {                  // records: narrow only
                   constexpr int NS = decltype(nsv)::value, D = decltype(dv)::value, IM = decltype(iv)::value;
                   // bf16x6 only where its three images fit a CU's LDS (gwen_gcn_chain_supported refuses the others)
-                  if constexpr (Geom(FI, FA, FB, NS, 64).fits(kLdsCU) && ((D == 1 && IM == 1) || narrow(FI, FA)))
+                  if constexpr (Geom(FI, FA, FB, NS, 64).fits(kLdsCU) && ((D == 1 && IM == 1) || narrow(FI, FA))) {
+                    if constexpr (narrow(FI, FA)) {
+                      if (packed == 2) return launch_ns<FI, FA, FB, PRE, NS, D, IM, true>(a, block_rows);
+                    }
                     return launch_ns<FI, FA, FB, PRE, NS, D, IM>(a, block_rows);
-                  else
+                  } else {
                     return (int)GWEN_EINVAL;
+                  }
                 });
               });
             });
@@ -518,6 +588,39 @@ extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *c
       });
     });
   });
+}
+
+extern "C" int gwen_gcn_chain_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W1, const float *W2,
+                                         const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                         int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                         int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                         int index_mode, const void *W1p, const void *W2p, int packed,
+                                         gwen_stream_t stream_) {
+  return chain_tuned(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x, mstride_o,
+                     contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, stream_, nullptr);
+}
+
+extern "C" int gwen_gcn_chain_blocks_per_cu(const int32_t *rowptr, const int32_t *col, const float *val,
+                                            const float *x, const float *W1, const float *W2,
+                                            const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                            int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                            int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                            int index_mode, const void *W1p, const void *W2p, int packed,
+                                            int *blocks_per_cu) {
+  if (!blocks_per_cu || N <= 0 || members <= 0) return GWEN_EINVAL;
+  return chain_tuned(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x, mstride_o,
+                     contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, nullptr, blocks_per_cu);
+}
+
+extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W1, const float *W2,
+                                         const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                         int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                         int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                         int index_mode, gwen_stream_t stream_) {
+  return gwen_gcn_chain_tuned3_f32(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x,
+                                   mstride_o, contract, entries, depth, block_rows, index_mode, nullptr, nullptr, 0, stream_);
 }
 
 extern "C" int gwen_gcn_chain_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,

@@ -75,12 +75,19 @@ extern "C" int64_t gwen_gnn_forward_scratch_floats(int64_t N, int64_t members,
 
 // entries: what the K4 / K5 launches are told about the grouped layout (gwen_gcn_layer_entries_f32): 8, or 7 when
 // g_rowptr is NULL and every row of the graph holds at most 7 stored entries (gwen_gcn_max_entries)
-extern "C" int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
-                                            int32_t n_layers, const float *x, float *out, float *scratch,
-                                            int64_t scratch_floats, int64_t members, gwen_stream_t stream,
-                                            void **events, gwen_launch_info *info, int32_t max_launches,
-                                            int32_t *n_launches, float *const *acts, int entries) {
-  if (!graph || (entries != 7 && entries != 8)) return GWEN_EINVAL;
+// packw, packed: the packed images of the layers' weights (packw.hip) for the K4 / K5 launches and whether they are read
+// (gwen_gcn_layer_tuned3_f32); the training forward reads none
+extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
+                                           int32_t n_layers, const float *x, float *out, float *scratch,
+                                           int64_t scratch_floats, int64_t members, gwen_stream_t stream,
+                                           void **events, gwen_launch_info *info, int32_t max_launches,
+                                           int32_t *n_launches, float *const *acts, int entries,
+                                           const void *const *packw, int packed) {
+  if (!graph || (entries != 7 && entries != 8) || packed < 0 || packed > 2) return GWEN_EINVAL;
+  if (acts || packed == 1) packw = nullptr;
+  // layer i's images; a launch without one for every weight it contracts with splits in the kernel (packed = 1)
+  auto img = [&](int32_t i) -> const void * { return packw && i < n_layers ? packw[i] : nullptr; };
+  auto mode = [&](const void *a, const void *b) { return packed == 2 ? (a && b ? 2 : 1) : packed; };
   const int64_t N = graph->N;
   const int32_t *rowptr = graph->rowptr, *col = graph->col, *g_rowptr = graph->g_rowptr,
                 *g_col = graph->g_col;
@@ -156,9 +163,10 @@ extern "C" int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_
       float *dst = acts ? acts[i] : ((last) ? out : buf[nbuf++ & 1]);
       if (chain) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fo, layers[i + 1].fout));
-        GWEN_TRY(gwen_gcn_chain_entries_f32(g_rowptr, g_col, g_val, cur, layers[i + 1].W, nullptr, L.bias,
+        GWEN_TRY(gwen_gcn_chain_tuned3_f32(g_rowptr, g_col, g_val, cur, layers[i + 1].W, nullptr, L.bias,
                                     dst, N, fo, layers[i + 1].fout, 0, 1, L.relu, members, N * fo,
-                                    N * layers[i + 1].fout, cn, entries, stream));
+                                    N * layers[i + 1].fout, cn, entries, 0, 0, 0, img(i + 1), nullptr,
+                                    mode(img(i + 1), img(i + 1)), stream));
         GWEN_TRY(after());
         projected = true;
       } else if (have_grouped && gwen_gcn_chain_supported(fo, 0, 0, 1, GWEN_CONTRACT_BF16X3)) {
@@ -201,16 +209,20 @@ extern "C" int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_
       float *dst = acts ? acts[i] : ((last && !chain) ? out : buf[nbuf++ & 1]);
       if (chain) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fi, layers[i + 1].fout));
-        GWEN_TRY(gwen_gcn_chain_entries_f32(g_rowptr, g_col, g_val, cur, L.W, layers[i + 1].W, L.bias, dst,
+        GWEN_TRY(gwen_gcn_chain_tuned3_f32(g_rowptr, g_col, g_val, cur, L.W, layers[i + 1].W, L.bias, dst,
                                     N, fi, fo, layers[i + 1].fout, 0, L.relu, members, N * fi,
-                                    N * layers[i + 1].fout, cc, entries, stream));
+                                    N * layers[i + 1].fout, cc, entries, 0, 0, 0, img(i), img(i + 1),
+                                    mode(img(i), img(i + 1)), stream));
         GWEN_TRY(after());
         projected = true;
       } else {
         GWEN_TRY(before(GWEN_KIND_LAYER, i, fi, fo));
-        GWEN_TRY(gwen_gcn_layer_entries_f32(g_rowptr, g_col, g_val, cur, L.W, L.bias, dst, N, fi, fo, fi, fo,
+        // images exist on a bf16 split at widths up to 64 only: the fp32-input MFMA and the wide layers get none
+        const void *wp = o == GWEN_ORDER_FUSED_EXACT || fi > 64 || fo > 64 ? nullptr : img(i);
+        GWEN_TRY(gwen_gcn_layer_tuned3_f32(g_rowptr, g_col, g_val, cur, L.W, L.bias, dst, N, fi, fo, fi, fo,
                                     members, N * fi, N * fo, L.relu,
-                                    o == GWEN_ORDER_FUSED_EXACT ? GWEN_CONTRACT_F32 : cc, entries, stream));
+                                    o == GWEN_ORDER_FUSED_EXACT ? GWEN_CONTRACT_F32 : cc, entries, 0, 0, 0, wp,
+                                    mode(wp, wp), stream));
         GWEN_TRY(after());
       }
       cur = dst;
@@ -243,6 +255,15 @@ extern "C" int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_
 #undef GWEN_TRY
   if (n_launches) *n_launches = nl;
   return GWEN_OK;
+}
+
+extern "C" int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_layer_desc *layers,
+                                            int32_t n_layers, const float *x, float *out, float *scratch,
+                                            int64_t scratch_floats, int64_t members, gwen_stream_t stream,
+                                            void **events, gwen_launch_info *info, int32_t max_launches,
+                                            int32_t *n_launches, float *const *acts, int entries) {
+  return gwen_gnn_forward_packed_f32(graph, layers, n_layers, x, out, scratch, scratch_floats, members, stream, events,
+                                     info, max_launches, n_launches, acts, entries, nullptr, 0);
 }
 
 extern "C" int gwen_gnn_forward_f32(const gwen_graph *graph, const gwen_layer_desc *layers,

@@ -100,8 +100,12 @@ constexpr bool layer_prologue(int fin, int fout, int ns) { return !(fin == 16 &&
 // GE: gathered entries per group (gather_rows.h); 7 only on the uniform layout.
 // D: gather depth (gather_rows.h): passes of row loads a wave keeps in flight; the backward runs D = 1.
 // IM: index mode (gather_rows.h): 2 = one record load per row and pass, broadcast in the lane group; narrow forward
-// kernels on the uniform layout only.  The last argument, so that every other kernel keeps its name but for a ", 1".
-template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1, int IM = 1>
+// kernels on the uniform layout only.  Behind the older arguments, so that every other kernel keeps its name but for a ", 1".
+// PK: packed W (packw.hip; narrow forward kernels on a bf16 split only): `W` points to the weight's bf16 images in fragment
+// order, cut once per weight version, and this wave's B fragments are plain 16-byte loads at the top of the kernel -- no
+// raw fp32 W, no split.  false compiles to the code the kernel had.
+template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1, int IM = 1,
+          bool PK = false>
 __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void k_layer(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W,
@@ -110,6 +114,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
     const float *__restrict__ mask = nullptr, float *__restrict__ bsum_out = nullptr, int32_t chunks_per_member = 0) {
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
   static_assert(IM == 1 || (IM == 2 && UNI && !BWD && FIN <= 64 && FOUT <= 64), "index records: narrow forward, uniform layout");
+  static_assert(!PK || (NS > 0 && !BWD && FIN <= 64 && FOUT <= 64), "packed W: narrow forward on a bf16 split");
   constexpr bool SPLIT = NS > 0;
   constexpr int NI = SPLIT ? NS : 1;
   __shared__ __attribute__((aligned(16))) char lds_raw[C::lds_bytes];
@@ -136,14 +141,23 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   // loads have left.  W then costs the block no round trip of its own: a block is indices, then rows.  The persistent
   // wide form and the backward keep the prologue they had: W split at once, above the chunk loop.
   constexpr bool kPersist = FIN * FOUT >= 128 * 128;
-  constexpr bool kOnce = !kPersist && !BWD && layer_prologue(FIN, FOUT, NS);   // the narrow forward: one chunk per block
-  constexpr bool kShadow = kOnce && SPLIT;
+  constexpr bool kOnce = !kPersist && !BWD && (PK || layer_prologue(FIN, FOUT, NS));   // the narrow forward: one chunk per block
+  constexpr bool kShadow = kOnce && SPLIT && !PK;
   const int j = wave % C::NJ;
   const float *wrow = W + (int64_t)(j * 16 + mi) * FIN;
   float2_t bfr[SPLIT ? 1 : C::NQ];
   typename BF<C::KF>::T bw[SPLIT ? C::KS : 1][NI];                       // W images per k-step
   float4_t wraw[kShadow ? C::KS : 1][kShadow ? C::KF / 4 : 1];   // kShadow: W as loaded
-  if constexpr (kShadow) {
+  if constexpr (PK) {
+    // the images themselves, [j][ks][s][lane][KF]: one contiguous run per fragment, nothing to split
+    using FT = typename BF<C::KF>::T;
+    const __bf16 *wp = reinterpret_cast<const __bf16 *>(W) + ((int64_t)j * C::KS * NI * 64 + lane) * C::KF;
+#pragma unroll
+    for (int ks = 0; ks < C::KS; ++ks)
+#pragma unroll
+      for (int s_ = 0; s_ < NI; ++s_)
+        bw[ks][s_] = *reinterpret_cast<const FT *>(wp + (ks * NI + s_) * 64 * C::KF);
+  } else if constexpr (kShadow) {
 #pragma unroll
     for (int ks = 0; ks < C::KS; ++ks)
 #pragma unroll
@@ -172,14 +186,20 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
     if (bias) bv4 = *reinterpret_cast<const float4_t *>(bias + j * 16 + 4 * mh);
   } else {
     // never a load under a condition (gather_rows.h): without a bias the same 16 bytes of W are read (W holds
-    // Fout * Fin >= Fout floats) and masked to +0 -- the value bv4 has always had then -- in the shadow callable:
-    // masked here, the mask would wait for the load in front of the first index request
+    // Fout * Fin >= Fout floats; packed: at least as many bytes) and masked to +0 -- the value bv4 has always had then --
+    // in the shadow callable: masked here, the mask would wait for the load in front of the first index request
     bv4 = *reinterpret_cast<const float4_t *>((bias ? bias : W) + j * 16 + 4 * mh);
     __builtin_amdgcn_sched_barrier(0);                     // the raw loads stay in front of the first index request
   }
   auto split_w = [&]() {                                   // in the first row loads' shadow (kOnce)
     bv4 = gwen::masked_f4(bv4, bias != nullptr);
     gwen::pin_here(bv4);                                   // or mask and load sink to the epilogue
+    if constexpr (PK) {                                    // the image loads stay at the top: their values are due here
+#pragma unroll
+      for (int ks = 0; ks < C::KS; ++ks)
+#pragma unroll
+        for (int s_ = 0; s_ < NI; ++s_) gwen::pin_here(bw[ks][s_]);
+    }
     if constexpr (kShadow) {                               // raw W -> images
 #pragma unroll
       for (int ks = 0; ks < C::KS; ++ks) {
@@ -305,12 +325,13 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
 // What one K4 launch works on; the forward and the backward entry points fill it once.
 struct LayerArgs {
   const int32_t *rowptr, *col;                             // rowptr NULL = uniform layout
-  const float *val, *x, *W, *bias;
+  const float *val, *x, *W, *bias;                         // W: the weight, or its packed images (launch_rows<.., PK>)
   float *out;
   int64_t N, ldo, members, msx, mso;
   int relu;
   hipStream_t st;
   float *agg_out; const float *mask; float *bsum_out; int64_t *chunks_out; bool bwd;   // the backward's: see k_layer
+  int *probe;                                              // not NULL: launch nothing, store resident_blocks' blocks per CU
 };
 
 constexpr bool narrow(int fin, int fout) { return fin <= 64 && fout <= 64; }
@@ -319,24 +340,33 @@ constexpr bool narrow(int fin, int fout) { return fin <= 64 && fout <= 64; }
 // bytes; 256: 64 rows keep two blocks per CU in LDS (bf16x3), and 64 rows at 256 channels on bf16x6 as well
 constexpr int wide_brmin(int fin) { return fin == 128 ? 128 : 64; }
 
+// Rows per block of a packed-W kernel (PK) at gather depth 2 when no block size makes the grid co-resident, where that is
+// not the 112 rows of the kernels that split W themselves; 0: the same.  64 -> 64 on bf16x6: 80 rows -- 38 400 B of LDS,
+// so four blocks fit a CU where the 53 760 B of a 112-row block stop at three whatever the registers (116 VGPRs: four
+// waves per SIMD) -- measured 14.5 us against 15.5 at 112 and 15.6 at 64 rows (profiles/packw_kernel_ab_*).
+constexpr int packed_rows(int fin, int fout, int ns) { return fin == 64 && fout == 64 && ns == 3 ? 80 : 0; }
+
 // Which rows per block exist for a shape: narrow layers 64 / 96 / 112 / 128 that are whole gather passes, wide layers
 // the kernel's one size.  Decides which launch_rows are instantiated and what block_rows a caller may force.
-constexpr bool rows_ok(int fin, int fout, int br) {
+// pk: the packed-W kernels also have 80 rows (Fin = 64: five passes) -- the largest block of 64 -> 64 on bf16x6 of which
+// four fit a CU's LDS (38 400 B each; 96 rows and more: three).  Forced through block_rows, and the library's own fallback
+// size where packed_rows() names it (launch()); never a candidate of the co-resident rule.
+constexpr bool rows_ok(int fin, int fout, int br, bool pk = false) {
   if (!narrow(fin, fout)) return br == Geom(fin, fout, 0, wide_brmin(fin)).BR;
-  return (br == 64 || br == 96 || br == 112 || br == 128) && br % Geom(fin, fout, 0, br).RB == 0;
+  return (br == 64 || (br == 80 && pk) || br == 96 || br == 112 || br == 128) && br % Geom(fin, fout, 0, br).RB == 0;
 }
 
 // Blocks of this instantiation that are resident at once.  Probed once per instantiation (function-local static): a warm
 // call makes no HIP query, so the launchers stay capturable.  The UNIFORM kernel is probed whichever layout is launched:
 // the block-rows choice of launch() on a non-uniform layout has always been made with the uniform kernel's occupancy.
 // The index mode is part of the instantiation: a record kernel holds fewer registers.
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK>
 int resident_blocks(int64_t &resident) {
   static int per_cu = 0;
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM>),
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK>),
         Cfg<FIN, FOUT, NS, BRMIN>::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
@@ -344,11 +374,12 @@ int resident_blocks(int64_t &resident) {
   return GWEN_OK;
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK>
 int launch_rows(const LayerArgs &a) {
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
   int64_t resident = 0;
-  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM>(resident); if (rc != GWEN_OK) return rc; }
+  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM, PK>(resident); if (rc != GWEN_OK) return rc; }
+  if (a.probe) { *a.probe = (int)(resident / 256); return GWEN_OK; }
   int64_t blocks = (a.N + C::BR - 1) / C::BR;
   const int64_t chunks_pm = blocks;                        // chunks of BR rows per member (bsum_out: one partial row each)
   float *bsum_out = C::geo.wide ? nullptr : a.bsum_out;    // the persistent form: no fused column sums (see the kernel)
@@ -363,32 +394,33 @@ int launch_rows(const LayerArgs &a) {
   };
   if constexpr (IM == 2) {                     // index records: the forward on the uniform layout, nothing else
     if (a.bwd || a.rowptr) return GWEN_EINVAL;
-    return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, 2>);
+    return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, 2, PK>);
   }
   if (a.bwd) {                                 // the backward runs on the layer's own split (bf16x3 / bf16x6), GE = 8, D = 1
-    if constexpr ((NS == 2 || NS == 3) && GE == 8 && D == 1)
+    if constexpr ((NS == 2 || NS == 3) && GE == 8 && D == 1 && !PK)
       return a.rowptr ? run(&k_layer<FIN, FOUT, NS, BRMIN, false, true>) : run(&k_layer<FIN, FOUT, NS, BRMIN, true, true>);
     else
       return GWEN_EINVAL;
   }
   // uniform layout (no rowptr): row r is the group at 8 r; only there may the 8th slot go ungathered (GE = 7)
-  return a.rowptr ? run(&k_layer<FIN, FOUT, NS, BRMIN, false, false, 8, D>)
-                  : run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D>);
+  return a.rowptr ? run(&k_layer<FIN, FOUT, NS, BRMIN, false, false, 8, D, 1, PK>)
+                  : run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, 1, PK>);
 }
 
 // block_rows: 0 = the choice below; else forced (rows_ok, checked by the extern "C" caller)
-template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1>
+template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1, bool PK = false>
 int launch(const LayerArgs &a, int block_rows) {
   static_assert(GE == 8 || narrow(FIN, FOUT), "7 gathered entries: narrow layers only");
   static_assert(IM == 1 || narrow(FIN, FOUT), "index records: narrow layers only");
   static_assert(D == 1 || narrow(FIN, FOUT), "gather depth 2: narrow layers only");
+  static_assert(!PK || (narrow(FIN, FOUT) && NS > 0), "packed W: narrow layers on a bf16 split only");
   if constexpr (!narrow(FIN, FOUT)) {
-    return launch_rows<FIN, FOUT, NS, wide_brmin(FIN), GE, D, 1>(a);
+    return launch_rows<FIN, FOUT, NS, wide_brmin(FIN), GE, D, 1, false>(a);
   } else {
     // f(BRV) for the block size br, where that size exists for this shape
     auto with_rows = [&](int br, auto &&f) {
-      return gwen::dispatch(gwen::ints<64, 96, 112, 128>{}, br, [&](auto brv) {
-        if constexpr (rows_ok(FIN, FOUT, decltype(brv)::value)) return f(brv);
+      return gwen::dispatch(gwen::ints<64, 80, 96, 112, 128>{}, br, [&](auto brv) {
+        if constexpr (rows_ok(FIN, FOUT, decltype(brv)::value, PK)) return f(brv);
         else return (int)GWEN_EINVAL;
       });
     };
@@ -403,11 +435,12 @@ int launch(const LayerArgs &a, int block_rows) {
     int rc = GWEN_OK, br = block_rows;
     auto fits = [&](int c, int64_t work) {                 // the grid of c-row blocks is co-resident (or rc says why not)
       int64_t res = 0;
-      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM>(res); });
+      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK>(res); });
       return rc != GWEN_OK || (work + c - 1) / c <= res;
     };
     if (br == 0) {
       br = D == 2 && rows_ok(FIN, FOUT, 112) ? 112 : 64;   // what is left when no size is co-resident
+      if constexpr (PK && D == 2 && packed_rows(FIN, FOUT, NS) != 0) br = packed_rows(FIN, FOUT, NS);
       if (fits(64, a.N * a.members) || a.members > 1) {
         br = 64;
       } else {
@@ -416,7 +449,7 @@ int launch(const LayerArgs &a, int block_rows) {
       }
       if (rc != GWEN_OK) return rc;
     }
-    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM>(a); });
+    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK>(a); });
   }
 }
 
@@ -465,25 +498,49 @@ extern "C" int gwen_gcn_layer_index_mode(int64_t Fin, int64_t Fout, int exact) {
   return layer_index_mode(Fin, Fout, gwen::images_of(exact));
 }
 
+// Whether the library's forward reads W as packed images (packw.hip; k_layer's PK) when the caller hands them over, per
+// (Fin, Fout, images): on only where the kernel measured faster on the MI355X by the rule of the depth and index tables
+// ("Packed W"; profiles/packw_*): 64 -> 64 on bf16x6 (16.7 -> 15.5 us at 112 rows).  32 -> 64 holds 92
+// VGPRs against 72 with the images live across the gather and measured slower (11.9 -> 12.2 us), 16 -> 32 the same
+// inside its spread (7.80 / 7.85): both keep the split in the kernel.
+static constexpr bool layer_packed(int64_t fin, int64_t fout, int ns) { return fin == 64 && fout == 64 && ns == 3; }
+
+extern "C" int gwen_gcn_layer_packed_mode(int64_t Fin, int64_t Fout, int exact) {
+  if (!gwen_gcn_layer_supported(Fin, Fout) || exact < 0 || exact > 2) return 0;
+  if (!narrow(Fin, Fout) || gwen::images_of(exact) == 0) return 1;
+  return layer_packed(Fin, Fout, gwen::images_of(exact)) ? 2 : 1;
+}
+
 // entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
 // kernels turn into one gather less per row; every other shape and layout gathers whole groups.
 // depth, block_rows, index_mode: 0 = the library's choice (layer_depth; the co-resident grid of launch();
 // layer_index_mode); none changes a value.  index_mode 1: every lane loads its row's group; 2: index records -- narrow
 // layers on the uniform layout only, GWEN_EINVAL elsewhere
-extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,
-                                         const float *x, const float *W, const float *bias, float *out,
-                                         int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
-                                         int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
-                                         int exact, int entries, int depth, int block_rows, int index_mode,
-                                         gwen_stream_t stream_) {
+// Wp, packed: the gwen_gcn_packw_f32 images of W and whether they are read.  1: W is read and split in the kernel; 2: the
+// images are read (W may be NULL) -- narrow layers on a bf16 split only, GWEN_EINVAL elsewhere or without images;
+// 0: the library's choice -- the images where they are given and gwen_gcn_layer_packed_mode says 2.  No value changes.
+// probe: not NULL = launch nothing and store the blocks per CU that hipOccupancyMaxActiveBlocksPerMultiprocessor reports for
+// the kernel this call would launch (the uniform-layout kernel, as resident_blocks has always asked)
+static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *val,
+                       const float *x, const float *W, const float *bias, float *out,
+                       int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                       int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                       int exact, int entries, int depth, int block_rows, int index_mode,
+                       const void *Wp, int packed, gwen_stream_t stream_, int *probe) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
+  if (packed < 0 || packed > 2) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
   if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
-  if (block_rows != 0 && !rows_ok(Fin, Fout, block_rows)) return GWEN_EINVAL;   // the one check of block_rows
   if (index_mode == 2 && (rowptr || !narrow(Fin, Fout))) return GWEN_EINVAL;    // records: uniform layout, narrow layers
+  const bool can_pack = narrow(Fin, Fout) && gwen::images_of(exact) > 0;        // packed W: narrow layers, bf16 splits
+  if (packed == 2 && (!can_pack || !Wp)) return GWEN_EINVAL;
+  if (packed == 0) packed = Wp && can_pack && gwen_gcn_layer_packed_mode(Fin, Fout, exact) == 2 ? 2 : 1;
+  if (packed == 2 && !gwen_aligned(Wp, 16)) return GWEN_EINVAL;
+  if (block_rows != 0 && !rows_ok(Fin, Fout, block_rows, packed == 2)) return GWEN_EINVAL;   // the one check of block_rows
   if (N == 0 || members == 0) return GWEN_OK;
+  if (packed == 2 && !W) W = static_cast<const float *>(Wp);                     // never read then; the checks below hold
   if (!col || !val || !x || !W || !out || x == out) return GWEN_EINVAL;   // rowptr NULL = uniform
   if (N >= (int64_t(1) << 28) || members > 65535) return GWEN_ERANGE;     // 8 N must fit int32
   if (!gwen_aligned(x, 16) || !gwen_aligned(out, 16) || !gwen_aligned(W, 16) || ldx != Fin ||
@@ -493,15 +550,21 @@ extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *c
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_layer_depth(Fin, Fout, exact);
   if (index_mode == 0) index_mode = rowptr ? 1 : gwen_gcn_layer_index_mode(Fin, Fout, exact);
   const int ge = entries == 7 && !rowptr ? 7 : 8;          // 7 on the uniform layout when the caller promises it
-  const LayerArgs a{rowptr, col, val, x, W, bias, out, N, ldo, members, mstride_x, mstride_o, relu, gwen_stream(stream_),
-                    nullptr, nullptr, nullptr, nullptr, false};
+  const LayerArgs a{rowptr, col, val, x, packed == 2 ? static_cast<const float *>(Wp) : W, bias, out, N, ldo, members,
+                    mstride_x, mstride_o, relu, gwen_stream(stream_), nullptr, nullptr, nullptr, nullptr, false, probe};
   return with_shape(Fin, Fout, gwen::ints<0, 2, 3>{}, gwen::images_of(exact), [&](auto fi, auto fo, auto nsv) {
     constexpr int FI = decltype(fi)::value, FO = decltype(fo)::value, NS = decltype(nsv)::value;
-    if constexpr (narrow(FI, FO)) {            // narrow layers: GE x D x index mode
+    if constexpr (narrow(FI, FO)) {            // narrow layers: GE x D x index mode x packed W
       return gwen::dispatch(gwen::ints<7, 8>{}, ge, [&](auto gev) {
         return gwen::dispatch(gwen::ints<1, 2>{}, depth, [&](auto dv) {
           return gwen::dispatch(gwen::ints<1, 2>{}, index_mode, [&](auto iv) {
-            return launch<FI, FO, NS, decltype(gev)::value, decltype(dv)::value, decltype(iv)::value>(a, block_rows);
+            return gwen::dispatch(gwen::ints<1, 2>{}, packed, [&](auto pv) {
+              constexpr bool PK = decltype(pv)::value == 2;
+              if constexpr (!PK || NS > 0)
+                return launch<FI, FO, NS, decltype(gev)::value, decltype(dv)::value, decltype(iv)::value, PK>(a, block_rows);
+              else
+                return (int)GWEN_EINVAL;
+            });
           });
         });
       });
@@ -509,6 +572,37 @@ extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *c
       return launch<FI, FO, NS, 8, 1>(a, block_rows);
     }
   });
+}
+
+extern "C" int gwen_gcn_layer_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W, const float *bias, float *out,
+                                         int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                         int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                         int exact, int entries, int depth, int block_rows, int index_mode,
+                                         const void *Wp, int packed, gwen_stream_t stream_) {
+  return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
+                     entries, depth, block_rows, index_mode, Wp, packed, stream_, nullptr);
+}
+
+extern "C" int gwen_gcn_layer_blocks_per_cu(const int32_t *rowptr, const int32_t *col, const float *val,
+                                            const float *x, const float *W, const float *bias, float *out,
+                                            int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                            int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                            int exact, int entries, int depth, int block_rows, int index_mode,
+                                            const void *Wp, int packed, int *blocks_per_cu) {
+  if (!blocks_per_cu || N <= 0 || members <= 0) return GWEN_EINVAL;
+  return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
+                     entries, depth, block_rows, index_mode, Wp, packed, nullptr, blocks_per_cu);
+}
+
+extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W, const float *bias, float *out,
+                                         int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                         int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                         int exact, int entries, int depth, int block_rows, int index_mode,
+                                         gwen_stream_t stream_) {
+  return gwen_gcn_layer_tuned3_f32(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x,
+                                   mstride_o, relu, exact, entries, depth, block_rows, index_mode, nullptr, 0, stream_);
 }
 
 extern "C" int gwen_gcn_layer_tuned_f32(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -564,7 +658,7 @@ extern "C" int gwen_gcn_layer_bwd_bias_f32(const int32_t *t_rowptr, const int32_
   if (N * Fg * 4 >= (int64_t(1) << 32)) return GWEN_ERANGE;
   if ((bias_partial != nullptr) != (bias_chunks != nullptr) || (bias_partial && !gwen_aligned(bias_partial, 16))) return GWEN_EINVAL;
   const LayerArgs a{t_rowptr, t_col, t_val, g, Wt, nullptr, gx, N, Fx, members, N * Fg, N * Fx, 0, gwen_stream(stream_),
-                    gh, mask, bias_partial, bias_chunks, true};
+                    gh, mask, bias_partial, bias_chunks, true, nullptr};
   return with_shape(Fg, Fx, gwen::ints<2, 3>{}, gwen::images_of(contract), [&](auto fi, auto fo, auto nsv) {
     return launch<decltype(fi)::value, decltype(fo)::value, decltype(nsv)::value, 8, 1>(a, 0);
   });

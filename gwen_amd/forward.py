@@ -13,7 +13,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .graph import GraphCSR, _ptr, _stream
+from .graph import GraphCSR, _ptr, _stream, _version_of
 
 # order string -> (GWEN_ORDER_*, GWEN_CONTRACT_* of an AUTO / FUSED layer).  "auto" is the default precision,
 # fp32-class on the kernel's own split ("f16x3": K8 on two scaled fp16 images, every other
@@ -111,16 +111,39 @@ def pack_weight(weight: Tensor) -> Optional[Tensor]:
     return img
 
 
+def pack_fragments(weight: Tensor, contract: int, into: Optional[Tensor] = None) -> Optional[Tensor]:
+    """The bf16 images of ``weight`` [Fout, Fin] in the fragment order of the narrow K4 / K5 forward kernels
+    (gwen_gcn_packw_f32): one launch on the current stream.  None when the shape has no packed form.
+    ``into``: an earlier image of a weight of this shape and contraction on the same device, overwritten in place --
+    its address stays what a captured graph has recorded."""
+    fout, fin = weight.shape
+    nbytes = int(_lib.lib().gwen_gcn_packw_bytes(fin, fout, contract))
+    if nbytes == 0:
+        return None
+    img = into if into is not None and into.numel() == nbytes and into.device == weight.device else \
+        torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = _lib.lib().gwen_gcn_packw_f32(_ptr(weight), fin, fout, contract, _ptr(img), _stream(weight.device))
+    _lib.check(rc, "gwen_gcn_packw_f32")
+    return img
+
+
 class StackForward:
     """A stack of GCN layers bound to one prepared graph: ``run(x)`` is one C call."""
 
     def __init__(self, layers: Sequence[Tuple[Tensor, Optional[Tensor], bool, str]], graph: GraphCSR,
-                 packed: Optional[Sequence[Optional[Tensor]]] = None):
+                 packed: Optional[Sequence[Optional[Tensor]]] = None, packw_cache: Optional[dict] = None):
         """``packed``: per layer the ``pack_weight`` image of its weight (or None) -- K7 then streams the
-        weights in fragment order (small graphs; the caller owns the cache, see GNNModel)."""
+        weights in fragment order (small graphs; the caller owns the cache, see GNNModel).
+        ``packw_cache``: where the K4 / K5 images (``pack_fragments``) are kept, layer index -> (key, image); a caller
+        that builds a StackForward per call hands its own dict over so that the images outlive the plan."""
         if not layers:
             raise ValueError("need at least one layer")
         self.graph = graph
+        self.packed_mode = 0                 # gwen_gnn_forward_packed_f32's `packed`: 0 the library's choice, 1 never, 2 always
+        self.pack_launches = 0               # gwen_gcn_packw_f32 launches this plan has made
+        self._packw = {} if packw_cache is None else packw_cache
+        self._wanted_mode, self._wanted, self._wanted_ptrs = None, [], None
         self._keep = []                      # tensors whose pointers sit in the descriptor array
         self.desc = (_lib.LayerDesc * len(layers))()
         for i, (w, b, relu, order) in enumerate(layers):
@@ -207,9 +230,61 @@ class StackForward:
             if wants and g.tiles() is None:
                 cl = g.clustered()
                 if cl is not None:
-                    hit = (cl[0], cl[1], StackForward(self._layers, cl[2], self._packed_in))
+                    hit = (cl[0], cl[1], StackForward(self._layers, cl[2], self._packed_in, self._packw))
             self._inner[members] = hit
         return self._inner[members]
+
+    def _image_wanted(self, i: int, contract: int) -> bool:
+        """Whether some K4 / K5 launch of the stack may read layer ``i``'s weight as packed images."""
+        L, d, n = _lib.lib(), self.desc, len(self.desc)
+        if d[i].order not in (_lib.ORDER_AUTO, _lib.ORDER_FUSED) or self.packed_mode == 1:
+            return False
+        fin, fout = d[i].fin, d[i].fout
+        if L.gwen_gcn_packw_bytes(fin, fout, contract) == 0:
+            return False
+        if self.packed_mode == 2:
+            return True
+        return (L.gwen_gcn_layer_packed_mode(fin, fout, contract) == 2
+                or L.gwen_gcn_chain_packed_mode(fin, fout, 0, 1, contract) == 2                       # W1, activation first
+                or (i + 1 < n and L.gwen_gcn_chain_packed_mode(fin, fout, d[i + 1].fout, 0, contract) == 2)   # W1, chained
+                or (i > 0 and L.gwen_gcn_chain_packed_mode(d[i - 1].fin, fin, fout, 0, contract) == 2))       # W2, chained
+
+    def _images(self):
+        """The K4 / K5 images of the layers' weights as the launcher's pointer array (None: no layer has one), packed
+        again -- in place, so an image keeps its address -- where a weight's (data_ptr, version, shape, contraction) is
+        not the one its image was made from.  A weight without a version counter (created under
+        ``torch.inference_mode()``) is packed on every run, never trusted.  What the key cannot see: a weight whose storage
+        was freed and handed out again at the same address with the same version count (``param.data = other`` can do
+        that) counts as unchanged, as it does for ``GNNModel._packed_weights``; and an image is ordered behind its pack
+        launch only on the stream it was packed on -- a run on another stream must be ordered behind that one by the
+        caller, as for any tensor."""
+        if self._wanted_mode != self.packed_mode:           # which layers: asked of the library once per mode
+            self._wanted = [(i, c) for i, c in ((i, _lib.dense_contract(d.contract)) for i, d in enumerate(self.desc))
+                            if self._image_wanted(i, c)]
+            self._wanted_mode = self.packed_mode
+            self._wanted_ptrs = (C.c_void_p * len(self.desc))() if self._wanted else None
+        for i, contract in self._wanted:
+            w = self._keep[3 * i]
+            ver = _version_of(w)
+            key = (w.data_ptr(), ver, w.shape, contract)
+            hit = self._packw.get(i)
+            if hit is None or hit[0] != key or ver is None:
+                hit = (key, pack_fragments(w, contract, None if hit is None else hit[1]))
+                self._packw[i] = hit
+                self.pack_launches += 1
+            self._wanted_ptrs[i] = hit[1].data_ptr()        # every run: another plan of the same cache may have packed it
+        return self._wanted_ptrs
+
+    def refresh_images(self, members: int = 1) -> None:
+        """The staleness check of ``run`` alone: packs again, in place and on the current stream, every image whose
+        weight changed.  For callers that launch the stack's kernels without ``run`` -- ``GraphedForward`` before each
+        replay: the captured kernels read the image buffers, and a replay does not pass through Python."""
+        inner = self._inner.get(members)
+        if inner is not None:
+            inner[2].packed_mode = self.packed_mode
+            return inner[2].refresh_images(members)
+        if not (self._small or self._long):
+            self._images()
 
     def run(self, x: Tensor, out: Optional[Tensor] = None,
             events: Optional[KernelEvents] = None, acts: Optional[List[Tensor]] = None) -> Tensor:
@@ -233,6 +308,7 @@ class StackForward:
             inner = self._clustered_plan(members)
             if inner is not None:
                 perm, inv, plan = inner
+                plan.packed_mode = self.packed_mode
                 y = plan.run(x.index_select(-2, perm), events=events)
                 if out is None:
                     return y.index_select(-2, inv)
@@ -267,15 +343,16 @@ class StackForward:
         scratch = self._scratch_for(members, dev)
         gd = self._graph_desc(members)
         with torch.cuda.device(dev):
-            rc = _lib.lib().gwen_gnn_forward_entries_f32(
+            images = None if (acts is not None or self._small) else self._images()   # training reads no images
+            rc = _lib.lib().gwen_gnn_forward_packed_f32(
                 C.byref(gd), self.desc, len(self.desc), _ptr(x),
                 _ptr(out), _ptr(scratch), scratch.numel(), members, _stream(dev),
                 None if events is None else events._ev,
                 None if events is None else events.info,
                 0 if events is None else events.max_launches,
                 None if events is None else C.byref(events.n), acts_arr,
-                8 if self._small else self.graph.entries())
-        _lib.check(rc, "gwen_gnn_forward_entries_f32")
+                8 if self._small else self.graph.entries(), images, self.packed_mode)
+        _lib.check(rc, "gwen_gnn_forward_packed_f32")
         return out
 
 
@@ -362,5 +439,8 @@ class GraphedForward:
     def __call__(self, x: Optional[Tensor] = None) -> Tensor:
         if x is not None and x.data_ptr() != self.x.data_ptr():
             self.x.copy_(x)
+        # the captured K4 / K5 launches read the packed images of the weights, not the weights: images whose weight
+        # changed since the last call are packed again first (in place, on this stream, in front of the replay)
+        self.stack.refresh_images(1 if self.x.dim() == 2 else self.x.size(0))
         self.graph.replay()
         return self.out

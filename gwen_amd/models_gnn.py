@@ -155,10 +155,12 @@ class GNNModel(nn.Module):
         self.conv_layers = GCNConvLayers(gnn_configs)
         self.activation = torch.nn.ReLU()
         self._packed = {}        # layer index -> (weight identity/version, packed image) for K7
+        self._packw = {}         # the same for K4 / K5 (StackForward's packw_cache)
 
     def __getstate__(self):      # derived data: keep the module picklable (mp.spawn, mlflow) and small
         state = self.__dict__.copy()
         state["_packed"] = {}
+        state["_packw"] = {}
         return state
 
     def _packed_weights(self, graph: GraphCSR):
@@ -209,4 +211,5 @@ class GNNModel(nn.Module):
                 return stack_apply(x, edge_index, self.stack())
             return self.conv_layers(x, edge_index)
         # inference: the whole stack from one host call (gwen_gnn_forward_f32)
-        return StackForward(self.stack(), edge_index, self._packed_weights(edge_index)).run(x)
+        return StackForward(self.stack(), edge_index, self._packed_weights(edge_index),
+                            getattr(self, "_packw", None)).run(x)

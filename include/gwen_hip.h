@@ -254,6 +254,43 @@ int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const f
 /* the index mode gwen_gcn_layer_f32 runs on a uniform layout: 1 or 2 (0: unsupported widths / exact) */
 int gwen_gcn_layer_index_mode(int64_t Fin, int64_t Fout, int exact);
 
+/* Packed W for the forward of K4 / K5 at Fin, Fout <= 64 on a bf16 split: the weight's NS bf16 images (2: bf16x3,
+ * 3: bf16x6), cut ONCE per weight version by the arithmetic the kernels use on W itself and stored in the order a wave
+ * reads its B fragments,
+ *     [column tile j of 16][k-step ks][image s][lane][KF]   bf16,   KF = 8 (4 at Fin = 16), Fin / (4 KF) k-steps,
+ *     lane (mi, mh) = (lane & 15, lane >> 4) holding W[16 j + mi][KF (4 ks + mh) .. + KF),
+ * so that a kernel loads each fragment as one contiguous run instead of reading fp32 rows of W and splitting them in
+ * every wave of every block.  A kernel that reads the images computes bit for bit what it computes from W.
+ * gwen_gcn_packw_bytes: size of the images, Fin * Fout * NS * 2; 0 = no packed form (a width outside {16, 32, 64} or a
+ *   contract other than GWEN_CONTRACT_BF16X3 / _BF16X6).
+ * gwen_gcn_packw_f32: W [Fout, Fin] contiguous -> packed (both 16-byte aligned); one launch on `stream`.  The images
+ *   hold for the VALUES W has at that point: pack again after W changes. */
+int64_t gwen_gcn_packw_bytes(int64_t Fin, int64_t Fout, int contract);
+int gwen_gcn_packw_f32(const float *W, int64_t Fin, int64_t Fout, int contract, void *packed, gwen_stream_t stream);
+/* gwen_gcn_layer_tuned2_f32 with the images of W: a fourth choice that CHANGES NO VALUE; gwen_gcn_layer_tuned2_f32
+ * forwards with NULL, 0.
+ * packed: 1 = W is read and split in the kernel (Wp ignored); 2 = Wp, the gwen_gcn_packw_f32 image of W for (Fin, Fout,
+ *   exact), is read and W may be NULL (Fin, Fout <= 64 and exact = GWEN_CONTRACT_BF16X3 / _BF16X6 only; elsewhere, or
+ *   with Wp NULL or misaligned, GWEN_EINVAL); 0 = the library's choice: 2 where Wp is given and
+ *   gwen_gcn_layer_packed_mode says so, else 1.  packed outside {0, 1, 2}: GWEN_EINVAL.
+ * block_rows: the kernels that read images also exist with 80 rows per block at Fin = 64 (five gather passes; four such
+ *   blocks of 64 -> 64 on bf16x6 fit a CU's LDS); without images 80 stays GWEN_EINVAL, as in every older entry point. */
+int gwen_gcn_layer_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                              int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                              int64_t mstride_o, int relu, int exact, int entries, int depth, int block_rows,
+                              int index_mode, const void *Wp, int packed, gwen_stream_t stream);
+/* For measurements: launches nothing and stores in *blocks_per_cu what hipOccupancyMaxActiveBlocksPerMultiprocessor reports
+ * for the kernel the same call of gwen_gcn_layer_tuned3_f32 would launch (asked of the uniform-layout kernel, as the
+ * launcher's own co-resident rule does).  Same checks and return codes; N, members > 0. */
+int gwen_gcn_layer_blocks_per_cu(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                                 const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                                 int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                                 int64_t mstride_o, int relu, int exact, int entries, int depth, int block_rows,
+                                 int index_mode, const void *Wp, int packed, int *blocks_per_cu);
+/* what packed = 0 does with an image: 1 = W is split in the kernel, 2 = the image is read (0: unsupported widths / exact) */
+int gwen_gcn_layer_packed_mode(int64_t Fin, int64_t Fout, int exact);
+
 /* ---------------------------------------------------------------------------------------------
  * K8  K4's contract for WIDE layers on locality-ordered bounded-degree graphs (meshes), tile-staged:
  *        out = act( (A~ x) W^T + bias )
@@ -347,6 +384,26 @@ int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *col, const f
                               int block_rows, int index_mode, gwen_stream_t stream);
 /* the index mode gwen_gcn_chain_f32 runs on a uniform layout: 1 or 2 (0: gwen_gcn_chain_supported says no) */
 int gwen_gcn_chain_index_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
+/* W1p, W2p, packed: as gwen_gcn_layer_tuned3_f32 -- no value changes; gwen_gcn_chain_tuned2_f32 forwards with NULL, NULL,
+ * 0.  W1p = gwen_gcn_packw_f32(W1, Fin, F1, contract), W2p = gwen_gcn_packw_f32(W2, F1, F2, contract) (F2 > 0 only).
+ * packed = 2 needs Fin, F1 <= 64, a contraction (F1 > 0) and an image for every weight of the form, else GWEN_EINVAL;
+ * W1 / W2 may then be NULL.  packed = 0: the images where all are given and gwen_gcn_chain_packed_mode says 2.
+ * block_rows: 80 as well at Fin = 64 where the images are read, as K4. */
+int gwen_gcn_chain_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+                              int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
+                              int64_t mstride_x, int64_t mstride_o, int contract, int entries, int depth,
+                              int block_rows, int index_mode, const void *W1p, const void *W2p, int packed,
+                              gwen_stream_t stream);
+/* as gwen_gcn_layer_blocks_per_cu, for the kernel gwen_gcn_chain_tuned3_f32 would launch (F1 > 0 only) */
+int gwen_gcn_chain_blocks_per_cu(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                                 const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+                                 int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
+                                 int64_t mstride_x, int64_t mstride_o, int contract, int entries, int depth,
+                                 int block_rows, int index_mode, const void *W1p, const void *W2p, int packed,
+                                 int *blocks_per_cu);
+/* what packed = 0 does with images: 1 or 2 as gwen_gcn_layer_packed_mode (0: gwen_gcn_chain_supported says no) */
+int gwen_gcn_chain_packed_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-stack forward == GNNModel.forward (/root/reference/src/gwen/models_gnn.py:292-303 ->
@@ -426,6 +483,18 @@ int gwen_gnn_forward_entries_f32(const gwen_graph *graph, const gwen_layer_desc 
                                  int64_t members, gwen_stream_t stream, void **events,
                                  gwen_launch_info *info, int32_t max_launches, int32_t *n_launches,
                                  float *const *acts, int entries);
+/* The same, handed the packed images of the layers' weights for the K4 / K5 launches of the stack.
+ * packw (HOST array of n_layers device pointers, or NULL; any element may be NULL): packw[l] =
+ *   gwen_gcn_packw_f32(layers[l].W, fin, fout, c) with c the layer's contraction in K4 / K5 (GWEN_CONTRACT_F16X3 layers:
+ *   _BF16X6).  A launch reads images only when it has one for every weight it contracts with.
+ * packed: 0 = each launch's own choice (gwen_gcn_layer_packed_mode / gwen_gcn_chain_packed_mode), 1 = never,
+ *   2 = wherever the images are given.  No value changes.  The training forward (acts) reads no images.
+ * gwen_gnn_forward_entries_f32 forwards with NULL, 0. */
+int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_layer_desc *layers, int32_t n_layers,
+                                const float *x, float *out, float *scratch, int64_t scratch_floats,
+                                int64_t members, gwen_stream_t stream, void **events,
+                                gwen_launch_info *info, int32_t max_launches, int32_t *n_launches,
+                                float *const *acts, int entries, const void *const *packw, int packed);
 
 /* ---------------------------------------------------------------------------------------------
  * K7  a whole GCNConv layer on a SMALL graph (N <= 256) with wide features -- the reference's own
