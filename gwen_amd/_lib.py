@@ -275,6 +275,11 @@ SIGNATURES = {
     "gwen_sht_analysis": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5 + [_vp, C.c_size_t, _vp]),
     "gwen_sht_synthesis": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5 + [_vp, C.c_size_t, _vp]),
     "gwen_sht_power_f64": (_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
+    "gwen_sht_vector_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64]),
+    "gwen_sht_vector_analysis": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5
+                                 + [_int, _vp, C.c_size_t, _vp]),
+    "gwen_sht_vector_synthesis": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5
+                                  + [_int, _vp, C.c_size_t, _vp]),
 }
 
 

@@ -13,6 +13,9 @@
 // contract against a tile of the ring sums (or of the coefficients).  Every sum is one thread's fp64 fma chain in index
 // order (i, j, l or m ascending) over one item and one channel: no atomics, nothing depends on the batch or on how it is
 // chunked, and a NaN stays in its (item, channel).
+//
+// The vector transforms, (u, v) <-> (vort, div), run the same longitude kernels on u and on v (ring [2, chunk, ...]) and
+// two latitude kernels of their own, k_vsht_lat_fwd and k_vsht_lat_inv ("vector harmonics" below).
 #include "common.h"
 
 namespace {
@@ -328,6 +331,247 @@ __global__ __launch_bounds__(kThreads) void k_sht_power(const double *__restrict
   power[e] = s;
 }
 
+// ---- vector harmonics: (u, v) <-> (vort, div) -------------------------------------------------------------------------
+// grad Y of the cos row (l, m >= 0) is (east, north) = (-m Q sin m lon, D cos m lon), of the sin row (l, -m) it is
+// (m Q cos m lon, D sin m lon), with Q = Pbar_l^m / cos lat and D = d Pbar_l^m / d lat; k x grad Y = (-north, east).
+// Neither table divides by cos lat.  For m >= 1 the block walks Q_l^m, the recurrence of Pbar_l^m seeded one cosine short
+// (seed[m] cos^(m-1) lat), and D_l^m = c_d Q_{l-1}^m - l sin lat Q_l^m.  For m = 0 the Q term carries the factor m = 0
+// and D_l^0 = c_d Pbar_l^1, so the block walks the order-1 recurrence from l = 1.  Either way one recurrence a latitude.
+
+// c_d of the line above: sqrt((2l + 1)(l^2 - m^2) / (2l - 1)) for m >= 1, sqrt(l (l + 1) / 2) for m = 0
+__device__ __forceinline__ double derivative_coefficient(int l, int m) {
+  const double dl = (double)l, dm = (double)m;
+  return m ? sqrt((2.0 * dl + 1.0) * (dl * dl - dm * dm) / (2.0 * dl - 1.0)) : sqrt(dl * (dl + 1.0) / 2.0);
+}
+
+// One degree of the walk: p1 = the recurrence value of degree l (p2 of l - 1) on the way out, (q, d) = (m Q_l^m, D_l^m).
+// mm = max(m, 1) is the order of the recurrence; a, b, cd belong to (l, mm) and to derivative_coefficient(l, m).
+__device__ __forceinline__ void vector_step(int l, int m, int mm, double mu, double a, double b, double cd, double &p1,
+                                            double &p2, double &q, double &d) {
+  if (l > mm) {
+    const double p = a * (mu * p1 - b * p2);
+    p2 = p1;
+    p1 = p;
+  }
+  if (m) {
+    q = (double)m * p1;
+    d = cd * p2 - (double)l * mu * p1;
+  } else {
+    q = 0.0;
+    d = l ? cd * p1 : 0.0;
+  }
+}
+
+// Block (item, channel tile, order m) as k_sht_lat_fwd, with two tables (m Q w, D w) and four ring columns (u cos, u sin,
+// v cos, v sin) in LDS.  vort_lm = sum_j w (u, v) . (D, m Q) {cos, sin}-wise and div_lm likewise (signs below), stored
+// as they are (inv_L = 0) or over L = l (l + 1) (inv_L = 1, the adjoint of the synthesis); row 0 is stored as 0.
+template <typename TOut>
+__global__ __launch_bounds__(kThreads) void k_vsht_lat_fwd(const double *__restrict__ ring_u,
+                                                           const double *__restrict__ ring_v,
+                                                           const dpair *__restrict__ nodes,
+                                                           const double *__restrict__ lat_w,
+                                                           const double *__restrict__ seed, TOut *__restrict__ vort,
+                                                           TOut *__restrict__ div, int nlat, int L, int C, int ctiles,
+                                                           int inv_L) {
+  extern __shared__ double smem[];
+  double *st1 = smem;                                     // [nlat]  the recurrence at l - 1, at the start of a degree tile
+  double *st2 = st1 + nlat;                               // [nlat]  at l - 2
+  double *qt = st2 + nlat;                                // [kLT][kJT]  m Q w
+  double *dt = qt + kLT * kJT;                            // [kLT][kJT]  D w
+  double *ft = dt + kLT * kJT;                            // [kJT][4][kCT]
+  double *ca = ft + kJT * 4 * kCT;                        // [kLT]
+  double *cb = ca + kLT;                                  // [kLT]
+  double *cd = cb + kLT;                                  // [kLT]
+  const int tid = threadIdx.x, cl = tid & (kCT - 1), lg = tid >> 4;
+  int64_t blk = blockIdx.x;
+  const int m = (int)(blk % (L + 1));
+  blk /= (L + 1);
+  const int ct = (int)(blk % ctiles);
+  const int64_t item = blk / ctiles;
+  const int c = ct * kCT + cl;
+  const int64_t T = (int64_t)(L + 1) * (L + 1);
+  const int mm = m ? m : 1;
+  const double sm = seed[mm < L ? mm : L];                // lmax = 0: seed has one entry, and nothing reads the walk
+  for (int j = tid; j < nlat; j += kThreads) {
+    st1[j] = sm * powi(nodes[j].y, m ? m - 1 : 1);
+    st2[j] = 0.0;
+  }
+  const int64_t item_off = item * (int64_t)nlat * (2 * L + 1) * C;
+  for (int l0 = m; l0 <= L; l0 += kLT) {
+    const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
+    __syncthreads();                                      // the tile before is done with ca, cb, cd
+    if (tid < nl) {
+      double a = 0.0, b = 0.0;
+      if (l0 + tid > mm) recurrence_coefficients(l0 + tid, mm, a, b);
+      ca[tid] = a;
+      cb[tid] = b;
+      cd[tid] = derivative_coefficient(l0 + tid, m);
+    }
+    double acc[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+    for (int j0 = 0; j0 < nlat; j0 += kJT) {
+      __syncthreads();
+      if (tid < kJT) {
+        const int j = j0 + tid;
+        if (j < nlat) {
+          double p1 = st1[j], p2 = st2[j];
+          const double mu = nodes[j].x, w = lat_w ? lat_w[j] : 1.0;
+          for (int t = 0; t < nl; ++t) {
+            double q, d;
+            vector_step(l0 + t, m, mm, mu, ca[t], cb[t], cd[t], p1, p2, q, d);
+            qt[t * kJT + ((tid + t) & (kJT - 1))] = q * w;
+            dt[t * kJT + ((tid + t) & (kJT - 1))] = d * w;
+          }
+          st1[j] = p1;
+          st2[j] = p2;
+        } else {
+          for (int t = 0; t < nl; ++t) {
+            qt[t * kJT + ((tid + t) & (kJT - 1))] = 0.0;
+            dt[t * kJT + ((tid + t) & (kJT - 1))] = 0.0;
+          }
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kJT * 4 * kCT / kThreads; ++r) {
+        const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 3, jj = e >> 6;
+        const int j = j0 + jj, gc = ct * kCT + cc;
+        const double *fr = (kk & 2 ? ring_v : ring_u) + item_off;
+        ft[e] = j < nlat && gc < C ? fr[((int64_t)j * (2 * L + 1) + (kk & 1 ? L - m : L + m)) * C + gc] : 0.0;
+      }
+      __syncthreads();
+      const int nj = nlat - j0 < kJT ? nlat - j0 : kJT;
+      for (int jj = 0; jj < nj; ++jj) {
+        const double uc = ft[(jj * 4 + 0) * kCT + cl], us = ft[(jj * 4 + 1) * kCT + cl];
+        const double vc = ft[(jj * 4 + 2) * kCT + cl], vs = ft[(jj * 4 + 3) * kCT + cl];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int t = lg + 16 * r;
+          const double q = t < nl ? qt[t * kJT + ((jj + t) & (kJT - 1))] : 0.0;
+          const double d = t < nl ? dt[t * kJT + ((jj + t) & (kJT - 1))] : 0.0;
+          acc[r][0] = fma(q, vs, fma(d, uc, acc[r][0]));     // vort, cos row:  D u_cos + m Q v_sin
+          acc[r][1] = fma(-q, vc, fma(d, us, acc[r][1]));    // vort, sin row:  D u_sin - m Q v_cos
+          acc[r][2] = fma(-d, vc, fma(q, us, acc[r][2]));    // div, cos row:   m Q u_sin - D v_cos
+          acc[r][3] = fma(-d, vs, fma(-q, uc, acc[r][3]));   // div, sin row:  -m Q u_cos - D v_sin
+        }
+      }
+    }
+    if (c < C) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int l = l0 + lg + 16 * r;
+        if (l > L) continue;
+        const double big = (double)l * (double)(l + 1);
+        const int64_t o = (item * T + (int64_t)l * l + l) * C + c;
+        double out[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[k] = l == 0 ? 0.0 : inv_L ? acc[r][k] / big : acc[r][k];
+        vort[o + (int64_t)m * C] = (TOut)out[0];
+        div[o + (int64_t)m * C] = (TOut)out[2];
+        if (m > 0) {
+          vort[o - (int64_t)m * C] = (TOut)out[1];
+          div[o - (int64_t)m * C] = (TOut)out[3];
+        }
+      }
+    }
+  }
+}
+
+// Block (item, channel tile, order m, 64 latitudes) as k_sht_lat_inv: the coefficient tile holds the potentials
+// psi = -vort / L and chi = -div / L (unit_L = 0) or -vort, -div (unit_L = 1, the adjoint of the analysis, whose factor L
+// cancels); row 0, a NULL pointer and the sin row of order 0 read as 0.  (u, v) = sum psi k x grad Y + chi grad Y.
+template <typename TIn>
+__global__ __launch_bounds__(kThreads) void k_vsht_lat_inv(const TIn *__restrict__ vort, const TIn *__restrict__ div,
+                                                           const dpair *__restrict__ nodes,
+                                                           const double *__restrict__ seed, double *__restrict__ ring_u,
+                                                           double *__restrict__ ring_v, int nlat, int L, int C,
+                                                           int ctiles, int jtiles, int unit_L) {
+  __shared__ double qt[kLT * kJT];
+  __shared__ double dt[kLT * kJT];
+  __shared__ double ctile[kLT * 4 * kCT];
+  __shared__ double ca[kLT], cb[kLT], cd[kLT];
+  const int tid = threadIdx.x, cl = tid & (kCT - 1), jg = tid >> 4;
+  int64_t blk = blockIdx.x;
+  const int jt = (int)(blk % jtiles);
+  blk /= jtiles;
+  const int m = (int)(blk % (L + 1));
+  blk /= (L + 1);
+  const int ct = (int)(blk % ctiles);
+  const int64_t item = blk / ctiles;
+  const int c = ct * kCT + cl;
+  const int64_t T = (int64_t)(L + 1) * (L + 1);
+  const int mm = m ? m : 1;
+  const int j0 = jt * kJT;
+  const int jmine = j0 + tid;
+  double p1 = 0.0, p2 = 0.0, mu = 0.0;
+  if (tid < kJT && jmine < nlat) {
+    p1 = seed[mm < L ? mm : L] * powi(nodes[jmine].y, m ? m - 1 : 1);
+    mu = nodes[jmine].x;
+  }
+  double acc[4][4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+  for (int l0 = m; l0 <= L; l0 += kLT) {
+    const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
+    __syncthreads();
+    if (tid < nl) {
+      double a = 0.0, b = 0.0;
+      if (l0 + tid > mm) recurrence_coefficients(l0 + tid, mm, a, b);
+      ca[tid] = a;
+      cb[tid] = b;
+      cd[tid] = derivative_coefficient(l0 + tid, m);
+    }
+#pragma unroll
+    for (int r = 0; r < kLT * 4 * kCT / kThreads; ++r) {
+      const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 3, t = e >> 6;
+      const int l = l0 + t, gc = ct * kCT + cc;
+      const TIn *cf = kk & 2 ? div : vort;
+      double val = 0.0;
+      if (cf && l > 0 && l <= L && gc < C && !((kk & 1) && m == 0)) {
+        const double raw = (double)cf[(item * T + (int64_t)l * l + l + (kk & 1 ? -m : m)) * C + gc];
+        val = unit_L ? -raw : -raw / ((double)l * (double)(l + 1));
+      }
+      ctile[e] = val;
+    }
+    __syncthreads();
+    if (tid < kJT) {
+      for (int t = 0; t < nl; ++t) {
+        double q, d;
+        vector_step(l0 + t, m, mm, mu, ca[t], cb[t], cd[t], p1, p2, q, d);
+        qt[t * kJT + ((tid + t) & (kJT - 1))] = q;
+        dt[t * kJT + ((tid + t) & (kJT - 1))] = d;
+      }
+    }
+    __syncthreads();
+    for (int t = 0; t < nl; ++t) {
+      const double pc = ctile[(t * 4 + 0) * kCT + cl], ps = ctile[(t * 4 + 1) * kCT + cl];
+      const double xc = ctile[(t * 4 + 2) * kCT + cl], xs = ctile[(t * 4 + 3) * kCT + cl];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double q = qt[t * kJT + ((jg + 16 * r + t) & (kJT - 1))];
+        const double d = dt[t * kJT + ((jg + 16 * r + t) & (kJT - 1))];
+        acc[r][0] = fma(q, xs, fma(-d, pc, acc[r][0]));      // u, cos column: -D psi_cos + m Q chi_sin
+        acc[r][1] = fma(-q, xc, fma(-d, ps, acc[r][1]));     // u, sin column: -D psi_sin - m Q chi_cos
+        acc[r][2] = fma(d, xc, fma(q, ps, acc[r][2]));       // v, cos column:  m Q psi_sin + D chi_cos
+        acc[r][3] = fma(d, xs, fma(-q, pc, acc[r][3]));      // v, sin column: -m Q psi_cos + D chi_sin
+      }
+    }
+  }
+  if (c >= C) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int j = j0 + jg + 16 * r;
+    if (j >= nlat) continue;
+    const int64_t o = ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
+    ring_u[o + (int64_t)m * C] = acc[r][0];
+    ring_v[o + (int64_t)m * C] = acc[r][2];
+    if (m > 0) {
+      ring_u[o - (int64_t)m * C] = acc[r][1];
+      ring_v[o - (int64_t)m * C] = acc[r][3];
+    }
+  }
+}
+
 struct Shape {
   int nlat, nlon, L, C, ctiles, mtiles, itiles, jtiles;
   int64_t item_bytes, item_blocks;
@@ -424,9 +668,141 @@ int check_call(const void *a, int a_f64, const void *b, int b_f64, const double 
   return chunk_items(s, workspace_bytes, batch, chunk);
 }
 
+size_t vector_lat_fwd_lds(int nlat) {
+  return sizeof(double) * (2 * (size_t)nlat + 2 * kLT * kJT + kJT * 4 * kCT + 3 * kLT);
+}
+
+// The ring of a pass is [2, nb, nlat, 2 lmax + 1, C]: u's first, then v's.
+template <typename TIn, typename TOut>
+int vector_analysis(const Shape &s, const TIn *u, const TIn *v, TOut *vort, TOut *div, const double *nodes,
+                    const double *lat_w, const double *tw, const double *seed, int adjoint, int64_t batch, int64_t chunk,
+                    double *ring, hipStream_t st) {
+  const size_t lds = vector_lat_fwd_lds(s.nlat);
+  if (lds > 64 * 1024)
+    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vsht_lat_fwd<TOut>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
+  const int64_t item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
+  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+    const int64_t rows = nb * s.nlat * s.C;
+    const int64_t xo = b0 * s.nlat * (int64_t)s.nlon * s.C;
+    double *ring_v = ring + nb * item;
+    const dim3 lon((unsigned)((rows + 63) / 64 * s.mtiles));
+    k_sht_lon_fwd<TIn><<<lon, dim3(kThreads), 0, st>>>(u + xo, reinterpret_cast<const dpair *>(tw), ring, rows, s.nlon,
+                                                        s.L, s.C, s.mtiles);
+    GWEN_LAUNCH_CHECK();
+    k_sht_lon_fwd<TIn><<<lon, dim3(kThreads), 0, st>>>(v + xo, reinterpret_cast<const dpair *>(tw), ring_v, rows, s.nlon,
+                                                        s.L, s.C, s.mtiles);
+    GWEN_LAUNCH_CHECK();
+    k_vsht_lat_fwd<TOut><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1))), dim3(kThreads), lds, st>>>(
+        ring, ring_v, reinterpret_cast<const dpair *>(nodes), lat_w, seed, vort + b0 * T * s.C, div + b0 * T * s.C,
+        s.nlat, s.L, s.C, s.ctiles, adjoint);
+    GWEN_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+template <typename TIn, typename TOut>
+int vector_synthesis(const Shape &s, const TIn *vort, const TIn *div, TOut *u, TOut *v, const double *nodes,
+                     const double *lat_w, const double *tw, const double *seed, int adjoint, int64_t batch, int64_t chunk,
+                     double *ring, hipStream_t st) {
+  const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
+  const int64_t item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
+  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
+    double *ring_v = ring + nb * item;
+    k_vsht_lat_inv<TIn><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1) * s.jtiles)), dim3(kThreads), 0, st>>>(
+        vort ? vort + b0 * T * s.C : nullptr, div ? div + b0 * T * s.C : nullptr,
+        reinterpret_cast<const dpair *>(nodes), seed, ring, ring_v, s.nlat, s.L, s.C, s.ctiles, s.jtiles, adjoint);
+    GWEN_LAUNCH_CHECK();
+    const int64_t rows = nb * s.nlat * s.C;
+    const int64_t xo = b0 * s.nlat * (int64_t)s.nlon * s.C;
+    const dim3 lon((unsigned)((rows + 63) / 64 * s.itiles));
+    k_sht_lon_inv<TOut><<<lon, dim3(kThreads), 0, st>>>(ring, reinterpret_cast<const dpair *>(tw), lat_w, u + xo, rows,
+                                                         s.nlat, s.nlon, s.L, s.C, s.itiles);
+    GWEN_LAUNCH_CHECK();
+    k_sht_lon_inv<TOut><<<lon, dim3(kThreads), 0, st>>>(ring_v, reinterpret_cast<const dpair *>(tw), lat_w, v + xo, rows,
+                                                         s.nlat, s.nlon, s.L, s.C, s.itiles);
+    GWEN_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// check_call for two inputs and two outputs; the ring of an item is twice the scalar's.  a1 may be NULL when
+// a_optional (a0 likewise): a missing coefficient tensor of the synthesis.
+int check_vector_call(const void *a0, const void *a1, int a_optional, int a_f64, const void *b0, const void *b1, int b_f64,
+                      const double *nodes, const double *lat_w, const double *tw, const double *seed, int grid,
+                      int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                      const void *workspace, size_t workspace_bytes, Shape &s, int64_t &chunk) {
+  const int rc = check_shape(grid, nlat, nlon, lmax, C, s);
+  if (rc) return rc;
+  s.item_bytes *= 2;
+  if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1) || (adjoint != 0 && adjoint != 1))
+    return GWEN_EINVAL;
+  chunk = 0;
+  if (batch == 0) return 0;
+  if (a_optional ? !a0 && !a1 : !a0 || !a1) return GWEN_EINVAL;
+  if (!b0 || !b1 || !nodes || !tw || !seed || !workspace) return GWEN_EINVAL;
+  if (!gwen_aligned(a0, a_f64 ? 8 : 4) || !gwen_aligned(a1, a_f64 ? 8 : 4) || !gwen_aligned(b0, b_f64 ? 8 : 4) ||
+      !gwen_aligned(b1, b_f64 ? 8 : 4) || !gwen_aligned(nodes, 16) || !gwen_aligned(tw, 16) || !gwen_aligned(seed, 8) ||
+      !gwen_aligned(workspace, 8) || (lat_w && !gwen_aligned(lat_w, 8)))
+    return GWEN_EINVAL;
+  return chunk_items(s, workspace_bytes, batch, chunk);
+}
+
 }  // namespace
 
 extern "C" {
+
+int64_t gwen_sht_vector_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {
+  Shape s;
+  return check_shape(grid, nlat, nlon, lmax, C, s) ? 0 : 2 * s.item_bytes;
+}
+
+int gwen_sht_vector_analysis(const void *u, const void *v, int x_f64, void *vort, void *div, int coef_f64,
+                             const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
+                             int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                             void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
+  Shape s;
+  int64_t chunk;
+  const int rc = check_vector_call(u, v, 0, x_f64, vort, div, coef_f64, nodes, lat_w, twiddle, seed, grid, batch, nlat,
+                                   nlon, lmax, C, adjoint, workspace, workspace_bytes, s, chunk);
+  if (rc || batch == 0) return rc;
+  hipStream_t st = gwen_stream(stream);
+  double *ring = static_cast<double *>(workspace);
+  if (x_f64)
+    return coef_f64 ? vector_analysis(s, (const double *)u, (const double *)v, (double *)vort, (double *)div, nodes,
+                                      lat_w, twiddle, seed, adjoint, batch, chunk, ring, st)
+                    : vector_analysis(s, (const double *)u, (const double *)v, (float *)vort, (float *)div, nodes, lat_w,
+                                      twiddle, seed, adjoint, batch, chunk, ring, st);
+  return coef_f64 ? vector_analysis(s, (const float *)u, (const float *)v, (double *)vort, (double *)div, nodes, lat_w,
+                                    twiddle, seed, adjoint, batch, chunk, ring, st)
+                  : vector_analysis(s, (const float *)u, (const float *)v, (float *)vort, (float *)div, nodes, lat_w,
+                                    twiddle, seed, adjoint, batch, chunk, ring, st);
+}
+
+int gwen_sht_vector_synthesis(const void *vort, const void *div, int coef_f64, void *u, void *v, int x_f64,
+                              const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
+                              int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                              void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
+  Shape s;
+  int64_t chunk;
+  const int rc = check_vector_call(vort, div, 1, coef_f64, u, v, x_f64, nodes, lat_w, twiddle, seed, grid, batch, nlat,
+                                   nlon, lmax, C, adjoint, workspace, workspace_bytes, s, chunk);
+  if (rc || batch == 0) return rc;
+  hipStream_t st = gwen_stream(stream);
+  double *ring = static_cast<double *>(workspace);
+  if (coef_f64)
+    return x_f64 ? vector_synthesis(s, (const double *)vort, (const double *)div, (double *)u, (double *)v, nodes, lat_w,
+                                    twiddle, seed, adjoint, batch, chunk, ring, st)
+                 : vector_synthesis(s, (const double *)vort, (const double *)div, (float *)u, (float *)v, nodes, lat_w,
+                                    twiddle, seed, adjoint, batch, chunk, ring, st);
+  return x_f64 ? vector_synthesis(s, (const float *)vort, (const float *)div, (double *)u, (double *)v, nodes, lat_w,
+                                  twiddle, seed, adjoint, batch, chunk, ring, st)
+               : vector_synthesis(s, (const float *)vort, (const float *)div, (float *)u, (float *)v, nodes, lat_w,
+                                  twiddle, seed, adjoint, batch, chunk, ring, st);
+}
 
 int64_t gwen_sht_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {
   Shape s;

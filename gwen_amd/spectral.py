@@ -20,9 +20,24 @@ Convention (include/gwen_hip.h, "Spherical harmonic transforms"; tests/sht_ref.p
     rows      the coefficient of ``(l, m)`` is row ``l^2 + l + m`` of ``T = (lmax + 1)^2``.
     analysis  ``c_lm = sum_p q_p Y_lm(p) x_p``;  synthesis ``x_p = sum_lm c_lm Y_lm(p)``;  power ``S_l = sum_m c_lm^2``
               (for a band-limited field ``sum_l S_l = sum_p q_p x_p^2``).
+    vector    winds are no scalars on the sphere (on a pole row ``u`` and ``v`` turn with the longitude), so they have
+              transforms of their own, on the unit sphere, ``u`` eastward and ``v`` northward.  With streamfunction
+              ``psi`` and velocity potential ``chi``:
+                  ``u = -d psi/d lat + (1/cos lat) d chi/d lon``,  ``v = (1/cos lat) d psi/d lon + d chi/d lat``,
+                  ``vort = lap psi``, ``div = lap chi``, ``lap Y_lm = -L Y_lm`` with ``L = l (l + 1)``.
+              ``vector_synthesis(vort, div)`` sums ``psi_lm (k x grad Y_lm) + chi_lm grad Y_lm`` with ``psi = -vort / L``,
+              ``chi = -div / L`` (row 0 read as 0); ``vector_analysis(u, v)`` gives ``div_lm = -sum_p q_p (u, v) . grad
+              Y_lm`` and ``vort_lm = -sum_p q_p (u, v) . (k x grad Y_lm)`` (row 0 is 0), its inverse on band-limited pairs,
+              pole rows included.  ``grad Y`` of a cos row is (east, north) = ``(-m Q sin m lon, D cos m lon)``, of a sin
+              row ``(m Q cos m lon, D sin m lon)``, with ``Q = Pbar_l^m / cos lat`` and ``D = d Pbar_l^m / d lat`` from
+              one recurrence that never divides by ``cos lat`` (include/gwen_hip.h); ``k x grad Y = (-north, east)``.
+              Kinetic energy ``E_l = sum_m (vort_lm^2 + div_lm^2) / (2 L)``, ``E_0 = 0``; for a band-limited wind
+              ``sum_l E_l = sum_p q_p (u^2 + v^2) / 2``.  ``gradient``, ``laplacian`` and ``inverse_laplacian`` follow.
+              Users of a sphere of radius ``a`` scale by ``1/a`` and ``1/a^2``.
 
 Everything is accumulated in fp64 by two HIP kernels a transform (csrc/sht.hip): direct sums along every latitude ring
-against an ``nlon``-entry twiddle table, and a contraction over the latitudes with ``Pbar_l^m`` generated on the fly.
+against an ``nlon``-entry twiddle table, and a contraction over the latitudes with ``Pbar_l^m`` generated on the fly (the
+vector transforms: the ring sums of ``u`` and of ``v``, and one contraction against ``m Q`` and ``D``).
 Results are bitwise reproducible, whatever the batch and the workspace.  Nodes, weights and tables are made on the host
 in fp64 at construction; after it nothing synchronises with the host, so a call can be captured into a hipGraph once it has
 run eagerly.  There is no CPU fallback: CPU tensors raise RuntimeError.
@@ -145,7 +160,8 @@ def _check_out_dtype(dtype) -> None:
 class SphericalHarmonics:
     """The transforms of one grid and truncation (module docstring).  ``workspace_bytes`` bounds the fp64 intermediate
     ``[chunk, nlat, 2 lmax + 1, C]``: the leading axes of a call, flattened into one batch, are cut into chunks that fit
-    (one item must: ValueError otherwise); the results do not depend on it."""
+    (one item must: ValueError otherwise); the results do not depend on it.  A vector transform holds the intermediate
+    of ``u`` and of ``v``, twice as much an item."""
 
     def __init__(self, nlat: int, nlon: int, device, lmax: Optional[int] = None, grid: str = "equiangular",
                  workspace_bytes: int = 1 << 30):
@@ -172,6 +188,10 @@ class SphericalHarmonics:
         self._lat_w = torch.from_numpy(np.ascontiguousarray(w / self.nlon)).to(dev)
         self._weights = torch.from_numpy(np.repeat(w / self.nlon, self.nlon).astype(np.float32)).to(dev)
         self._degrees = torch.from_numpy(degree_index(self.lmax)).to(dev)
+        big = (self._degrees * (self._degrees + 1)).to(torch.float64)
+        self._lap = -big[:, None]                                # [T, 1]: the Laplacian's factor of every row
+        l = torch.arange(self.lmax + 1, dtype=torch.float64, device=dev)
+        self._ke_scale = torch.where(l > 0, 0.5 / (l * (l + 1.0)).clamp(min=1.0), torch.zeros_like(l))[:, None]
 
     # ---- tables -----------------------------------------------------------------------------------------------------
     @property
@@ -211,9 +231,10 @@ class SphericalHarmonics:
         if t.device != self.device:
             raise RuntimeError(f"gwen_amd: {name} is on {t.device}, the transform's tables on {self.device}")
 
-    def _workspace(self, batch: int, c: int) -> Tensor:
+    def _workspace(self, batch: int, c: int, vector: bool = False) -> Tensor:
         from . import _lib
-        item = int(_lib.lib().gwen_sht_workspace_bytes(_lib.SHT_GRIDS[self.grid], self.nlat, self.nlon, self.lmax, c))
+        size = _lib.lib().gwen_sht_vector_workspace_bytes if vector else _lib.lib().gwen_sht_workspace_bytes
+        item = int(size(_lib.SHT_GRIDS[self.grid], self.nlat, self.nlon, self.lmax, c))
         if item > self.workspace_bytes:
             raise ValueError(f"workspace_bytes = {self.workspace_bytes} is below one item's intermediate ({item} bytes)")
         items = min(max(batch, 1), self.workspace_bytes // item)
@@ -290,6 +311,170 @@ class SphericalHarmonics:
                 rc = _lib.lib().gwen_sht_power_f64(_ptr(c64), _ptr(power), batch, self.lmax, c, _stream(self.device))
             _lib.check(rc, "gwen_sht_power_f64")
         return power if dtype == torch.float64 else power.to(dtype)
+
+    # ---- vector harmonics -------------------------------------------------------------------------------------------
+    def _check_pair(self, names, pair, rows: int, what: str, dtypes, optional: bool = False) -> None:
+        """``_check`` for two tensors of one shape and dtype: every shape, then every dtype, then every device.  With
+        ``optional`` one of them (not both) may be None."""
+        given = [(n, t) for n, t in zip(names, pair) if not (optional and t is None)]
+        if not given:
+            raise ValueError(f"at least one of {names[0]} and {names[1]} must be a tensor")
+        for n, t in given:
+            check_rows(n, t, rows, what)
+        if len(given) == 2 and given[0][1].shape != given[1][1].shape:
+            raise ValueError(f"{names[0]} and {names[1]} must have one shape, got {tuple(given[0][1].shape)} and "
+                             f"{tuple(given[1][1].shape)}")
+        for n, t in given:
+            if t.dtype not in dtypes:
+                raise TypeError(f"gwen_amd: {n} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)} "
+                                f"(got {t.dtype})")
+        if len(given) == 2 and given[0][1].dtype != given[1][1].dtype:
+            raise TypeError(f"gwen_amd: {names[0]} and {names[1]} must have one dtype, got {given[0][1].dtype} and "
+                            f"{given[1][1].dtype}")
+        for n, t in given:
+            if not t.is_cuda:
+                raise RuntimeError(f"gwen_amd: {n} must live on a HIP device (no CPU fallback)")
+            if t.device != self.device:
+                raise RuntimeError(f"gwen_amd: {n} is on {t.device}, the transform's tables on {self.device}")
+
+    def _vector_launch(self, inverse: bool, a0: Optional[Tensor], a1: Optional[Tensor], out_rows: int, dtype,
+                       weighted: bool, adjoint: bool) -> Tuple[Tensor, Tensor]:
+        """One vector transform of the contiguous pair ``a0, a1 [..., rows, C]`` (one of them may be None for the
+        synthesis) into two new ``[..., out_rows, C]`` of ``dtype``."""
+        from . import _lib
+        from .graph import _ptr, _stream
+        src = a0 if a0 is not None else a1
+        lead, c = src.shape[:-2], src.shape[-1]
+        batch = 1
+        for s in lead:
+            batch *= int(s)
+        b0 = torch.empty(*lead, out_rows, c, dtype=dtype, device=self.device)
+        b1 = torch.empty_like(b0)
+        if batch == 0:
+            return b0, b1
+        ws = self._workspace(batch, c, vector=True)
+        name = "gwen_sht_vector_synthesis" if inverse else "gwen_sht_vector_analysis"
+        with torch.cuda.device(self.device):
+            rc = getattr(_lib.lib(), name)(
+                _ptr(a0) if a0 is not None else None, _ptr(a1) if a1 is not None else None,
+                int(src.dtype == torch.float64), _ptr(b0), _ptr(b1), int(dtype == torch.float64), _ptr(self._nodes),
+                _ptr(self._lat_w) if weighted else None, _ptr(self._twiddle), _ptr(self._seed),
+                _lib.SHT_GRIDS[self.grid], batch, self.nlat, self.nlon, self.lmax, c, int(adjoint), _ptr(ws),
+                ws.numel() * 8, _stream(self.device))
+        _lib.check(rc, name)
+        return b0, b1
+
+    def vector_analysis_launch(self, u: Tensor, v: Tensor, dtype=torch.float32, weighted: bool = True,
+                               adjoint: bool = False) -> Tuple[Tensor, Tensor]:
+        """``gwen_sht_vector_analysis`` on contiguous device tensors, no autograd: weighted and plain it is the vector
+        analysis; with unit weights and ``adjoint`` (every row over ``L``) the adjoint of the vector synthesis."""
+        return self._vector_launch(False, u, v, self.num_coefficients, dtype, weighted, adjoint)
+
+    def vector_synthesis_launch(self, vort: Optional[Tensor], div: Optional[Tensor], dtype=torch.float32,
+                                weighted: bool = False, adjoint: bool = False) -> Tuple[Tensor, Tensor]:
+        """``gwen_sht_vector_synthesis`` on contiguous device tensors, no autograd: unweighted and plain it is the vector
+        synthesis; with the quadrature weights and ``adjoint`` (no division by ``L``) the adjoint of the analysis."""
+        return self._vector_launch(True, vort, div, self.rows, dtype, weighted, adjoint)
+
+    def vector_analysis(self, u: Tensor, v: Tensor, dtype=torch.float32) -> Tuple[Tensor, Tensor]:
+        """The eastward and northward components ``u, v [..., nlat * nlon, C]`` fp32 -> spectral vorticity and
+        divergence ``[..., T, C]`` in ``dtype``; row 0 of both is 0.  Differentiable in ``u`` and ``v``."""
+        self._check_pair(("u", "v"), (u, v), self.rows, "nlat * nlon", (torch.float32,))
+        _check_out_dtype(dtype)
+        return _VectorAnalysis.apply(u, v, self, dtype)
+
+    def vector_synthesis(self, vort: Optional[Tensor], div: Optional[Tensor],
+                         dtype=torch.float32) -> Tuple[Tensor, Tensor]:
+        """Spectral vorticity and divergence ``[..., T, C]`` fp32 or fp64 (one of them may be None: zero) -> the wind
+        ``(u, v)``, ``[..., nlat * nlon, C]`` each in ``dtype``.  Row 0 is read as 0.  Differentiable in both."""
+        self._check_pair(("vort", "div"), (vort, div), self.num_coefficients, "T", (torch.float32, torch.float64),
+                         optional=True)
+        _check_out_dtype(dtype)
+        return _VectorSynthesis.apply(vort, div, self, dtype)
+
+    def laplacian(self, coeffs: Tensor) -> Tensor:
+        """The coefficients of the Laplacian of the scalar with ``coeffs [..., T, C]``: every row times ``-l (l + 1)``."""
+        check_rows("coeffs", coeffs, self.num_coefficients, "T")
+        return coeffs * self._lap.to(coeffs.dtype)
+
+    def inverse_laplacian(self, coeffs: Tensor) -> Tensor:
+        """Every row over ``-l (l + 1)``; row 0 (the mean, which no Laplacian has) becomes 0 whatever it holds."""
+        check_rows("coeffs", coeffs, self.num_coefficients, "T")
+        lap = self._lap.to(coeffs.dtype)
+        return torch.where(lap != 0, coeffs / torch.where(lap != 0, lap, torch.ones_like(lap)), torch.zeros_like(coeffs))
+
+    def gradient(self, coeffs: Tensor, dtype=torch.float32) -> Tuple[Tensor, Tensor]:
+        """``(east, north)``, ``[..., nlat * nlon, C]`` each: the horizontal gradient of the scalar with coefficients
+        ``coeffs [..., T, C]`` -- ``vector_synthesis(None, laplacian(coeffs))``.  Differentiable in ``coeffs``."""
+        self._check("coeffs", coeffs, self.num_coefficients, "T", (torch.float32, torch.float64))
+        _check_out_dtype(dtype)
+        return self.vector_synthesis(None, self.laplacian(coeffs), dtype)
+
+    def kinetic_energy_spectrum(self, u: Optional[Tensor] = None, v: Optional[Tensor] = None,
+                                vort: Optional[Tensor] = None, div: Optional[Tensor] = None,
+                                dtype=torch.float64) -> Tensor:
+        """``[..., lmax + 1, C]``: ``E_l = sum_m (vort_lm^2 + div_lm^2) / (2 l (l + 1))``, ``E_0 = 0``, of the wind
+        ``(u, v)`` (its coefficients stay fp64 on the way) or of given ``(vort, div) [..., T, C]``.  For a band-limited
+        wind ``sum_l E_l = sum_p q_p (u^2 + v^2) / 2``.  Not differentiable: the inputs are read detached."""
+        from . import _lib
+        from .graph import _ptr, _stream
+        given = tuple(t is not None for t in (u, v, vort, div))
+        if given not in ((True, True, False, False), (False, False, True, True)):
+            raise ValueError("kinetic_energy_spectrum takes exactly one of the pairs (u, v) and (vort, div)")
+        wind = given[0]
+        if wind:
+            self._check_pair(("u", "v"), (u, v), self.rows, "nlat * nlon", (torch.float32,))
+        else:
+            self._check_pair(("vort", "div"), (vort, div), self.num_coefficients, "T", (torch.float32, torch.float64))
+        _check_out_dtype(dtype)
+        if wind:
+            pair = self.vector_analysis_launch(u.detach().contiguous(), v.detach().contiguous(), torch.float64)
+        else:
+            pair = (vort.detach().to(torch.float64).contiguous(), div.detach().to(torch.float64).contiguous())
+        lead, c = pair[0].shape[:-2], pair[0].shape[-1]
+        power = torch.empty(2, *lead, self.lmax + 1, c, dtype=torch.float64, device=self.device)
+        batch = power[0].numel() // ((self.lmax + 1) * c)
+        if batch:
+            with torch.cuda.device(self.device):
+                for k in range(2):
+                    rc = _lib.lib().gwen_sht_power_f64(_ptr(pair[k]), _ptr(power[k]), batch, self.lmax, c,
+                                                       _stream(self.device))
+                    _lib.check(rc, "gwen_sht_power_f64")
+        energy = (power[0] + power[1]) * self._ke_scale
+        return energy if dtype == torch.float64 else energy.to(dtype)
+
+
+class _VectorAnalysis(torch.autograd.Function):
+    """(vort, div) = VA (u, v); VA^T (g_vort, g_div) = q * VS(L g_vort, L g_div): the synthesis kernels with the
+    quadrature weights on the way out and no division by L on the way in."""
+
+    @staticmethod
+    def forward(ctx, u: Tensor, v: Tensor, sh: SphericalHarmonics, dtype):
+        ctx.sh = sh
+        return sh.vector_analysis_launch(u.detach().contiguous(), v.detach().contiguous(), dtype)
+
+    @staticmethod
+    def backward(ctx, g_vort, g_div):
+        h_u, h_v = ctx.sh.vector_synthesis_launch(g_vort.contiguous(), g_div.contiguous(), torch.float32, weighted=True,
+                                                  adjoint=True)
+        return h_u, h_v, None, None
+
+
+class _VectorSynthesis(torch.autograd.Function):
+    """(u, v) = VS (vort, div); VS^T (h_u, h_v) = the analysis kernels with unit weights, every row over L."""
+
+    @staticmethod
+    def forward(ctx, vort: Optional[Tensor], div: Optional[Tensor], sh: SphericalHarmonics, dtype):
+        ctx.sh, ctx.dtype = sh, (vort if vort is not None else div).dtype
+        ctx.given = (vort is not None, div is not None)
+        return sh.vector_synthesis_launch(None if vort is None else vort.detach().contiguous(),
+                                          None if div is None else div.detach().contiguous(), dtype)
+
+    @staticmethod
+    def backward(ctx, h_u, h_v):
+        g_vort, g_div = ctx.sh.vector_analysis_launch(h_u.contiguous(), h_v.contiguous(), ctx.dtype, weighted=False,
+                                                      adjoint=True)
+        return g_vort if ctx.given[0] else None, g_div if ctx.given[1] else None, None, None
 
 
 class _Analysis(torch.autograd.Function):

@@ -1199,6 +1199,28 @@ int gwen_cell_overlap_weights(const int64_t *rowptr, const double *area, const d
  *         or flag, a missing or misaligned pointer: GWEN_EINVAL; nlat nlon or C >= 2^31: GWEN_ERANGE; both before any HIP
  *         call.  batch == 0 returns 0.  Element offsets are 64-bit.
  *   gwen_sht_power_f64: power [batch, lmax + 1, C] fp64, S_l = sum_m coef_lm^2 in the order m = -l ... l.
+ *
+ *   Vector harmonics, on the unit sphere: u [batch, nlat * nlon, C] is the eastward and v the northward component, vort
+ *   and div [batch, (lmax + 1)^2, C] the spectral vorticity and divergence, rows as coef.  With streamfunction psi and
+ *   velocity potential chi,
+ *         u = -d psi/d lat + (1 / cos lat) d chi/d lon,   v = (1 / cos lat) d psi/d lon + d chi/d lat,
+ *         vort = lap psi,  div = lap chi,  lap Y_lm = -L Y_lm,  L = l (l + 1).
+ *   With Q_l^m = Pbar_l^m / cos lat and D_l^m = d Pbar_l^m / d lat, grad Y of the cos row (l, m >= 0) is (east, north) =
+ *   (-m Q sin m lon, D cos m lon), of the sin row (l, -m) it is (m Q cos m lon, D sin m lon), and k x grad Y =
+ *   (-north, east) of grad Y.  The kernels never divide by cos lat (pole rows are ordinary rows): for m >= 1, Q_l^m walks
+ *   the recurrence of Pbar_l^m from seed[m] cos^(m-1) lat and D_l^m = -l sin lat Q_l^m + sqrt((2l + 1)(l^2 - m^2) /
+ *   (2l - 1)) Q_{l-1}^m; for m = 0 the Q term carries the factor m = 0 and D_l^0 = sqrt(l (l + 1) / 2) Pbar_l^1.
+ *   gwen_sht_vector_synthesis: (u, v)[j, i] = lat_w[j] sum_lm psi_lm (k x grad Y_lm) + chi_lm grad Y_lm, with psi_lm =
+ *         -vort_lm / L and chi_lm = -div_lm / L (adjoint = 0) or psi_lm = -vort_lm, chi_lm = -div_lm (adjoint = 1).  Row 0
+ *         is read as 0 whatever it holds; vort or div (not both) may be NULL, meaning zero.  lat_w = NULL, adjoint = 0:
+ *         the synthesis.  lat_w = the quadrature weights, adjoint = 1: the adjoint of the analysis.
+ *   gwen_sht_vector_analysis: div_lm = -s_l sum_p lat_w (u, v) . grad Y_lm and vort_lm = -s_l sum_p lat_w (u, v) .
+ *         (k x grad Y_lm), with s_l = 1 (adjoint = 0) or 1 / L (adjoint = 1); row 0 is stored as 0.  lat_w = the
+ *         quadrature weights, adjoint = 0: the analysis, the inverse of the synthesis on band-limited pairs.  lat_w =
+ *         NULL, adjoint = 1: the adjoint of the synthesis.
+ *   u, v share x_f64 and vort, div share coef_f64.  Tables, sums, reproducibility and errors are those of the scalar
+ *   entries; adjoint outside {0, 1} is GWEN_EINVAL.  workspace: the ring sums of u and of v, [2, chunk, nlat,
+ *   2 lmax + 1, C] fp64; gwen_sht_vector_workspace_bytes() is the size of ONE item (twice the scalar's, 0 for bad sizes).
  * ------------------------------------------------------------------------------------------- */
 #define GWEN_SHT_EQUIANGULAR 0
 #define GWEN_SHT_EQUIANGULAR_CENTRED 1
@@ -1212,6 +1234,15 @@ int gwen_sht_synthesis(const void *coef, int coef_f64, void *x, int x_f64, const
                        int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream);
 int gwen_sht_power_f64(const double *coef, double *power, int64_t batch, int64_t lmax, int64_t C,
                        gwen_stream_t stream);
+int64_t gwen_sht_vector_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C);
+int gwen_sht_vector_analysis(const void *u, const void *v, int x_f64, void *vort, void *div, int coef_f64,
+                             const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
+                             int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                             void *workspace, size_t workspace_bytes, gwen_stream_t stream);
+int gwen_sht_vector_synthesis(const void *vort, const void *div, int coef_f64, void *u, void *v, int x_f64,
+                              const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
+                              int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                              void *workspace, size_t workspace_bytes, gwen_stream_t stream);
 
 #ifdef __cplusplus
 }
