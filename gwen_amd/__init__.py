@@ -6,7 +6,7 @@ torch-geometric (:19).  Kernels live in libgwen_hip.so (include/gwen_hip.h); bui
 ``python -m gwen_amd.build``.
 """
 from . import attention, checkpoint, forcings, forecaster, g2m, gridgraph, interaction, loss_functions, losses, noise, ops
-from . import products, regrid, spectral
+from . import products, regrid, sfno, spectral
 from .attention import GraphTransformer, edge_attention, edge_attention_kv
 from .checkpoint import checkpointed_step
 from .forward import GraphedForward, KernelEvents, StackForward, event_bracket_overhead
@@ -22,6 +22,7 @@ from .gridgraph import containing_faces, grid_graphs, latlon_grid, radius_edges,
 from .regrid import (Regridder, cell_areas, cell_overlaps, latlon_cells, mesh_cells, mesh_dual_cells,
                      nearest_neighbours)
 from .spectral import SphericalHarmonics
+from .sfno import SFNO, SFNOBlock, SpectralConv, spectral_conv, spectral_conv_supported
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
 from .models_gnn import (DownConvLayers, GCNConvLayers, GNNConfig, GNNModel, UpConvLayers,
@@ -35,6 +36,6 @@ __all__ = [
     "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
     "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
     "Regridder", "nearest_neighbours", "mesh_cells", "mesh_dual_cells", "latlon_cells", "cell_areas", "cell_overlaps", "checkpointed_step", "CRPSLoss", "EnsembleVarRegLoss", "MaskedLoss",
-    "SphericalHarmonics",
+    "SphericalHarmonics", "SFNO", "SFNOBlock", "SpectralConv", "spectral_conv", "spectral_conv_supported",
 ]
 __version__ = "0.1.0"

@@ -280,6 +280,9 @@ SIGNATURES = {
                                  + [_int, _vp, C.c_size_t, _vp]),
     "gwen_sht_vector_synthesis": (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int] + [_i64] * 5
                                   + [_int, _vp, C.c_size_t, _vp]),
+    "gwen_spectral_conv_supported": (_int, [_i64, _i64, _int]),
+    "gwen_spectral_conv_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
+    "gwen_spectral_conv_grad_weight_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
 }
 
 

@@ -1244,6 +1244,33 @@ int gwen_sht_vector_synthesis(const void *vort, const void *div, int coef_f64, v
                               int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
                               void *workspace, size_t workspace_bytes, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Spectral convolution (csrc/spectral_conv.hip, gwen_amd.sfno): the learned map of a spherical Fourier neural operator.
+ *
+ *   coef [batch, T, Cin], T = (lmax + 1)^2, rows as the transforms above: degree l owns rows l^2 .. l^2 + 2l.
+ *   W [lmax + 1, Cin, Cout]: one real matrix a degree, shared by every m (a zonal filter: the map commutes with every
+ *         rotation of the sphere).  out [batch, T, Cout].  Everything fp32, contiguous, 16-byte aligned.
+ *
+ *   gwen_spectral_conv_f32: out[b, l^2 + j, :] = coef[b, l^2 + j, :] . W[l], 0 <= j <= 2l.  With transpose_w = 1 the
+ *         product is with W[l]^T and W is read as stored [lmax + 1, Cout, Cin] -- the gradient in coef of the forward
+ *         whose weight it is, without a transposing copy.  out must not alias coef.
+ *   gwen_spectral_conv_grad_weight_f32: grad_W[l] = sum_b sum_j coef[b, l^2 + j, :]^T g[b, l^2 + j, :], g [batch, T,
+ *         Cout], grad_W [lmax + 1, Cin, Cout]; summed b outer, j inner by the one block that owns the tile: no atomics.
+ *   gwen_spectral_conv_supported: 1 where Cin and Cout are multiples of 16 in [16, 512] and contract is a split
+ *         contraction -- GWEN_CONTRACT_BF16X6 (fp32-class; GWEN_CONTRACT_F16X3 means it here, as in K3) or
+ *         GWEN_CONTRACT_BF16X3 -- else 0.  There is no fp32-input-MFMA and no fp64 path.
+ *   W[l] is cut into bf16 images on the fly (split.h), fp32 accumulators in ascending k.  Results are bitwise equal run
+ *   to run; in the forward an item's rows are the same bits whatever the batch and the other items.  Element offsets are
+ *   64-bit.  Unsupported sizes, batch < 0, lmax outside [0, 1023], a flag outside {0, 1}, a missing or misaligned
+ *   pointer: GWEN_EINVAL; batch (2 lmax + 1) >= 2^31: GWEN_ERANGE; both before any HIP call.  batch == 0 returns 0 and
+ *   writes nothing.  No host synchronisation.
+ * ------------------------------------------------------------------------------------------- */
+int gwen_spectral_conv_supported(int64_t Cin, int64_t Cout, int contract);
+int gwen_spectral_conv_f32(const float *coef, const float *W, float *out, int64_t batch, int64_t lmax, int64_t Cin,
+                           int64_t Cout, int transpose_w, int contract, gwen_stream_t stream);
+int gwen_spectral_conv_grad_weight_f32(const float *coef, const float *g, float *grad_W, int64_t batch, int64_t lmax,
+                                       int64_t Cin, int64_t Cout, int contract, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
