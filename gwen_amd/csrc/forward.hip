@@ -9,8 +9,18 @@
 
 namespace {
 
+// Activation buffers of the stack: a ring of THREE, not a ping-pong pair.  With two, every launch stores over the rows
+// that the launch before it has just read, and on the MI355X such stores are slow: k_gather at 16 channels on the c2 mesh
+// takes 5.6 us behind its producer and 8.8 us when it stores where that producer read (tools/experiments/xcd_place,
+// DESIGN 7.2).  With three, a launch stores over rows that were last read two launches earlier.  Only while the three
+// together fit the Infinity Cache (256 MiB): larger activations have left the caches by the time they are stored over,
+// their launches are long, and a third buffer of that size is real memory -- they keep the pair.
+constexpr int kRing = 3;
+constexpr int64_t kRingBytes = int64_t(256) << 20;
+
 struct Plan {
-  int64_t ping, pong, tmp, lin;   // element offsets into scratch (lin: split-K workspace of K3)
+  int64_t ring[kRing], tmp, lin;  // element offsets into scratch (lin: split-K workspace of K3)
+  int nring;                      // buffers in use: kRing, or 2
   int64_t lin_floats, total;
 };
 
@@ -54,9 +64,10 @@ int make_plan(int64_t N, int64_t members, const gwen_layer_desc *layers, int32_t
     const int64_t w7 = gwen_gcn_small_workspace_floats(N, members, layers[i].fin, layers[i].fout);
     if (w7 > lin_w) lin_w = w7;               // K7's split-K partials share the region
   }
-  P->ping = 0;
-  P->pong = round4(rows * out_w);
-  P->tmp = P->pong + round4(rows * out_w);
+  const int64_t one = round4(rows * out_w);
+  P->nring = kRing * one * (int64_t)sizeof(float) <= kRingBytes ? kRing : 2;
+  for (int r = 0; r < kRing; ++r) P->ring[r] = (r % P->nring) * one;
+  P->tmp = P->nring * one;
   P->lin = P->tmp + round4(rows * tmp_w);
   P->lin_floats = lin_w;
   P->total = P->lin + round4(lin_w) + 4;
@@ -105,7 +116,8 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
       if (!acts[i]) return GWEN_EINVAL;
   hipStream_t st = gwen_stream(stream);
   const int64_t rows = members * N;
-  float *buf[2] = {scratch + P.ping, scratch + P.pong};
+  float *buf[kRing];
+  for (int r = 0; r < kRing; ++r) buf[r] = scratch + P.ring[r];
   float *tmp = scratch + P.tmp;
   float *lin_ws = scratch + P.lin;
   int32_t nl = 0;
@@ -138,7 +150,7 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
   if (small) {
     for (int32_t i = 0; i < n_layers; ++i) {
       const gwen_layer_desc &L = layers[i];
-      float *dst = acts ? acts[i] : (i + 1 == n_layers ? out : buf[i & 1]);
+      float *dst = acts ? acts[i] : (i + 1 == n_layers ? out : buf[i % P.nring]);
       GWEN_TRY(before(GWEN_KIND_SMALL, i, L.fin, L.fout));
       GWEN_TRY(gwen_gcn_small_layer_f32(dense, cur, L.W, L.packed, L.bias, dst, N, L.fin, L.fout, members,
                                         N * L.fin, N * L.fout, L.relu, lin_ws, P.lin_floats,
@@ -160,7 +172,7 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
       const int cn = last ? 0 : dense_contract(contract_of(layers[i + 1]));
       const bool chain = !last && have_grouped && shrinking_auto(i + 1, cn) &&
                          gwen_gcn_chain_supported(fo, layers[i + 1].fout, 0, 1, cn);
-      float *dst = acts ? acts[i] : ((last) ? out : buf[nbuf++ & 1]);
+      float *dst = acts ? acts[i] : ((last) ? out : buf[nbuf++ % P.nring]);
       if (chain) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fo, layers[i + 1].fout));
         GWEN_TRY(gwen_gcn_chain_tuned3_f32(g_rowptr, g_col, g_val, cur, layers[i + 1].W, nullptr, L.bias,
@@ -195,7 +207,7 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
       if (!chain && L.order == GWEN_ORDER_AUTO && have_tiles &&
           gwen_gcn_wide_preferred(N, members, fi, fo) && gwen_gcn_wide_contract_supported(fi, fo, cw) &&
           (cw != GWEN_CONTRACT_BF16X6 || graph->union_max <= 128)) {   // K8: the layer tile-staged
-        float *dst = acts ? acts[i] : (last ? out : buf[nbuf++ & 1]);
+        float *dst = acts ? acts[i] : (last ? out : buf[nbuf++ % P.nring]);
         GWEN_TRY(before(GWEN_KIND_WIDE, i, fi, fo));
         GWEN_TRY(gwen_gcn_wide_layer_f32(graph->t_rows, graph->t_lid, graph->t_val, cur, L.W, L.bias, dst,
                                          N, N, fi, fo, fo, members, N * fi, N * fo, L.relu,
@@ -206,7 +218,7 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
       }
       if (!have_grouped) return GWEN_EINVAL;
       // a chained kernel stores the NEXT layer's input, never the stack's output
-      float *dst = acts ? acts[i] : ((last && !chain) ? out : buf[nbuf++ & 1]);
+      float *dst = acts ? acts[i] : ((last && !chain) ? out : buf[nbuf++ % P.nring]);
       if (chain) {
         GWEN_TRY(before(GWEN_KIND_CHAIN, i, fi, layers[i + 1].fout));
         GWEN_TRY(gwen_gcn_chain_tuned3_f32(g_rowptr, g_col, g_val, cur, L.W, layers[i + 1].W, L.bias, dst,
@@ -227,7 +239,7 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
       }
       cur = dst;
     } else if (o == GWEN_ORDER_TRANSFORM_FIRST) {
-      float *dst = acts ? acts[i] : (last ? out : buf[nbuf++ & 1]);
+      float *dst = acts ? acts[i] : (last ? out : buf[nbuf++ % P.nring]);
       GWEN_TRY(before(GWEN_KIND_LINEAR, i, fi, fo));
       GWEN_TRY(gwen_gcn_linear_f32(cur, L.W, nullptr, tmp, rows, fi, fo, fi, fo, 0, cc, lin_ws,
                                    P.lin_floats, stream));
@@ -238,7 +250,7 @@ extern "C" int gwen_gnn_forward_packed_f32(const gwen_graph *graph, const gwen_l
       GWEN_TRY(after());
       cur = dst;
     } else if (o == GWEN_ORDER_AGGREGATE_FIRST) {
-      float *dst = acts ? acts[i] : (last ? out : buf[nbuf++ & 1]);
+      float *dst = acts ? acts[i] : (last ? out : buf[nbuf++ % P.nring]);
       GWEN_TRY(before(GWEN_KIND_PROPAGATE, i, fi, fi));
       GWEN_TRY(gwen_gcn_propagate_f32(rowptr, col, val, cur, nullptr, tmp, N, fi, fi, fi, members,
                                       N * fi, N * fi, 0, stream));
