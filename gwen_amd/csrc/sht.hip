@@ -14,9 +14,14 @@
 // order (i, j, l or m ascending) over one item and one channel: no atomics, nothing depends on the batch or on how it is
 // chunked, and a NaN stays in its (item, channel).
 //
+// With longitude = GWEN_SHT_LON_FFT (gwen_sht_transform) the two longitude kernels are k_sht_lon_fft_fwd and
+// k_sht_lon_fft_inv of sht_fft.h, one fp64 FFT a ring and channel in LDS: the same ring, the same numbers up to rounding.
+// lon_fwd() and lon_inv() below are the one place where the four launchers choose.
+//
 // The vector transforms, (u, v) <-> (vort, div), run the same longitude kernels on u and on v (ring [2, chunk, ...]) and
 // two latitude kernels of their own, k_vsht_lat_fwd and k_vsht_lat_inv ("vector harmonics" below).
 #include "common.h"
+#include "sht_fft.h"
 
 namespace {
 
@@ -575,10 +580,15 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_inv(const TIn *__restrict
 struct Shape {
   int nlat, nlon, L, C, ctiles, mtiles, itiles, jtiles;
   int64_t item_bytes, item_blocks;
+  int longitude;                 // GWEN_SHT_LON_*
+  sht_fft::Plan fft;             // longitude == GWEN_SHT_LON_FFT: the butterfly schedule and the channel tile
+  int fft_ctiles;
 };
 
 // sizes only; 0 = fine
-int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, Shape &s) {
+int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, Shape &s,
+                int longitude = GWEN_SHT_LON_DIRECT) {
+  if (longitude != GWEN_SHT_LON_DIRECT && longitude != GWEN_SHT_LON_FFT) return GWEN_EINVAL;
   if (grid != GWEN_SHT_EQUIANGULAR && grid != GWEN_SHT_EQUIANGULAR_CENTRED && grid != GWEN_SHT_GAUSS) return GWEN_EINVAL;
   if (nlat < (grid == GWEN_SHT_EQUIANGULAR ? 2 : 1) || nlat > kMaxLat || nlon < 1 || C < 1) return GWEN_EINVAL;
   if (lmax < 0 || lmax > kLMax) return GWEN_EINVAL;
@@ -597,6 +607,15 @@ int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, S
   const int64_t lon = ((nlat * C + 63) / 64 + 1) * (int64_t)(s.mtiles > s.itiles ? s.mtiles : s.itiles);
   const int64_t lat = s.ctiles * (lmax + 1) * (int64_t)s.jtiles;
   s.item_blocks = lon > lat ? lon : lat;
+  s.longitude = longitude;
+  if (longitude == GWEN_SHT_LON_FFT) {
+    if (!sht_fft::supported(nlon)) return GWEN_EINVAL;
+    s.fft = sht_fft::make_plan(s.nlon, s.C);
+    s.fft_ctiles = (s.C + s.fft.tile - 1) / s.fft.tile;
+    // blocks (ring, channel tile), the rings rounded up to the XCD count: at most nlat + kXcds - 1 rings an item
+    s.item_blocks = (nlat + sht_fft::kXcds - 1) * (int64_t)s.fft_ctiles;
+    if (lat > s.item_blocks) s.item_blocks = lat;
+  }
   return 0;
 }
 
@@ -608,6 +627,49 @@ int chunk_items(const Shape &s, size_t workspace_bytes, int64_t batch, int64_t &
   const int64_t by_grid = INT32_MAX / s.item_blocks;
   if (chunk > by_grid) chunk = by_grid;
   if (chunk > batch) chunk = batch;
+  return 0;
+}
+
+// The longitude stage of nb items: the direct sums or the FFT, as the shape says.
+template <typename TIn>
+int lon_fwd(const Shape &s, const TIn *x, const double *tw, double *ring, int64_t nb, hipStream_t st) {
+  const int64_t rows = nb * s.nlat * s.C;
+  if (s.longitude == GWEN_SHT_LON_DIRECT) {
+    k_sht_lon_fwd<TIn><<<dim3((unsigned)((rows + 63) / 64 * s.mtiles)), dim3(kThreads), 0, st>>>(
+        x, reinterpret_cast<const dpair *>(tw), ring, rows, s.nlon, s.L, s.C, s.mtiles);
+    GWEN_LAUNCH_CHECK();
+    return 0;
+  }
+  const size_t lds = sht_fft::lds_bytes(s.fft);
+  if (lds > 64 * 1024)
+    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sht_fft::k_sht_lon_fft_fwd<TIn>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  sht_fft::k_sht_lon_fft_fwd<TIn>
+      <<<dim3((unsigned)sht_fft::grid_blocks(nb * s.nlat, s.fft_ctiles)), dim3(sht_fft::kThreads), lds, st>>>(
+          x, reinterpret_cast<const sht_fft::cpx *>(tw), ring, nb * s.nlat, s.nlon, s.L, s.C, s.fft_ctiles, s.fft);
+  GWEN_LAUNCH_CHECK();
+  return 0;
+}
+
+template <typename TOut>
+int lon_inv(const Shape &s, const double *ring, const double *tw, const double *lat_w, TOut *x, int64_t nb,
+            hipStream_t st) {
+  const int64_t rows = nb * s.nlat * s.C;
+  if (s.longitude == GWEN_SHT_LON_DIRECT) {
+    k_sht_lon_inv<TOut><<<dim3((unsigned)((rows + 63) / 64 * s.itiles)), dim3(kThreads), 0, st>>>(
+        ring, reinterpret_cast<const dpair *>(tw), lat_w, x, rows, s.nlat, s.nlon, s.L, s.C, s.itiles);
+    GWEN_LAUNCH_CHECK();
+    return 0;
+  }
+  const size_t lds = sht_fft::lds_bytes(s.fft);
+  if (lds > 64 * 1024)
+    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sht_fft::k_sht_lon_fft_inv<TOut>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  sht_fft::k_sht_lon_fft_inv<TOut>
+      <<<dim3((unsigned)sht_fft::grid_blocks(nb * s.nlat, s.fft_ctiles)), dim3(sht_fft::kThreads), lds, st>>>(
+          ring, reinterpret_cast<const sht_fft::cpx *>(tw), lat_w, x, nb * s.nlat, s.nlat, s.nlon, s.L, s.C,
+          s.fft_ctiles, s.fft);
+  GWEN_LAUNCH_CHECK();
   return 0;
 }
 
@@ -623,11 +685,7 @@ int analysis(const Shape &s, const TIn *x, TOut *coef, const double *nodes, cons
   const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    const int64_t rows = nb * s.nlat * s.C;
-    k_sht_lon_fwd<TIn><<<dim3((unsigned)((rows + 63) / 64 * s.mtiles)), dim3(kThreads), 0, st>>>(
-        x + b0 * s.nlat * (int64_t)s.nlon * s.C, reinterpret_cast<const dpair *>(tw), ring, rows, s.nlon, s.L, s.C,
-        s.mtiles);
-    GWEN_LAUNCH_CHECK();
+    if (const int rc = lon_fwd(s, x + b0 * s.nlat * (int64_t)s.nlon * s.C, tw, ring, nb, st)) return rc;
     k_sht_lat_fwd<TOut><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1))), dim3(kThreads), lds, st>>>(
         ring, reinterpret_cast<const dpair *>(nodes), lat_w, seed, coef + b0 * T * s.C, s.nlat, s.L, s.C, s.ctiles);
     GWEN_LAUNCH_CHECK();
@@ -644,19 +702,15 @@ int synthesis(const Shape &s, const TIn *coef, TOut *x, const double *nodes, con
     k_sht_lat_inv<TIn><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1) * s.jtiles)), dim3(kThreads), 0, st>>>(
         coef + b0 * T * s.C, reinterpret_cast<const dpair *>(nodes), seed, ring, s.nlat, s.L, s.C, s.ctiles, s.jtiles);
     GWEN_LAUNCH_CHECK();
-    const int64_t rows = nb * s.nlat * s.C;
-    k_sht_lon_inv<TOut><<<dim3((unsigned)((rows + 63) / 64 * s.itiles)), dim3(kThreads), 0, st>>>(
-        ring, reinterpret_cast<const dpair *>(tw), lat_w, x + b0 * s.nlat * (int64_t)s.nlon * s.C, rows, s.nlat, s.nlon,
-        s.L, s.C, s.itiles);
-    GWEN_LAUNCH_CHECK();
+    if (const int rc = lon_inv(s, ring, tw, lat_w, x + b0 * s.nlat * (int64_t)s.nlon * s.C, nb, st)) return rc;
   }
   return 0;
 }
 
 int check_call(const void *a, int a_f64, const void *b, int b_f64, const double *nodes, const double *tw,
                const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C,
-               const void *workspace, size_t workspace_bytes, Shape &s, int64_t &chunk) {
-  const int rc = check_shape(grid, nlat, nlon, lmax, C, s);
+               int longitude, const void *workspace, size_t workspace_bytes, Shape &s, int64_t &chunk) {
+  const int rc = check_shape(grid, nlat, nlon, lmax, C, s, longitude);
   if (rc) return rc;
   if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1)) return GWEN_EINVAL;
   chunk = 0;
@@ -685,16 +739,10 @@ int vector_analysis(const Shape &s, const TIn *u, const TIn *v, TOut *vort, TOut
   const int64_t item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    const int64_t rows = nb * s.nlat * s.C;
     const int64_t xo = b0 * s.nlat * (int64_t)s.nlon * s.C;
     double *ring_v = ring + nb * item;
-    const dim3 lon((unsigned)((rows + 63) / 64 * s.mtiles));
-    k_sht_lon_fwd<TIn><<<lon, dim3(kThreads), 0, st>>>(u + xo, reinterpret_cast<const dpair *>(tw), ring, rows, s.nlon,
-                                                        s.L, s.C, s.mtiles);
-    GWEN_LAUNCH_CHECK();
-    k_sht_lon_fwd<TIn><<<lon, dim3(kThreads), 0, st>>>(v + xo, reinterpret_cast<const dpair *>(tw), ring_v, rows, s.nlon,
-                                                        s.L, s.C, s.mtiles);
-    GWEN_LAUNCH_CHECK();
+    if (const int rc = lon_fwd(s, u + xo, tw, ring, nb, st)) return rc;
+    if (const int rc = lon_fwd(s, v + xo, tw, ring_v, nb, st)) return rc;
     k_vsht_lat_fwd<TOut><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1))), dim3(kThreads), lds, st>>>(
         ring, ring_v, reinterpret_cast<const dpair *>(nodes), lat_w, seed, vort + b0 * T * s.C, div + b0 * T * s.C,
         s.nlat, s.L, s.C, s.ctiles, adjoint);
@@ -716,15 +764,9 @@ int vector_synthesis(const Shape &s, const TIn *vort, const TIn *div, TOut *u, T
         vort ? vort + b0 * T * s.C : nullptr, div ? div + b0 * T * s.C : nullptr,
         reinterpret_cast<const dpair *>(nodes), seed, ring, ring_v, s.nlat, s.L, s.C, s.ctiles, s.jtiles, adjoint);
     GWEN_LAUNCH_CHECK();
-    const int64_t rows = nb * s.nlat * s.C;
     const int64_t xo = b0 * s.nlat * (int64_t)s.nlon * s.C;
-    const dim3 lon((unsigned)((rows + 63) / 64 * s.itiles));
-    k_sht_lon_inv<TOut><<<lon, dim3(kThreads), 0, st>>>(ring, reinterpret_cast<const dpair *>(tw), lat_w, u + xo, rows,
-                                                         s.nlat, s.nlon, s.L, s.C, s.itiles);
-    GWEN_LAUNCH_CHECK();
-    k_sht_lon_inv<TOut><<<lon, dim3(kThreads), 0, st>>>(ring_v, reinterpret_cast<const dpair *>(tw), lat_w, v + xo, rows,
-                                                         s.nlat, s.nlon, s.L, s.C, s.itiles);
-    GWEN_LAUNCH_CHECK();
+    if (const int rc = lon_inv(s, ring, tw, lat_w, u + xo, nb, st)) return rc;
+    if (const int rc = lon_inv(s, ring_v, tw, lat_w, v + xo, nb, st)) return rc;
   }
   return 0;
 }
@@ -733,9 +775,9 @@ int vector_synthesis(const Shape &s, const TIn *vort, const TIn *div, TOut *u, T
 // a_optional (a0 likewise): a missing coefficient tensor of the synthesis.
 int check_vector_call(const void *a0, const void *a1, int a_optional, int a_f64, const void *b0, const void *b1, int b_f64,
                       const double *nodes, const double *lat_w, const double *tw, const double *seed, int grid,
-                      int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                      int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint, int longitude,
                       const void *workspace, size_t workspace_bytes, Shape &s, int64_t &chunk) {
-  const int rc = check_shape(grid, nlat, nlon, lmax, C, s);
+  const int rc = check_shape(grid, nlat, nlon, lmax, C, s, longitude);
   if (rc) return rc;
   s.item_bytes *= 2;
   if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1) || (adjoint != 0 && adjoint != 1))
@@ -751,9 +793,124 @@ int check_vector_call(const void *a0, const void *a1, int a_optional, int a_f64,
   return chunk_items(s, workspace_bytes, batch, chunk);
 }
 
+// The four transforms behind gwen_sht_transform, each after its checks.
+int scalar_analysis(const gwen_sht_call &k) {
+  Shape s;
+  int64_t chunk;
+  const int rc = check_call(k.in0, k.in_f64, k.out0, k.out_f64, k.nodes, k.twiddle, k.seed, k.grid, k.batch, k.nlat,
+                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, s, chunk);
+  if (rc || k.batch == 0) return rc;
+  if (k.lat_w && !gwen_aligned(k.lat_w, 8)) return GWEN_EINVAL;
+  hipStream_t st = gwen_stream(k.stream);
+  double *ring = static_cast<double *>(k.workspace);
+  const auto run = [&](auto *x, auto *coef) {
+    return analysis(s, x, coef, k.nodes, k.lat_w, k.twiddle, k.seed, k.batch, chunk, ring, st);
+  };
+  if (k.in_f64) return k.out_f64 ? run((const double *)k.in0, (double *)k.out0) : run((const double *)k.in0, (float *)k.out0);
+  return k.out_f64 ? run((const float *)k.in0, (double *)k.out0) : run((const float *)k.in0, (float *)k.out0);
+}
+
+int scalar_synthesis(const gwen_sht_call &k) {
+  Shape s;
+  int64_t chunk;
+  const int rc = check_call(k.in0, k.in_f64, k.out0, k.out_f64, k.nodes, k.twiddle, k.seed, k.grid, k.batch, k.nlat,
+                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, s, chunk);
+  if (rc || k.batch == 0) return rc;
+  if (k.lat_w && !gwen_aligned(k.lat_w, 8)) return GWEN_EINVAL;
+  hipStream_t st = gwen_stream(k.stream);
+  double *ring = static_cast<double *>(k.workspace);
+  const auto run = [&](auto *coef, auto *x) {
+    return synthesis(s, coef, x, k.nodes, k.lat_w, k.twiddle, k.seed, k.batch, chunk, ring, st);
+  };
+  if (k.in_f64) return k.out_f64 ? run((const double *)k.in0, (double *)k.out0) : run((const double *)k.in0, (float *)k.out0);
+  return k.out_f64 ? run((const float *)k.in0, (double *)k.out0) : run((const float *)k.in0, (float *)k.out0);
+}
+
+int vector_analysis_call(const gwen_sht_call &k) {
+  Shape s;
+  int64_t chunk;
+  const int rc = check_vector_call(k.in0, k.in1, 0, k.in_f64, k.out0, k.out1, k.out_f64, k.nodes, k.lat_w, k.twiddle,
+                                   k.seed, k.grid, k.batch, k.nlat, k.nlon, k.lmax, k.C, k.adjoint, k.longitude,
+                                   k.workspace, k.workspace_bytes, s, chunk);
+  if (rc || k.batch == 0) return rc;
+  hipStream_t st = gwen_stream(k.stream);
+  double *ring = static_cast<double *>(k.workspace);
+  const auto run = [&](auto *u, auto *v, auto *vort, auto *div) {
+    return vector_analysis(s, u, v, vort, div, k.nodes, k.lat_w, k.twiddle, k.seed, k.adjoint, k.batch, chunk, ring, st);
+  };
+  if (k.in_f64)
+    return k.out_f64 ? run((const double *)k.in0, (const double *)k.in1, (double *)k.out0, (double *)k.out1)
+                     : run((const double *)k.in0, (const double *)k.in1, (float *)k.out0, (float *)k.out1);
+  return k.out_f64 ? run((const float *)k.in0, (const float *)k.in1, (double *)k.out0, (double *)k.out1)
+                   : run((const float *)k.in0, (const float *)k.in1, (float *)k.out0, (float *)k.out1);
+}
+
+int vector_synthesis_call(const gwen_sht_call &k) {
+  Shape s;
+  int64_t chunk;
+  const int rc = check_vector_call(k.in0, k.in1, 1, k.in_f64, k.out0, k.out1, k.out_f64, k.nodes, k.lat_w, k.twiddle,
+                                   k.seed, k.grid, k.batch, k.nlat, k.nlon, k.lmax, k.C, k.adjoint, k.longitude,
+                                   k.workspace, k.workspace_bytes, s, chunk);
+  if (rc || k.batch == 0) return rc;
+  hipStream_t st = gwen_stream(k.stream);
+  double *ring = static_cast<double *>(k.workspace);
+  const auto run = [&](auto *vort, auto *div, auto *u, auto *v) {
+    return vector_synthesis(s, vort, div, u, v, k.nodes, k.lat_w, k.twiddle, k.seed, k.adjoint, k.batch, chunk, ring, st);
+  };
+  if (k.in_f64)
+    return k.out_f64 ? run((const double *)k.in0, (const double *)k.in1, (double *)k.out0, (double *)k.out1)
+                     : run((const double *)k.in0, (const double *)k.in1, (float *)k.out0, (float *)k.out1);
+  return k.out_f64 ? run((const float *)k.in0, (const float *)k.in1, (double *)k.out0, (double *)k.out1)
+                   : run((const float *)k.in0, (const float *)k.in1, (float *)k.out0, (float *)k.out1);
+}
+
+// the argument lists of the four older entries as a direct-sum call
+gwen_sht_call direct_call(int op, const void *in0, const void *in1, int in_f64, void *out0, void *out1, int out_f64,
+                          const double *nodes, const double *lat_w, const double *twiddle, const double *seed, int grid,
+                          int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
+                          void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
+  gwen_sht_call k;
+  k.op = op;
+  k.longitude = GWEN_SHT_LON_DIRECT;
+  k.in0 = in0;
+  k.in1 = in1;
+  k.in_f64 = in_f64;
+  k.out0 = out0;
+  k.out1 = out1;
+  k.out_f64 = out_f64;
+  k.nodes = nodes;
+  k.lat_w = lat_w;
+  k.twiddle = twiddle;
+  k.seed = seed;
+  k.grid = grid;
+  k.adjoint = adjoint;
+  k.batch = batch;
+  k.nlat = nlat;
+  k.nlon = nlon;
+  k.lmax = lmax;
+  k.C = C;
+  k.workspace = workspace;
+  k.workspace_bytes = workspace_bytes;
+  k.stream = stream;
+  return k;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gwen_sht_fft_supported(int64_t nlon) { return sht_fft::supported(nlon) ? 1 : 0; }
+
+int gwen_sht_transform(const gwen_sht_call *call) {
+  if (!call) return GWEN_EINVAL;
+  switch (call->op) {
+    case GWEN_SHT_OP_ANALYSIS: return scalar_analysis(*call);
+    case GWEN_SHT_OP_SYNTHESIS: return scalar_synthesis(*call);
+    case GWEN_SHT_OP_VECTOR_ANALYSIS: return vector_analysis_call(*call);
+    case GWEN_SHT_OP_VECTOR_SYNTHESIS: return vector_synthesis_call(*call);
+  }
+  return GWEN_EINVAL;
+}
 
 int64_t gwen_sht_vector_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {
   Shape s;
@@ -764,44 +921,18 @@ int gwen_sht_vector_analysis(const void *u, const void *v, int x_f64, void *vort
                              const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
                              int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
                              void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_vector_call(u, v, 0, x_f64, vort, div, coef_f64, nodes, lat_w, twiddle, seed, grid, batch, nlat,
-                                   nlon, lmax, C, adjoint, workspace, workspace_bytes, s, chunk);
-  if (rc || batch == 0) return rc;
-  hipStream_t st = gwen_stream(stream);
-  double *ring = static_cast<double *>(workspace);
-  if (x_f64)
-    return coef_f64 ? vector_analysis(s, (const double *)u, (const double *)v, (double *)vort, (double *)div, nodes,
-                                      lat_w, twiddle, seed, adjoint, batch, chunk, ring, st)
-                    : vector_analysis(s, (const double *)u, (const double *)v, (float *)vort, (float *)div, nodes, lat_w,
-                                      twiddle, seed, adjoint, batch, chunk, ring, st);
-  return coef_f64 ? vector_analysis(s, (const float *)u, (const float *)v, (double *)vort, (double *)div, nodes, lat_w,
-                                    twiddle, seed, adjoint, batch, chunk, ring, st)
-                  : vector_analysis(s, (const float *)u, (const float *)v, (float *)vort, (float *)div, nodes, lat_w,
-                                    twiddle, seed, adjoint, batch, chunk, ring, st);
+  const gwen_sht_call k = direct_call(GWEN_SHT_OP_VECTOR_ANALYSIS, u, v, x_f64, vort, div, coef_f64, nodes, lat_w, twiddle,
+                                      seed, grid, batch, nlat, nlon, lmax, C, adjoint, workspace, workspace_bytes, stream);
+  return gwen_sht_transform(&k);
 }
 
 int gwen_sht_vector_synthesis(const void *vort, const void *div, int coef_f64, void *u, void *v, int x_f64,
                               const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
                               int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
                               void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_vector_call(vort, div, 1, coef_f64, u, v, x_f64, nodes, lat_w, twiddle, seed, grid, batch, nlat,
-                                   nlon, lmax, C, adjoint, workspace, workspace_bytes, s, chunk);
-  if (rc || batch == 0) return rc;
-  hipStream_t st = gwen_stream(stream);
-  double *ring = static_cast<double *>(workspace);
-  if (coef_f64)
-    return x_f64 ? vector_synthesis(s, (const double *)vort, (const double *)div, (double *)u, (double *)v, nodes, lat_w,
-                                    twiddle, seed, adjoint, batch, chunk, ring, st)
-                 : vector_synthesis(s, (const double *)vort, (const double *)div, (float *)u, (float *)v, nodes, lat_w,
-                                    twiddle, seed, adjoint, batch, chunk, ring, st);
-  return x_f64 ? vector_synthesis(s, (const float *)vort, (const float *)div, (double *)u, (double *)v, nodes, lat_w,
-                                  twiddle, seed, adjoint, batch, chunk, ring, st)
-               : vector_synthesis(s, (const float *)vort, (const float *)div, (float *)u, (float *)v, nodes, lat_w,
-                                  twiddle, seed, adjoint, batch, chunk, ring, st);
+  const gwen_sht_call k = direct_call(GWEN_SHT_OP_VECTOR_SYNTHESIS, vort, div, coef_f64, u, v, x_f64, nodes, lat_w, twiddle,
+                                      seed, grid, batch, nlat, nlon, lmax, C, adjoint, workspace, workspace_bytes, stream);
+  return gwen_sht_transform(&k);
 }
 
 int64_t gwen_sht_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {
@@ -812,37 +943,19 @@ int64_t gwen_sht_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t l
 int gwen_sht_analysis(const void *x, int x_f64, void *coef, int coef_f64, const double *nodes, const double *lat_w,
                       const double *twiddle, const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon,
                       int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_call(x, x_f64, coef, coef_f64, nodes, twiddle, seed, grid, batch, nlat, nlon, lmax, C, workspace,
-                            workspace_bytes, s, chunk);
-  if (rc || batch == 0) return rc;
-  if (lat_w && !gwen_aligned(lat_w, 8)) return GWEN_EINVAL;
-  hipStream_t st = gwen_stream(stream);
-  double *ring = static_cast<double *>(workspace);
-  if (x_f64)
-    return coef_f64 ? analysis(s, (const double *)x, (double *)coef, nodes, lat_w, twiddle, seed, batch, chunk, ring, st)
-                    : analysis(s, (const double *)x, (float *)coef, nodes, lat_w, twiddle, seed, batch, chunk, ring, st);
-  return coef_f64 ? analysis(s, (const float *)x, (double *)coef, nodes, lat_w, twiddle, seed, batch, chunk, ring, st)
-                  : analysis(s, (const float *)x, (float *)coef, nodes, lat_w, twiddle, seed, batch, chunk, ring, st);
+  const gwen_sht_call k = direct_call(GWEN_SHT_OP_ANALYSIS, x, nullptr, x_f64, coef, nullptr, coef_f64, nodes, lat_w,
+                                      twiddle, seed, grid, batch, nlat, nlon, lmax, C, 0, workspace, workspace_bytes,
+                                      stream);
+  return gwen_sht_transform(&k);
 }
 
 int gwen_sht_synthesis(const void *coef, int coef_f64, void *x, int x_f64, const double *nodes, const double *lat_w,
                        const double *twiddle, const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon,
                        int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_call(coef, coef_f64, x, x_f64, nodes, twiddle, seed, grid, batch, nlat, nlon, lmax, C, workspace,
-                            workspace_bytes, s, chunk);
-  if (rc || batch == 0) return rc;
-  if (lat_w && !gwen_aligned(lat_w, 8)) return GWEN_EINVAL;
-  hipStream_t st = gwen_stream(stream);
-  double *ring = static_cast<double *>(workspace);
-  if (coef_f64)
-    return x_f64 ? synthesis(s, (const double *)coef, (double *)x, nodes, lat_w, twiddle, seed, batch, chunk, ring, st)
-                 : synthesis(s, (const double *)coef, (float *)x, nodes, lat_w, twiddle, seed, batch, chunk, ring, st);
-  return x_f64 ? synthesis(s, (const float *)coef, (double *)x, nodes, lat_w, twiddle, seed, batch, chunk, ring, st)
-               : synthesis(s, (const float *)coef, (float *)x, nodes, lat_w, twiddle, seed, batch, chunk, ring, st);
+  const gwen_sht_call k = direct_call(GWEN_SHT_OP_SYNTHESIS, coef, nullptr, coef_f64, x, nullptr, x_f64, nodes, lat_w,
+                                      twiddle, seed, grid, batch, nlat, nlon, lmax, C, 0, workspace, workspace_bytes,
+                                      stream);
+  return gwen_sht_transform(&k);
 }
 
 int gwen_sht_power_f64(const double *coef, double *power, int64_t batch, int64_t lmax, int64_t C,

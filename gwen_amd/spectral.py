@@ -35,9 +35,12 @@ Convention (include/gwen_hip.h, "Spherical harmonic transforms"; tests/sht_ref.p
               ``sum_l E_l = sum_p q_p (u^2 + v^2) / 2``.  ``gradient``, ``laplacian`` and ``inverse_laplacian`` follow.
               Users of a sphere of radius ``a`` scale by ``1/a`` and ``1/a^2``.
 
-Everything is accumulated in fp64 by two HIP kernels a transform (csrc/sht.hip): direct sums along every latitude ring
+Everything is accumulated in fp64 by two HIP kernels a transform (csrc/sht.hip): the sums along every latitude ring
 against an ``nlon``-entry twiddle table, and a contraction over the latitudes with ``Pbar_l^m`` generated on the fly (the
-vector transforms: the ring sums of ``u`` and of ``v``, and one contraction against ``m Q`` and ``D``).
+vector transforms: the ring sums of ``u`` and of ``v``, and one contraction against ``m Q`` and ``D``).  The ring sums
+are direct sums (``longitude="direct"``, the default) or, on request (``longitude="fft"``), one fp64 mixed-radix FFT a
+ring and channel in LDS (csrc/sht_fft.h) for ``nlon = 2^a 3^b 5^c <= 4096``: the same numbers up to rounding, in
+``O(nlon log nlon)`` and not ``O(nlon lmax)``.  There is no automatic choice and no fallback between the two.
 Results are bitwise reproducible, whatever the batch and the workspace.  Nodes, weights and tables are made on the host
 in fp64 at construction; after it nothing synchronises with the host, so a call can be captured into a hipGraph once it has
 run eagerly.  There is no CPU fallback: CPU tensors raise RuntimeError.
@@ -53,6 +56,20 @@ from torch import Tensor
 GRIDS = ("equiangular", "equiangular-centred", "gauss")
 MAX_LMAX = 1023
 MAX_NLAT = 2048
+LONGITUDE = ("direct", "fft")
+MAX_FFT_NLON = 4096
+
+
+def fft_supported(nlon: int) -> bool:
+    """Whether ``longitude="fft"`` takes rings of ``nlon`` points: ``1 <= nlon <= 4096`` with no prime factor other than
+    2, 3 and 5 (``gwen_sht_fft_supported``)."""
+    nlon = int(nlon)
+    if not 1 <= nlon <= MAX_FFT_NLON:
+        return False
+    for f in (2, 3, 5):
+        while nlon % f == 0:
+            nlon //= f
+    return nlon == 1
 
 
 def quadrature(grid: str, nlat: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -100,11 +117,16 @@ def max_degree(grid: str, nlat: int, nlon: int) -> int:
     return min(by_lat, (nlon - 1) // 2, MAX_LMAX)
 
 
-def check_sizes(grid: str, nlat: int, nlon: int, lmax: Optional[int]) -> int:
+def check_sizes(grid: str, nlat: int, nlon: int, lmax: Optional[int], longitude: str = "direct") -> int:
     """``lmax`` (the default filled in) after every size check; ValueError otherwise.  No device is touched."""
     if grid not in GRIDS:
         raise ValueError(f"grid must be one of {GRIDS} (got {grid!r})")
+    if longitude not in LONGITUDE:
+        raise ValueError(f"longitude must be one of {LONGITUDE} (got {longitude!r})")
     nlat, nlon = int(nlat), int(nlon)
+    if longitude == "fft" and not fft_supported(nlon):
+        raise ValueError(f'longitude="fft" needs 1 <= nlon <= {MAX_FFT_NLON} with no prime factor other than 2, 3 and 5 '
+                         f"(got nlon = {nlon})")
     if nlat < (2 if grid == "equiangular" else 1) or nlon < 1:
         raise ValueError(f"nlat and nlon must be >= 1 (nlat >= 2 with poles); got {nlat}, {nlon}")
     if nlat > MAX_NLAT:
@@ -161,12 +183,14 @@ class SphericalHarmonics:
     """The transforms of one grid and truncation (module docstring).  ``workspace_bytes`` bounds the fp64 intermediate
     ``[chunk, nlat, 2 lmax + 1, C]``: the leading axes of a call, flattened into one batch, are cut into chunks that fit
     (one item must: ValueError otherwise); the results do not depend on it.  A vector transform holds the intermediate
-    of ``u`` and of ``v``, twice as much an item."""
+    of ``u`` and of ``v``, twice as much an item.  ``longitude`` chooses the longitude stage of every transform of the
+    object, the adjoints behind autograd included: ``"direct"`` sums or ``"fft"`` (module docstring; ValueError where
+    ``fft_supported(nlon)`` is false)."""
 
     def __init__(self, nlat: int, nlon: int, device, lmax: Optional[int] = None, grid: str = "equiangular",
-                 workspace_bytes: int = 1 << 30):
-        self.lmax = check_sizes(grid, nlat, nlon, lmax)
-        self.nlat, self.nlon, self.grid = int(nlat), int(nlon), grid
+                 workspace_bytes: int = 1 << 30, longitude: str = "direct"):
+        self.lmax = check_sizes(grid, nlat, nlon, lmax, longitude)
+        self.nlat, self.nlon, self.grid, self.longitude = int(nlat), int(nlon), grid, longitude
         self.workspace_bytes = int(workspace_bytes)
         if self.workspace_bytes < 1:
             raise ValueError(f"workspace_bytes must be positive (got {workspace_bytes})")
@@ -243,7 +267,6 @@ class SphericalHarmonics:
     def _launch(self, inverse: bool, src: Tensor, out_rows: int, dtype, weighted: bool) -> Tensor:
         """One transform of ``src [..., rows, C]`` (contiguous) into a new ``[..., out_rows, C]`` of ``dtype``."""
         from . import _lib
-        from .graph import _ptr, _stream
         lead, c = src.shape[:-2], src.shape[-1]
         batch = 1
         for s in lead:
@@ -252,14 +275,29 @@ class SphericalHarmonics:
         if batch == 0:
             return out
         ws = self._workspace(batch, c)
-        fn = _lib.lib().gwen_sht_synthesis if inverse else _lib.lib().gwen_sht_analysis
-        with torch.cuda.device(self.device):
-            rc = fn(_ptr(src), int(src.dtype == torch.float64), _ptr(out), int(dtype == torch.float64), _ptr(self._nodes),
-                    _ptr(self._lat_w) if weighted else None, _ptr(self._twiddle), _ptr(self._seed),
-                    _lib.SHT_GRIDS[self.grid], batch, self.nlat, self.nlon, self.lmax, c, _ptr(ws), ws.numel() * 8,
-                    _stream(self.device))
-        _lib.check(rc, "gwen_sht_synthesis" if inverse else "gwen_sht_analysis")
+        self._transform(_lib.SHT_OP_SYNTHESIS if inverse else _lib.SHT_OP_ANALYSIS, (src, None), (out, None), weighted,
+                        False, batch, c, ws)
         return out
+
+    def _transform(self, op: int, ins, outs, weighted: bool, adjoint: bool, batch: int, c: int, ws: Tensor) -> None:
+        """``gwen_sht_transform``: one of the four transforms with this object's tables and longitude stage."""
+        from . import _lib
+
+        def ptr(t):                                              # a structure's pointer field takes an int or None
+            return None if t is None else t.data_ptr()
+
+        src = ins[0] if ins[0] is not None else ins[1]
+        call = _lib.ShtCall(
+            op=op, longitude=_lib.SHT_LONGITUDE[self.longitude], in0=ptr(ins[0]), in1=ptr(ins[1]),
+            in_f64=int(src.dtype == torch.float64), out0=ptr(outs[0]), out1=ptr(outs[1]),
+            out_f64=int(outs[0].dtype == torch.float64), nodes=ptr(self._nodes),
+            lat_w=ptr(self._lat_w) if weighted else None, twiddle=ptr(self._twiddle), seed=ptr(self._seed),
+            grid=_lib.SHT_GRIDS[self.grid], adjoint=int(adjoint), batch=batch, nlat=self.nlat, nlon=self.nlon,
+            lmax=self.lmax, C=c, workspace=ptr(ws), workspace_bytes=ws.numel() * 8,
+            stream=torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().gwen_sht_transform(call)
+        _lib.check(rc, f"gwen_sht_transform(op={op}, longitude={self.longitude!r})")
 
     def analysis_launch(self, x: Tensor, dtype=torch.float32, weighted: bool = True) -> Tensor:
         """``gwen_sht_analysis`` on a contiguous device tensor, no autograd: with the quadrature weights the analysis,
@@ -342,7 +380,6 @@ class SphericalHarmonics:
         """One vector transform of the contiguous pair ``a0, a1 [..., rows, C]`` (one of them may be None for the
         synthesis) into two new ``[..., out_rows, C]`` of ``dtype``."""
         from . import _lib
-        from .graph import _ptr, _stream
         src = a0 if a0 is not None else a1
         lead, c = src.shape[:-2], src.shape[-1]
         batch = 1
@@ -353,15 +390,8 @@ class SphericalHarmonics:
         if batch == 0:
             return b0, b1
         ws = self._workspace(batch, c, vector=True)
-        name = "gwen_sht_vector_synthesis" if inverse else "gwen_sht_vector_analysis"
-        with torch.cuda.device(self.device):
-            rc = getattr(_lib.lib(), name)(
-                _ptr(a0) if a0 is not None else None, _ptr(a1) if a1 is not None else None,
-                int(src.dtype == torch.float64), _ptr(b0), _ptr(b1), int(dtype == torch.float64), _ptr(self._nodes),
-                _ptr(self._lat_w) if weighted else None, _ptr(self._twiddle), _ptr(self._seed),
-                _lib.SHT_GRIDS[self.grid], batch, self.nlat, self.nlon, self.lmax, c, int(adjoint), _ptr(ws),
-                ws.numel() * 8, _stream(self.device))
-        _lib.check(rc, name)
+        self._transform(_lib.SHT_OP_VECTOR_SYNTHESIS if inverse else _lib.SHT_OP_VECTOR_ANALYSIS, (a0, a1), (b0, b1),
+                        weighted, adjoint, batch, c, ws)
         return b0, b1
 
     def vector_analysis_launch(self, u: Tensor, v: Tensor, dtype=torch.float32, weighted: bool = True,

@@ -1244,6 +1244,44 @@ int gwen_sht_vector_synthesis(const void *vort, const void *div, int coef_f64, v
                               int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
                               void *workspace, size_t workspace_bytes, gwen_stream_t stream);
 
+/* One entry for the four transforms above, and the choice of the longitude stage.
+ *
+ *   op: which transform.  in0 (in1) and out0 (out1) are its inputs and outputs in the order of the entry above -- x and
+ *         coef, or (u, v) and (vort, div); the scalar transforms ignore in1, out1 and adjoint.  in_f64 / out_f64 are the
+ *         dtype flags of the inputs and of the outputs.  Every other field is the argument of that name.
+ *   longitude: GWEN_SHT_LON_DIRECT, the direct sums of the four entries above (which are this call with it, bit for bit),
+ *         or GWEN_SHT_LON_FFT: every latitude ring of every channel is one fp64 mixed-radix FFT (radices 4, 2, 3, 5) in
+ *         LDS, of length nlon / 2 and a split step when nlon is even, of length nlon when it is odd; every twiddle is an
+ *         entry of the same nlon-entry table.  Orders above lmax are not stored and read as zero.  The ring sums, the
+ *         workspace and the latitude kernels are the same; results agree with the direct sums to rounding (not bit for
+ *         bit: the order of the additions differs) and are as reproducible: fixed by one item's, one latitude's and one
+ *         channel's inputs and by nlon, whatever the batch, the chunking or the run; a non-finite input stays in its
+ *         (item, channel).  gwen_sht_fft_supported(nlon): 1 iff 1 <= nlon <= 4096 and nlon = 2^a 3^b 5^c (no HIP call).
+ *   A NULL call, an unknown op or longitude, GWEN_SHT_LON_FFT with an nlon it does not support: GWEN_EINVAL; every other
+ *   error as the entries above, all before any HIP call. */
+#define GWEN_SHT_OP_ANALYSIS 0
+#define GWEN_SHT_OP_SYNTHESIS 1
+#define GWEN_SHT_OP_VECTOR_ANALYSIS 2
+#define GWEN_SHT_OP_VECTOR_SYNTHESIS 3
+#define GWEN_SHT_LON_DIRECT 0
+#define GWEN_SHT_LON_FFT 1
+typedef struct gwen_sht_call {
+  int32_t op;        /* GWEN_SHT_OP_* */
+  int32_t longitude; /* GWEN_SHT_LON_* */
+  const void *in0, *in1;
+  int32_t in_f64;
+  void *out0, *out1;
+  int32_t out_f64;
+  const double *nodes, *lat_w, *twiddle, *seed;
+  int32_t grid, adjoint;
+  int64_t batch, nlat, nlon, lmax, C;
+  void *workspace;
+  size_t workspace_bytes;
+  gwen_stream_t stream;
+} gwen_sht_call;
+int gwen_sht_transform(const gwen_sht_call *call);
+int gwen_sht_fft_supported(int64_t nlon);
+
 /* ---------------------------------------------------------------------------------------------
  * Spectral convolution (csrc/spectral_conv.hip, gwen_amd.sfno): the learned map of a spherical Fourier neural operator.
  *

@@ -3,7 +3,7 @@ outputs, and one SFNOBlock, on device events; print one JSON line a case and app
 
     python tools/sfno_bench.py                          the three standard shapes and the block
     python tools/sfno_bench.py LMAX CIN COUT BATCH      one spectral-convolution shape
-    options: --precision f16x3|3xbf16  --calls K  --rounds R  --warmup W  --no-block
+    options: --precision f16x3|3xbf16  --calls K  --rounds R  --warmup W  --no-block  --longitude direct|fft|both
 
 Spectral convolution: the forward, the gradient in coef and the gradient in the weight, each as microseconds a call and
 as a fraction of the 8 TB/s HBM peak by compulsory bytes (the weights once, the coefficients in and out; for the weight
@@ -13,7 +13,9 @@ Cout]`` and gathers the rows back; the padding and the gather are inside the tim
 two sides alternate bracket by bracket in one process; a side's figure is the median of its brackets.
 
 Block: one SFNOBlock at 361 x 720, lmax 180, 64 channels, forward (no_grad) and forward + backward, and the same for its
-transforms alone (analysis + synthesis; with their adjoints for the backward), whose share of the block is stated."""
+transforms alone (analysis + synthesis; with their adjoints for the backward), whose share of the block is stated.
+``--longitude both`` (the default) runs the block on the direct-sum and on the FFT longitude stage of the transforms in
+one process, bracket after bracket in turn, and writes one line per stage (field ``longitude``)."""
 from __future__ import annotations
 
 import argparse
@@ -74,16 +76,21 @@ def bracket(fn, calls):
     return t0.elapsed_time(t1) / calls * 1e3                                   # us per call
 
 
-def alternate(a, b, calls, rounds, warmup):
+def alternate_many(fns, calls, rounds, warmup):
+    """Median microseconds per call of every function, their brackets taken in turn."""
     for _ in range(warmup):
-        a()
-        b()
+        for fn in fns:
+            fn()
     torch.cuda.synchronize()
-    ta, tb = [], []
+    times = [[] for _ in fns]
     for _ in range(rounds):
-        ta.append(bracket(a, calls))
-        tb.append(bracket(b, calls))
-    return statistics.median(ta), statistics.median(tb)
+        for t, fn in zip(times, fns):
+            t.append(bracket(fn, calls))
+    return [statistics.median(t) for t in times]
+
+
+def alternate(a, b, calls, rounds, warmup):
+    return tuple(alternate_many([a, b], calls, rounds, warmup))
 
 
 def run_conv(lmax, cin, cout, batch, precision, calls, rounds, warmup) -> dict:
@@ -129,42 +136,55 @@ def run_conv(lmax, cin, cout, batch, precision, calls, rounds, warmup) -> dict:
     return line
 
 
-def run_block(nlat, nlon, lmax, channels, members, precision, calls, rounds, warmup) -> dict:
+def run_block(nlat, nlon, lmax, channels, members, precision, calls, rounds, warmup, longitude="both") -> list:
+    """One line per longitude stage."""
     import gwen_amd
     dev = torch.device("cuda:0")
-    sh = gwen_amd.SphericalHarmonics(nlat, nlon, dev, lmax=lmax, workspace_bytes=4 << 30)
-    torch.manual_seed(37)
-    block = gwen_amd.SFNOBlock(sh, channels, precision=precision).to(dev)
-    x = torch.randn(members, sh.rows, channels, device=dev)
-    xg = x.clone().requires_grad_()
-    xt = x.clone().requires_grad_()
+    modes = ["direct", "fft"] if longitude == "both" else [longitude]
+    x = torch.randn(members, nlat * nlon, channels, device=dev, generator=torch.Generator(device=dev).manual_seed(38))
     r = torch.randn_like(x)
 
-    def forward():
-        with torch.no_grad():
-            return block(x)
+    def side(mode):
+        sh = gwen_amd.SphericalHarmonics(nlat, nlon, dev, lmax=lmax, workspace_bytes=4 << 30, longitude=mode)
+        torch.manual_seed(37)
+        block = gwen_amd.SFNOBlock(sh, channels, precision=precision).to(dev)
+        xg = x.clone().requires_grad_()
+        xt = x.clone().requires_grad_()
 
-    def transforms():
-        with torch.no_grad():
-            return sh.synthesis(sh.analysis(x))
+        def forward():
+            with torch.no_grad():
+                return block(x)
 
-    def training():
-        xg.grad = None
-        block.zero_grad(set_to_none=True)
-        block(xg).backward(r)
+        def transforms():
+            with torch.no_grad():
+                return sh.synthesis(sh.analysis(x))
 
-    def transforms_training():
-        xt.grad = None
-        sh.synthesis(sh.analysis(xt)).backward(r)
+        def training():
+            xg.grad = None
+            block.zero_grad(set_to_none=True)
+            block(xg).backward(r)
 
-    fwd, fwd_t = alternate(forward, transforms, calls, rounds, warmup)
-    trn, trn_t = alternate(training, transforms_training, calls, rounds, warmup)
-    return {"tool": "sfno_bench", "case": "sfno_block", "nlat": nlat, "nlon": nlon, "lmax": lmax, "channels": channels,
-            "members": members, "precision": precision, "calls": calls, "rounds": rounds,
-            "forward_us": round(fwd, 1), "forward_transforms_us": round(fwd_t, 1),
-            "forward_transforms_share": round(fwd_t / fwd, 4),
-            "forward_backward_us": round(trn, 1), "forward_backward_transforms_us": round(trn_t, 1),
-            "forward_backward_transforms_share": round(trn_t / trn, 4)}
+        def transforms_training():
+            xt.grad = None
+            sh.synthesis(sh.analysis(xt)).backward(r)
+
+        return forward, transforms, training, transforms_training
+
+    sides = [side(m) for m in modes]
+    fwd = alternate_many([f for s in sides for f in s[:2]], calls, rounds, warmup)
+    trn = alternate_many([f for s in sides for f in s[2:]], calls, rounds, warmup)
+    lines = []
+    for k, mode in enumerate(modes):
+        line = {"tool": "sfno_bench", "case": "sfno_block", "longitude": mode, "nlat": nlat, "nlon": nlon, "lmax": lmax,
+                "channels": channels, "members": members, "precision": precision, "calls": calls, "rounds": rounds,
+                "forward_us": round(fwd[2 * k], 1), "forward_transforms_us": round(fwd[2 * k + 1], 1),
+                "forward_transforms_share": round(fwd[2 * k + 1] / fwd[2 * k], 4),
+                "forward_backward_us": round(trn[2 * k], 1), "forward_backward_transforms_us": round(trn[2 * k + 1], 1),
+                "forward_backward_transforms_share": round(trn[2 * k + 1] / trn[2 * k], 4)}
+        if mode == "fft" and "direct" in modes:
+            line["direct_forward_us"], line["direct_forward_backward_us"] = round(fwd[0], 1), round(trn[0], 1)
+        lines.append(line)
+    return lines
 
 
 def main() -> None:
@@ -175,6 +195,7 @@ def main() -> None:
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-block", action="store_true")
+    ap.add_argument("--longitude", choices=("direct", "fft", "both"), default="both")
     a = ap.parse_args()
     if len(a.shape) not in (0, 4):
         ap.error("give LMAX CIN COUT BATCH, or nothing")
@@ -192,7 +213,8 @@ def main() -> None:
     for shape in ([tuple(a.shape)] if a.shape else STANDARD):
         emit(run_conv(*shape, a.precision, a.calls, a.rounds, a.warmup))
     if not a.shape and not a.no_block:
-        emit(run_block(*BLOCK, a.precision, max(1, a.calls // 2), a.rounds, 1))
+        for line in run_block(*BLOCK, a.precision, max(1, a.calls // 2), a.rounds, 1, a.longitude):
+            emit(line)
 
 
 if __name__ == "__main__":

@@ -2,6 +2,11 @@
 outputs, on device events, print one JSON line and append it to profiles/sht_bench.jsonl.
 
     python tools/sht_bench.py NLAT NLON LMAX C MEMBERS [--grid equiangular] [--calls K] [--rounds R]
+                              [--longitude {direct,fft,both}]
+
+``--longitude both`` (the default) times the direct-sum and the FFT longitude stage and the composition in one process,
+bracket after bracket in turn, and writes one line per longitude stage (field ``longitude``; the FFT's line also carries
+``direct_us``, the other path's time from the same run).
 
 Four operations: analysis (fp32 coefficients), synthesis, power_spectrum (fp64 on the way) and analysis + backward.  The
 composition is ``torch.fft.rfft`` along the longitudes and an fp64 ``einsum`` against a Legendre table ``[m, l, lat]`` that
@@ -9,13 +14,15 @@ is made on the host outside the timed region (``irfft`` and the transposed einsu
 alternate, bracket by bracket, on the same box; the figure of a side is the median of its brackets.
 
 fp64 flops issued by the fused path, per transform: 4 B nlat nlon (lmax + 1) C along the longitudes (two fma per point
-and order) and 2 B nlat (lmax + 1)(lmax + 2) C over the latitudes (two fma per latitude and (l, m >= 0)); the fraction
+and order; with the FFT the nominal 2.5 nlon log2 nlon a ring and channel) and 2 B nlat (lmax + 1)(lmax + 2) C over the latitudes (two fma per latitude and (l, m >= 0)); the fraction
 is of the 78.6 TF/s fp64 peak.  Compulsory bytes: the input read, the output written, the fp64 intermediate written and
-read; the fraction is of the 8 TB/s HBM peak.  Kernel times per stage come from one profiled call of each operation."""
+read; the fraction is of the 8 TB/s HBM peak.  Kernel times per stage come from one profiled call of each operation;
+``lon_kernel_fraction_of_8tbs`` sets the longitude kernels' compulsory bytes (x once, the ring once) against them."""
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -88,16 +95,17 @@ def bracket(fn, calls):
     return t0.elapsed_time(t1) / calls * 1e3                                 # us per call
 
 
-def alternate(a, b, calls, rounds, warmup):
+def alternate(fns, calls, rounds, warmup):
+    """Median microseconds per call of every function, their brackets taken in turn."""
     for _ in range(warmup):
-        a()
-        b()
+        for fn in fns:
+            fn()
     torch.cuda.synchronize()
-    ta, tb = [], []
+    times = [[] for _ in fns]
     for _ in range(rounds):
-        ta.append(bracket(a, calls))
-        tb.append(bracket(b, calls))
-    return statistics.median(ta), statistics.median(tb)
+        for t, fn in zip(times, fns):
+            t.append(bracket(fn, calls))
+    return [statistics.median(t) for t in times]
 
 
 def kernel_times(fns) -> dict:
@@ -132,12 +140,15 @@ def main() -> None:
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--longitude", choices=("direct", "fft", "both"), default="both")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sht_bench needs the MI355X")
     import gwen_amd
     dev = torch.device("cuda:0")
-    sh = gwen_amd.SphericalHarmonics(a.nlat, a.nlon, dev, lmax=a.lmax, grid=a.grid)
+    modes = ["direct", "fft"] if a.longitude == "both" else [a.longitude]
+    shs = {m: gwen_amd.SphericalHarmonics(a.nlat, a.nlon, dev, lmax=a.lmax, grid=a.grid, longitude=m) for m in modes}
+    sh = shs[modes[-1]]
     comp = Composition(sh, dev)
     g = torch.Generator(device=dev).manual_seed(23)
     B, N, T, L, C = a.members, a.nlat * a.nlon, sh.num_coefficients, sh.lmax, a.C
@@ -146,23 +157,27 @@ def main() -> None:
     gout = torch.randn(B, T, C, device=dev, generator=g)
     ccoef = comp.analysis(x)
     cgout = torch.randn_like(ccoef.real).to(ccoef.dtype)
-    xg, xc = x.clone().requires_grad_(), x.clone().requires_grad_()
+    xc = x.clone().requires_grad_()
 
-    def fused_backward():
-        xg.grad = None
-        sh.analysis(xg).backward(gout)
+    def fused(s):
+        xg = x.clone().requires_grad_()
+
+        def backward():
+            xg.grad = None
+            s.analysis(xg).backward(gout)
+
+        return {"analysis": lambda: s.analysis(x), "synthesis": lambda: s.synthesis(coef),
+                "power_spectrum": lambda: s.power_spectrum(x), "analysis_backward": backward}
 
     def composed_backward():
         xc.grad = None
         comp.analysis(xc).backward(cgout)
 
-    pairs = {
-        "analysis": (lambda: sh.analysis(x), lambda: comp.analysis(x)),
-        "synthesis": (lambda: sh.synthesis(coef), lambda: comp.synthesis(ccoef)),
-        "power_spectrum": (lambda: sh.power_spectrum(x), lambda: comp.power(x)),
-        "analysis_backward": (fused_backward, composed_backward),
-    }
-    lon_flops = 4.0 * B * a.nlat * a.nlon * (L + 1) * C
+    ops = {m: fused(shs[m]) for m in modes}
+    composed = {"analysis": lambda: comp.analysis(x), "synthesis": lambda: comp.synthesis(ccoef),
+                "power_spectrum": lambda: comp.power(x), "analysis_backward": composed_backward}
+    lon_flops = {"direct": 4.0 * B * a.nlat * a.nlon * (L + 1) * C,
+                 "fft": 2.5 * a.nlon * math.log2(max(a.nlon, 2)) * B * a.nlat * C}
     lat_flops = 2.0 * B * a.nlat * (L + 1) * (L + 2) * C
     ring_bytes = 8.0 * B * a.nlat * (2 * L + 1) * C
     nbytes = {"analysis": 4.0 * B * N * C + 4.0 * B * T * C + 2 * ring_bytes}
@@ -170,29 +185,43 @@ def main() -> None:
     nbytes["power_spectrum"] = 4.0 * B * N * C + 2 * 8.0 * B * T * C + 8.0 * B * (L + 1) * C + 2 * ring_bytes
     nbytes["analysis_backward"] = 2 * nbytes["analysis"]
     passes = {"analysis": 1, "synthesis": 1, "power_spectrum": 1, "analysis_backward": 2}
-    line = {"tool": "sht_bench", "grid": a.grid, "nlat": a.nlat, "nlon": a.nlon, "lmax": L, "C": C, "members": B,
-            "calls": a.calls, "rounds": a.rounds, "flops_longitude_stage": lon_flops, "flops_latitude_stage": lat_flops}
-    for name, (fused, composed) in pairs.items():
-        us, us_torch = alternate(fused, composed, a.calls, a.rounds, a.warmup)
-        flops = passes[name] * (lon_flops + lat_flops)
-        line[name] = {"us": round(us, 1), "torch_us": round(us_torch, 1), "speedup": round(us_torch / us, 3),
-                      "fraction_of_fp64_peak": round(flops / (us * 1e-6) / PEAK_FP64_FLOPS, 4),
-                      "fraction_of_8tbs_peak": round(nbytes[name] / (us * 1e-6) / PEAK_BYTES_PER_S, 4)}
-    line["kernel_us"] = kernel_times([pairs["analysis"][0], pairs["synthesis"][0]])
-    got = sh.analysis(x, dtype=torch.float64)
+    lines = {m: {"tool": "sht_bench", "longitude": m, "grid": a.grid, "nlat": a.nlat, "nlon": a.nlon, "lmax": L, "C": C,
+                 "members": B, "calls": a.calls, "rounds": a.rounds, "flops_longitude_stage": lon_flops[m],
+                 "flops_latitude_stage": lat_flops} for m in modes}
+    for name in composed:
+        times = alternate([ops[m][name] for m in modes] + [composed[name]], a.calls, a.rounds, a.warmup)
+        us_torch = times[-1]
+        for m, us in zip(modes, times):
+            flops = passes[name] * (lon_flops[m] + lat_flops)
+            lines[m][name] = {"us": round(us, 1), "torch_us": round(us_torch, 1), "speedup": round(us_torch / us, 3),
+                              "fraction_of_fp64_peak": round(flops / (us * 1e-6) / PEAK_FP64_FLOPS, 4),
+                              "fraction_of_8tbs_peak": round(nbytes[name] / (us * 1e-6) / PEAK_BYTES_PER_S, 4)}
+            if m == "fft" and "direct" in modes:
+                lines[m][name]["direct_us"] = round(times[0], 1)
+                lines[m][name]["fft_over_direct"] = round(us / times[0], 3)
+    lon_bytes = 4.0 * B * N * C + ring_bytes                                 # x once, the ring once
+    for m in modes:
+        kernels = kernel_times([ops[m]["analysis"], ops[m]["synthesis"]])
+        lines[m]["kernel_us"] = kernels
+        stage = {k: v for k, v in kernels.items() if k.startswith("k_sht_lon") and isinstance(v, float) and v > 0}
+        lines[m]["lon_kernel_fraction_of_8tbs"] = {k: round(lon_bytes / (v * 1e-6) / PEAK_BYTES_PER_S, 4)
+                                                   for k, v in stage.items()}
     want = comp.analysis(x)
     rows = torch.arange(L + 1, device=dev)
-    diff = 0.0
-    for m in (0, 1, L):                                                      # a few orders against the composition
-        r = rows[m:] ** 2 + rows[m:]
-        diff = max(diff, float((got[:, r + m] - want[:, m:, m].real).abs().max()),
-                   float((got[:, r - m] + want[:, m:, m].imag).abs().max()) if m else 0.0)
-    line["max_abs_diff_vs_torch"] = diff
-    text = json.dumps(line)
-    print(text, flush=True)
+    for mode in modes:
+        got = shs[mode].analysis(x, dtype=torch.float64)
+        diff = 0.0
+        for m in (0, 1, L):                                                  # a few orders against the composition
+            r = rows[m:] ** 2 + rows[m:]
+            diff = max(diff, float((got[:, r + m] - want[:, m:, m].real).abs().max()),
+                       float((got[:, r - m] + want[:, m:, m].imag).abs().max()) if m else 0.0)
+        lines[mode]["max_abs_diff_vs_torch"] = diff
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    with open(os.path.join(ROOT, "profiles", "sht_bench.jsonl"), "a") as fh:
-        fh.write(text + "\n")
+    for mode in modes:
+        text = json.dumps(lines[mode])
+        print(text, flush=True)
+        with open(os.path.join(ROOT, "profiles", "sht_bench.jsonl"), "a") as fh:
+            fh.write(text + "\n")
 
 
 if __name__ == "__main__":

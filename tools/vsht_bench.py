@@ -4,6 +4,11 @@ same outputs, on device events, print one JSON line a shape and append it to pro
     python tools/vsht_bench.py                                  the four standard shapes: 721 x 1440 lmax 360 and
                                                                 361 x 720 lmax 180, 16 and 64 channels, 4 members
     python tools/vsht_bench.py NLAT NLON LMAX C MEMBERS [--grid equiangular] [--calls K] [--rounds R]
+                               [--longitude {direct,fft,both}]
+
+``--longitude both`` (the default) times the direct-sum and the FFT longitude stage and the composition in one process,
+bracket after bracket in turn, and writes one line per longitude stage (field ``longitude``; the FFT's line also carries
+``direct_us``, the other path's time from the same run).
 
 Four operations: vector_analysis (fp32 coefficients), vector_synthesis, kinetic_energy_spectrum (fp64 on the way) and
 vector_analysis + backward.  The composition is ``torch.fft.rfft`` along the longitudes of u and v and fp64 ``einsum``s
@@ -21,6 +26,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import re
 import statistics
@@ -119,16 +125,17 @@ def bracket(fn, calls):
     return t0.elapsed_time(t1) / calls * 1e3                                 # us per call
 
 
-def alternate(a, b, calls, rounds, warmup):
+def alternate(fns, calls, rounds, warmup):
+    """Median microseconds per call of every function, their brackets taken in turn."""
     for _ in range(warmup):
-        a()
-        b()
+        for fn in fns:
+            fn()
     torch.cuda.synchronize()
-    ta, tb = [], []
+    times = [[] for _ in fns]
     for _ in range(rounds):
-        ta.append(bracket(a, calls))
-        tb.append(bracket(b, calls))
-    return statistics.median(ta), statistics.median(tb)
+        for t, fn in zip(times, fns):
+            t.append(bracket(fn, calls))
+    return [statistics.median(t) for t in times]
 
 
 def kernel_times(fns) -> dict:
@@ -141,7 +148,7 @@ def kernel_times(fns) -> dict:
             torch.cuda.synchronize()
         out = {}
         for e in prof.key_averages():
-            hit = re.search(r"k_v?sht_(lon|lat)_(fwd|inv)", e.key)
+            hit = re.search(r"k_v?sht_(lon|lat)_(fft_)?(fwd|inv)", e.key)
             if hit:
                 total = getattr(e, "device_time_total", None)
                 if total is None:
@@ -152,10 +159,14 @@ def kernel_times(fns) -> dict:
         return {"error": repr(exc)[:200]}
 
 
-def run(nlat, nlon, lmax, C, members, grid, calls, rounds, warmup) -> dict:
+def run(nlat, nlon, lmax, C, members, grid, calls, rounds, warmup, longitude="both") -> list:
+    """One line per longitude stage."""
     import gwen_amd
     dev = torch.device("cuda:0")
-    sh = gwen_amd.SphericalHarmonics(nlat, nlon, dev, lmax=lmax, grid=grid, workspace_bytes=4 << 30)
+    modes = ["direct", "fft"] if longitude == "both" else [longitude]
+    shs = {m: gwen_amd.SphericalHarmonics(nlat, nlon, dev, lmax=lmax, grid=grid, workspace_bytes=4 << 30, longitude=m)
+           for m in modes}
+    sh = shs[modes[-1]]
     comp = Composition(sh, dev)
     g = torch.Generator(device=dev).manual_seed(29)
     B, N, T, L = members, nlat * nlon, sh.num_coefficients, sh.lmax
@@ -164,24 +175,29 @@ def run(nlat, nlon, lmax, C, members, grid, calls, rounds, warmup) -> dict:
     gv, gd = torch.randn(B, T, C, device=dev, generator=g), torch.randn(B, T, C, device=dev, generator=g)
     cvort, cdiv = comp.analysis(u, v)
     cgv, cgd = torch.randn_like(cvort.real).to(cvort.dtype), torch.randn_like(cvort.real).to(cvort.dtype)
-    ug, vg = u.clone().requires_grad_(), v.clone().requires_grad_()
     uc, vc = u.clone().requires_grad_(), v.clone().requires_grad_()
 
-    def fused_backward():
-        ug.grad = vg.grad = None
-        torch.autograd.backward(sh.vector_analysis(ug, vg), [gv, gd])
+    def fused(s):
+        ug, vg = u.clone().requires_grad_(), v.clone().requires_grad_()
+
+        def backward():
+            ug.grad = vg.grad = None
+            torch.autograd.backward(s.vector_analysis(ug, vg), [gv, gd])
+
+        return {"vector_analysis": lambda: s.vector_analysis(u, v),
+                "vector_synthesis": lambda: s.vector_synthesis(vort, div),
+                "kinetic_energy_spectrum": lambda: s.kinetic_energy_spectrum(u=u, v=v),
+                "vector_analysis_backward": backward}
 
     def composed_backward():
         uc.grad = vc.grad = None
         torch.autograd.backward(comp.analysis(uc, vc), [cgv, cgd])
 
-    pairs = {
-        "vector_analysis": (lambda: sh.vector_analysis(u, v), lambda: comp.analysis(u, v)),
-        "vector_synthesis": (lambda: sh.vector_synthesis(vort, div), lambda: comp.synthesis(cvort, cdiv)),
-        "kinetic_energy_spectrum": (lambda: sh.kinetic_energy_spectrum(u=u, v=v), lambda: comp.energy(u, v)),
-        "vector_analysis_backward": (fused_backward, composed_backward),
-    }
-    lon_flops = 8.0 * B * nlat * nlon * (L + 1) * C
+    ops = {m: fused(shs[m]) for m in modes}
+    composed = {"vector_analysis": lambda: comp.analysis(u, v), "vector_synthesis": lambda: comp.synthesis(cvort, cdiv),
+                "kinetic_energy_spectrum": lambda: comp.energy(u, v), "vector_analysis_backward": composed_backward}
+    lon_flops = {"direct": 8.0 * B * nlat * nlon * (L + 1) * C,
+                 "fft": 2 * 2.5 * nlon * math.log2(max(nlon, 2)) * B * nlat * C}
     lat_flops = 8.0 * B * nlat * (L + 1) * (L + 2) * C
     ring_bytes = 2 * 8.0 * B * nlat * (2 * L + 1) * C
     nbytes = {"vector_analysis": 2 * 4.0 * B * N * C + 2 * 4.0 * B * T * C + 2 * ring_bytes}
@@ -190,27 +206,33 @@ def run(nlat, nlon, lmax, C, members, grid, calls, rounds, warmup) -> dict:
                                          + 2 * ring_bytes)
     nbytes["vector_analysis_backward"] = 2 * nbytes["vector_analysis"]
     passes = {"vector_analysis": 1, "vector_synthesis": 1, "kinetic_energy_spectrum": 1, "vector_analysis_backward": 2}
-    line = {"tool": "vsht_bench", "grid": grid, "nlat": nlat, "nlon": nlon, "lmax": L, "C": C, "members": B,
-            "calls": calls, "rounds": rounds, "flops_longitude_stage": lon_flops, "flops_latitude_stage": lat_flops,
-            "composition_table_bytes": 4 * comp.q.numel() * 16}
-    for name, (fused, composed) in pairs.items():
-        us, us_torch = alternate(fused, composed, calls, rounds, warmup)
-        flops = passes[name] * (lon_flops + lat_flops)
-        line[name] = {"us": round(us, 1), "torch_us": round(us_torch, 1), "speedup": round(us_torch / us, 3),
-                      "faster": "fused" if us < us_torch else "torch",
-                      "fraction_of_fp64_peak": round(flops / (us * 1e-6) / PEAK_FP64_FLOPS, 4),
-                      "fraction_of_8tbs_peak": round(nbytes[name] / (us * 1e-6) / PEAK_BYTES_PER_S, 4)}
-    line["kernel_us"] = kernel_times([pairs["vector_analysis"][0], pairs["vector_synthesis"][0]])
-    got = sh.vector_analysis(u, v, dtype=torch.float64)
+    lines = {m: {"tool": "vsht_bench", "longitude": m, "grid": grid, "nlat": nlat, "nlon": nlon, "lmax": L, "C": C,
+                 "members": B, "calls": calls, "rounds": rounds, "flops_longitude_stage": lon_flops[m],
+                 "flops_latitude_stage": lat_flops, "composition_table_bytes": 4 * comp.q.numel() * 16} for m in modes}
+    for name in composed:
+        times = alternate([ops[m][name] for m in modes] + [composed[name]], calls, rounds, warmup)
+        us_torch = times[-1]
+        for m, us in zip(modes, times):
+            flops = passes[name] * (lon_flops[m] + lat_flops)
+            lines[m][name] = {"us": round(us, 1), "torch_us": round(us_torch, 1), "speedup": round(us_torch / us, 3),
+                              "faster": "fused" if us < us_torch else "torch",
+                              "fraction_of_fp64_peak": round(flops / (us * 1e-6) / PEAK_FP64_FLOPS, 4),
+                              "fraction_of_8tbs_peak": round(nbytes[name] / (us * 1e-6) / PEAK_BYTES_PER_S, 4)}
+            if m == "fft" and "direct" in modes:
+                lines[m][name]["direct_us"] = round(times[0], 1)
+                lines[m][name]["fft_over_direct"] = round(us / times[0], 3)
     rows = torch.arange(L + 1, device=dev)
-    diff = 0.0
-    for m in (0, 1, L):                                                      # a few orders against the composition
-        r = rows[max(m, 1):] ** 2 + rows[max(m, 1):]
-        for have, want in zip(got, (cvort, cdiv)):
-            diff = max(diff, float((have[:, r + m] - want[:, max(m, 1):, m].real).abs().max()),
-                       float((have[:, r - m] + want[:, max(m, 1):, m].imag).abs().max()) if m else 0.0)
-    line["max_abs_diff_vs_torch"] = diff
-    return line
+    for mode in modes:
+        lines[mode]["kernel_us"] = kernel_times([ops[mode]["vector_analysis"], ops[mode]["vector_synthesis"]])
+        got = shs[mode].vector_analysis(u, v, dtype=torch.float64)
+        diff = 0.0
+        for m in (0, 1, L):                                                  # a few orders against the composition
+            r = rows[max(m, 1):] ** 2 + rows[max(m, 1):]
+            for have, want in zip(got, (cvort, cdiv)):
+                diff = max(diff, float((have[:, r + m] - want[:, max(m, 1):, m].real).abs().max()),
+                           float((have[:, r - m] + want[:, max(m, 1):, m].imag).abs().max()) if m else 0.0)
+        lines[mode]["max_abs_diff_vs_torch"] = diff
+    return [lines[m] for m in modes]
 
 
 def main() -> None:
@@ -220,6 +242,7 @@ def main() -> None:
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--longitude", choices=("direct", "fft", "both"), default="both")
     a = ap.parse_args()
     if len(a.shape) not in (0, 5):
         ap.error("give NLAT NLON LMAX C MEMBERS, or nothing")
@@ -227,10 +250,11 @@ def main() -> None:
         raise SystemExit("vsht_bench needs the MI355X")
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
     for shape in ([tuple(a.shape)] if a.shape else STANDARD):
-        text = json.dumps(run(*shape, a.grid, a.calls, a.rounds, a.warmup))
-        print(text, flush=True)
-        with open(os.path.join(ROOT, "profiles", "vsht_bench.jsonl"), "a") as fh:
-            fh.write(text + "\n")
+        for line in run(*shape, a.grid, a.calls, a.rounds, a.warmup, a.longitude):
+            text = json.dumps(line)
+            print(text, flush=True)
+            with open(os.path.join(ROOT, "profiles", "vsht_bench.jsonl"), "a") as fh:
+                fh.write(text + "\n")
         torch.cuda.empty_cache()
 
 
