@@ -146,6 +146,9 @@ SIGNATURES = {
     "gwen_gcn_layer_tuned3_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int, _vp]),
     "gwen_gcn_layer_packed_mode": (_int, [_i64, _i64, _int]),
+    "gwen_gcn_layer_tuned4_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int, _vp, _int]),
+    "gwen_gcn_layer_store_mode": (_int, [_i64, _i64, _int]),
     "gwen_gcn_layer_blocks_per_cu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                             _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int,
                                             C.POINTER(C.c_int)]),
@@ -164,6 +167,9 @@ SIGNATURES = {
     "gwen_gcn_chain_tuned3_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                          _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int, _vp]),
     "gwen_gcn_chain_packed_mode": (_int, [_i64, _i64, _i64, _int, _int]),
+    "gwen_gcn_chain_tuned4_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
+                                         _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int, _vp, _int]),
+    "gwen_gcn_chain_store_mode": (_int, [_i64, _i64, _i64, _int, _int]),
     "gwen_gcn_chain_blocks_per_cu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _int,
                                             _int, _i64, _i64, _i64, _int, _int, _int, _int, _int, _vp, _vp, _int,
                                             C.POINTER(C.c_int)]),

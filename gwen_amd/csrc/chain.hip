@@ -21,6 +21,9 @@
 // (chain_pin says per shape whether it is pinned under the first row loads or left to the optimiser from there on).
 // k_gather loads its bias above the gather as well (from x when there is none; nothing is added then), not in the sink,
 // where it was a dependent round trip at the tail of every wave.
+// Stores (template argument ST of k_chain and k_gather; gather_rows.h, store_out): as K4's -- 1 plain, 3 the same 16-byte
+// stores written through (sc1), at both store sites of k_chain (phase 2 when nothing is chained, phase 3) and in k_gather's
+// sink.  Which shapes run 3: chain_store_mode.  Modes 2 / 4 (whole rows through LDS) are not built.
 #include "common.h"
 #include "dispatch.h"
 #include "gather_rows.h"
@@ -148,7 +151,10 @@ constexpr bool chain_pin(int fin, int f1, int f2, int ns, int ge) {
 // before NS because profile tooling keys this kernel's name on its first and its last template argument.
 // PK: packed W (packw.hip; narrow kernels only): W1 and W2 point to the weights' bf16 images in fragment order and the B
 // fragments are plain loads at the top of the kernel.  false compiles to the code the kernel had.
-template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int IM, bool PK, int NS>
+// ST: store mode of both store sites -- phase 2 at F2 == 0, and phase 3 (gather_rows.h, store_out): 1 = plain 16-byte
+// stores, the code the kernel had; 3 = the same addresses written through.  Narrow kernels on the uniform layout only;
+// in front of NS for the reason above.
+template <int FIN, int F1, int F2, bool PRE, bool UNI, int GE, int D, int BRQ, int IM, bool PK, int ST, int NS>
 __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W1,
@@ -157,6 +163,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
   static_assert(IM == 1 || (IM == 2 && UNI && FIN <= 64 && F1 <= 64), "index records: narrow kernels, uniform layout");
   static_assert(!PK || (FIN <= 64 && F1 <= 64), "packed W: narrow kernels");
+  static_assert(ST == 1 || (ST == 3 && UNI && FIN <= 64 && F1 <= 64), "store modes: narrow kernels, uniform layout");
   __shared__ __attribute__((aligned(16))) __bf16 lds[C::lds_elems];
   constexpr int kImg0 = C::BR * C::PB0, kImg1 = C::BR * C::PB1;
   __bf16 *t0 = lds;                                                      // aggregated rows: NS x [BR][PB0]
@@ -253,8 +260,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
       for (int s = 0; s < NS; ++s)
         *reinterpret_cast<bf16x4 *>(t1 + s * kImg1 + lr * C::PB1 + j1 * 16 + 4 * mh) = im[s];
     } else {
-      if (b0 + lr < N)
-        *reinterpret_cast<float4_t *>(om + (int64_t)(b0 + lr) * F1 + j1 * 16 + 4 * mh) = o;
+      if (b0 + lr < N) gwen::store_out<ST>(om + (int64_t)(b0 + lr) * F1 + j1 * 16 + 4 * mh, o);
     }
   }
   if constexpr (C::ALIAS) {
@@ -279,9 +285,7 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
       f32x4 d = {0.f, 0.f, 0.f, 0.f};
       d = b2.mma(t1, kImg1, (tt * kTile + mi) * C::PB1, mh, d);
       const int r = b0 + tt * kTile + mi;
-      if (r < N)
-        *reinterpret_cast<float4_t *>(om + (int64_t)r * F2 + j2 * 16 + 4 * mh) =
-            float4_t{d[0], d[1], d[2], d[3]};
+      if (r < N) gwen::store_out<ST>(om + (int64_t)r * F2 + j2 * 16 + 4 * mh, float4_t{d[0], d[1], d[2], d[3]});
     }
   }
 }
@@ -289,7 +293,8 @@ __global__ __launch_bounds__((F1 > 64 ? 512 : 256)) void k_chain(
 // Activation-first layer with nothing chained: out = act(A~ h + bias) on the grouped layout (the
 // fma form of K2; K2 itself keeps the rounded-product order that is bit-identical to the CPU path).
 // D: accepted for symmetry with K4 / K5 -- a wave gathers ONE pass here, so both depths are the same code
-template <int FIN, bool UNI, int GE = 8, int D = 1, int IM = 1>
+// ST: store mode (gather_rows.h, store_out): the rows are stored whole already, so 1 (plain) and 3 (written through) only
+template <int FIN, bool UNI, int GE = 8, int D = 1, int IM = 1, int ST = 1>
 __global__ __launch_bounds__(256) void k_gather(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ bias,
@@ -316,8 +321,7 @@ __global__ __launch_bounds__(256) void k_gather(
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc[e] = acc[e] < 0.0f ? 0.0f : acc[e];
         }
-        if (lb * BR + lr < N)
-          *reinterpret_cast<float4_t *>(om + (int64_t)(lb * BR + lr) * FIN + gl * 4) = acc;
+        if (lb * BR + lr < N) gwen::store_out<ST>(om + (int64_t)(lb * BR + lr) * FIN + gl * 4, acc);
       });
 }
 
@@ -328,6 +332,7 @@ struct ChainArgs {
   float *out;
   int64_t N, members, msx, mso;
   int relu, entries;
+  int store_mode;                                          // 1 or 3, resolved (k_chain's / k_gather's ST)
   hipStream_t st;
   int *probe;                                              // not NULL: launch nothing, store the kernel's blocks per CU
 };
@@ -361,6 +366,13 @@ int launch_gather(const ChainArgs &a) {
     GWEN_LAUNCH_CHECK();
     return (int)GWEN_OK;
   };
+  if constexpr (FIN <= 64 && D == 1) {         // written through: the uniform layout, up to 64 channels (both depths are one code)
+    if (a.store_mode == 3) {
+      if (a.rowptr) return GWEN_EINVAL;
+      return a.entries == 7 ? run(&k_gather<FIN, true, 7, 1, IM, 3>) : run(&k_gather<FIN, true, 8, 1, IM, 3>);
+    }
+  }
+  if (a.store_mode != 1) return GWEN_EINVAL;
   if constexpr (IM == 2) {                     // index records: the uniform layout, up to 64 channels
     if (a.rowptr) return GWEN_EINVAL;
     return a.entries == 7 ? run(&k_gather<FIN, true, 7, D, 2>) : run(&k_gather<FIN, true, 8, D, 2>);
@@ -372,7 +384,7 @@ int launch_gather(const ChainArgs &a) {
   return run(&k_gather<FIN, true, 8, D>);
 }
 
-template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ, int IM, bool PK>
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int BRQ, int IM, bool PK, int ST>
 int launch_br(const ChainArgs &a) {
   using C = Cfg<FIN, F1, F2, PRE, NS, BRQ>;
   static_assert(C::geo.fits(kLdsCU), "one block must fit a CU's LDS");
@@ -388,16 +400,16 @@ int launch_br(const ChainArgs &a) {
     GWEN_LAUNCH_CHECK();
     return (int)GWEN_OK;
   };
-  if constexpr (IM == 2) {                     // index records: the uniform layout, narrow kernels
+  if constexpr (IM == 2 || ST != 1) {          // index records, store modes: the uniform layout, narrow kernels
     if (a.rowptr) return GWEN_EINVAL;
-    return a.entries == 7 ? run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 2, PK, NS>)
-                          : run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 2, PK, NS>);
+    return a.entries == 7 ? run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, IM, PK, ST, NS>)
+                          : run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, IM, PK, ST, NS>);
   }
-  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, 1, PK, NS>);
+  if (a.rowptr) return run(&k_chain<FIN, F1, F2, PRE, false, 8, D, BRQ, 1, PK, 1, NS>);
   if constexpr (narrow(FIN, F1)) {
-    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 1, PK, NS>);
+    if (a.entries == 7) return run(&k_chain<FIN, F1, F2, PRE, true, 7, D, BRQ, 1, PK, 1, NS>);
   }
-  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 1, PK, NS>);
+  return run(&k_chain<FIN, F1, F2, PRE, true, 8, D, BRQ, 1, PK, 1, NS>);
 }
 
 // Rows per block of a packed-W kernel (PK) at gather depth 2 where launch_ns would take 112; 0: the same.  64 -> 64 -> 32
@@ -411,8 +423,9 @@ constexpr int packed_rows(int fin, int f1, int f2, int ns) { return fin == 64 &&
 // 893 blocks) and 96 / 112 rows measured SLOWER at depth 1 (23.3 / 23.5 against 22.2 us), so depth 1 keeps 64.  At depth
 // 2 one member whose 64-row grid is more than one resident round runs 112-row blocks where the width allows it: the
 // two-deep gather fills and drains once per block (20.1 against 20.8 us).
-template <int FIN, int F1, int F2, bool PRE, int NS, int D, int IM, bool PK = false>
+template <int FIN, int F1, int F2, bool PRE, int NS, int D, int IM, bool PK = false, int ST = 1>
 int launch_ns(const ChainArgs &a, int block_rows) {
+  static_assert(ST == 1 || narrow(FIN, F1), "store modes: narrow kernels only");
   static_assert(IM == 1 || narrow(FIN, F1), "index records: narrow kernels only");
   static_assert(!PK || narrow(FIN, F1), "packed W: narrow kernels only");
   int brq = block_rows == 0 || block_rows == Cfg<FIN, F1, F2, PRE, NS>::BR ? 64 : block_rows;   // BRQ 64 = the own size
@@ -424,9 +437,9 @@ int launch_ns(const ChainArgs &a, int block_rows) {
       static int per_cu[3] = {0, 0, 0};
       const int v = a.rowptr ? 2 : (a.entries == 7 ? 0 : 1);
       if (per_cu[v] == 0) {
-        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, 1, PK, NS>)
-                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, IM, PK, NS>)
-                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, IM, PK, NS>);
+        const void *k = v == 2   ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, false, 8, D, 64, 1, PK, 1, NS>)
+                        : v == 1 ? reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 8, D, 64, IM, PK, ST, NS>)
+                                 : reinterpret_cast<const void *>(&k_chain<FIN, F1, F2, PRE, true, 7, D, 64, IM, PK, ST, NS>);
         int nbk = 0;
         GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbk, k, Cfg<FIN, F1, F2, PRE, NS>::NWB * 64, 0));
         per_cu[v] = nbk < 1 ? 1 : nbk;
@@ -437,7 +450,7 @@ int launch_ns(const ChainArgs &a, int block_rows) {
   }
   return gwen::dispatch(gwen::ints<64, 80, 96, 112>{}, brq, [&](auto brv) {
     constexpr int BRQ = decltype(brv)::value;
-    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ, PK)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ, IM, PK>(a);
+    if constexpr (BRQ == 64 || rows_ok(FIN, F1, BRQ, PK)) return launch_br<FIN, F1, F2, PRE, NS, D, BRQ, IM, PK, ST>(a);
     else return (int)GWEN_EINVAL;
   });
 }
@@ -496,6 +509,24 @@ extern "C" int gwen_gcn_chain_packed_mode(int64_t Fin, int64_t F1, int64_t F2, i
   return chain_packed(Fin, F1, F2, pre, gwen::images_of(contract)) ? 2 : 1;
 }
 
+// The library's store mode per (Fin, F1, F2, pre, images) on the uniform layout (gather_rows.h, store_out): 3, the 16-byte
+// output stores written through, only where the kernel measured faster on the MI355X by the rule of the depth and index
+// tables ("Stores"; profiles/store_*).  F1 == 0: k_gather.  The modes exist for the narrow kernels on the
+// uniform layout at the shape's own depth and index mode; everything else has mode 1 only.
+// 64 -> 64 -> 32 and activation-first 32 -> 16 on bf16x6, the only split that was measured, and k_gather<16>, which
+// contracts nothing and is one kernel whatever `contract` says (the stack launcher calls it with bf16x3)
+// (profiles/store_kernel_ab.tsv).
+static constexpr int chain_store_mode(int64_t fin, int64_t f1, int64_t f2, int pre, int ns) {
+  if (pre && f1 == 0) return fin == 16 ? 3 : 1;
+  return ns == 3 && ((!pre && fin == 64 && f1 == 64 && f2 == 32) || (pre && fin == 32 && f1 == 16 && f2 == 0)) ? 3 : 1;
+}
+
+extern "C" int gwen_gcn_chain_store_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract) {
+  if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return 0;
+  if (!narrow(Fin, F1)) return 1;
+  return chain_store_mode(Fin, F1, F2, pre, gwen::images_of(contract));
+}
+
 // entries = 7: the caller's promise (uniform layout, every row at most 7 stored entries), see gwen_gcn_layer_entries_f32
 // depth, block_rows, index_mode: 0 = the library's choice (chain_depth; launch_ns; chain_index_mode); none changes a
 // value.  index_mode 1: every lane loads its row's group; 2: index records -- narrow kernels (Fin, F1 <= 64) on the
@@ -504,6 +535,8 @@ extern "C" int gwen_gcn_chain_packed_mode(int64_t Fin, int64_t F1, int64_t F2, i
 // split in the kernel; 2: the images are read (W1 / W2 may be NULL) -- narrow kernels with a contraction only, and an
 // image for every weight the form has, GWEN_EINVAL otherwise; 0: the library's choice -- the images where all of them are
 // given and gwen_gcn_chain_packed_mode says 2.  No value changes.
+// store_mode: as gwen_gcn_layer_tuned4_f32 -- 0 the library's choice (chain_store_mode, one member only), 1 plain, 3 written
+// through (narrow kernels, uniform layout, the shape's own depth and index mode; GWEN_EINVAL elsewhere), 2 and 4 not built
 // probe: not NULL = launch nothing and store the blocks per CU that hipOccupancyMaxActiveBlocksPerMultiprocessor reports for
 // the kernel this call would launch (forms with a contraction only)
 static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -511,9 +544,10 @@ static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *v
                        const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
                        int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
                        int64_t mstride_o, int contract, int entries, int depth, int block_rows,
-                       int index_mode, const void *W1p, const void *W2p, int packed,
+                       int index_mode, const void *W1p, const void *W2p, int packed, int store_mode,
                        gwen_stream_t stream_, int *probe) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
+  if (store_mode < 0 || store_mode > 4) return GWEN_EINVAL;
   if (packed < 0 || packed > 2) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
@@ -521,6 +555,12 @@ static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *v
   if (!gwen_gcn_chain_supported(Fin, F1, F2, pre, contract)) return GWEN_EINVAL;
   const bool plain = pre && F1 == 0;                       // activation-first, nothing chained: k_gather
   if (index_mode == 2 && (rowptr || !narrow(Fin, F1))) return GWEN_EINVAL;     // records: uniform layout, narrow kernels
+  // store modes: narrow kernels, uniform layout, the shape's own depth (k_gather: either) and index mode; row stores: not built
+  const bool can_store = narrow(Fin, F1) && !rowptr &&
+                         (plain || depth == 0 || depth == gwen_gcn_chain_depth(Fin, F1, F2, pre, contract)) &&
+                         (index_mode == 0 || index_mode == gwen_gcn_chain_index_mode(Fin, F1, F2, pre, contract));
+  if (store_mode > 1 && (!can_store || store_mode != 3)) return GWEN_EINVAL;
+  if (store_mode == 0) store_mode = can_store && members == 1 ? gwen_gcn_chain_store_mode(Fin, F1, F2, pre, contract) : 1;
   const bool can_pack = !plain && narrow(Fin, F1);                             // packed W: narrow kernels that contract
   const bool have_images = W1p && (F2 == 0 || W2p);
   if (packed == 2 && (!can_pack || !have_images)) return GWEN_EINVAL;
@@ -542,7 +582,7 @@ static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *v
   if (depth == 0) depth = rowptr ? 1 : gwen_gcn_chain_depth(Fin, F1, F2, pre, contract);
   if (index_mode == 0) index_mode = rowptr ? 1 : gwen_gcn_chain_index_mode(Fin, F1, F2, pre, contract);
   if (probe && plain) return GWEN_EINVAL;
-  const ChainArgs a{rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, mstride_o, relu, entries,
+  const ChainArgs a{rowptr, col, val, x, W1, W2, bias, out, N, members, mstride_x, mstride_o, relu, entries, store_mode,
                     gwen_stream(stream_), probe};
   using Widths = gwen::ints<16, 32, 64, 128>;
   using Depths = gwen::ints<1, 2>;
@@ -550,7 +590,8 @@ static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *v
   return gwen::dispatch(Widths{}, Fin, [&](auto fi) {
     constexpr int FI = decltype(fi)::value;
     if (plain) {
-      return gwen::dispatch(Depths{}, FI <= 64 ? depth : 1, [&](auto dv) {         // gather depth 2: up to 64 channels
+      // k_gather is one code at both depths: the written-through form exists once, at depth 1
+      return gwen::dispatch(Depths{}, FI <= 64 && store_mode == 1 ? depth : 1, [&](auto dv) {   // gather depth 2: up to 64 channels
         return gwen::dispatch(Modes{}, index_mode, [&](auto iv) {
           constexpr int D = decltype(dv)::value, IM = decltype(iv)::value;
           if constexpr (FI <= 64 || (D == 1 && IM == 1)) return launch_gather<FI, D, IM>(a);
@@ -572,6 +613,13 @@ static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *v
                   // bf16x6 only where its three images fit a CU's LDS (gwen_gcn_chain_supported refuses the others)
                   if constexpr (Geom(FI, FA, FB, NS, 64).fits(kLdsCU) && ((D == 1 && IM == 1) || narrow(FI, FA))) {
                     if constexpr (narrow(FI, FA)) {
+                      // the written-through kernels: at the depth and index mode the library launches for the shape
+                      if constexpr (D == chain_depth(FI, FA, FB, NS) && IM == chain_index_mode(FI, FA, FB, PRE, NS)) {
+                        if (store_mode == 3)
+                          return packed == 2 ? launch_ns<FI, FA, FB, PRE, NS, D, IM, true, 3>(a, block_rows)
+                                             : launch_ns<FI, FA, FB, PRE, NS, D, IM, false, 3>(a, block_rows);
+                      }
+                      if (store_mode != 1) return (int)GWEN_EINVAL;
                       if (packed == 2) return launch_ns<FI, FA, FB, PRE, NS, D, IM, true>(a, block_rows);
                     }
                     return launch_ns<FI, FA, FB, PRE, NS, D, IM>(a, block_rows);
@@ -590,6 +638,17 @@ static int chain_tuned(const int32_t *rowptr, const int32_t *col, const float *v
   });
 }
 
+extern "C" int gwen_gcn_chain_tuned4_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W1, const float *W2,
+                                         const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
+                                         int64_t F2, int pre, int relu, int64_t members, int64_t mstride_x,
+                                         int64_t mstride_o, int contract, int entries, int depth, int block_rows,
+                                         int index_mode, const void *W1p, const void *W2p, int packed,
+                                         gwen_stream_t stream_, int store_mode) {
+  return chain_tuned(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x, mstride_o,
+                     contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, store_mode, stream_, nullptr);
+}
+
 extern "C" int gwen_gcn_chain_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val,
                                          const float *x, const float *W1, const float *W2,
                                          const float *bias, float *out, int64_t N, int64_t Fin, int64_t F1,
@@ -597,8 +656,8 @@ extern "C" int gwen_gcn_chain_tuned3_f32(const int32_t *rowptr, const int32_t *c
                                          int64_t mstride_o, int contract, int entries, int depth, int block_rows,
                                          int index_mode, const void *W1p, const void *W2p, int packed,
                                          gwen_stream_t stream_) {
-  return chain_tuned(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x, mstride_o,
-                     contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, stream_, nullptr);
+  return gwen_gcn_chain_tuned4_f32(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x,
+                                   mstride_o, contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, stream_, 0);
 }
 
 extern "C" int gwen_gcn_chain_blocks_per_cu(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -610,7 +669,7 @@ extern "C" int gwen_gcn_chain_blocks_per_cu(const int32_t *rowptr, const int32_t
                                             int *blocks_per_cu) {
   if (!blocks_per_cu || N <= 0 || members <= 0) return GWEN_EINVAL;
   return chain_tuned(rowptr, col, val, x, W1, W2, bias, out, N, Fin, F1, F2, pre, relu, members, mstride_x, mstride_o,
-                     contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, nullptr, blocks_per_cu);
+                     contract, entries, depth, block_rows, index_mode, W1p, W2p, packed, 0, nullptr, blocks_per_cu);
 }
 
 extern "C" int gwen_gcn_chain_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,

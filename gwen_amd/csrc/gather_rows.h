@@ -425,4 +425,22 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
   }
 }
 
+// The 16-byte output store of K4 / K5's epilogues and of k_gather.  ST (the kernels' store mode):
+//   1  a plain store -- the statement the kernels had, instruction for instruction;
+//   3  the same address and bytes WRITTEN THROUGH (the sc1 bit): the line goes to memory at the store and leaves the XCD's
+//      L2, so the launch leaves nothing dirty behind for its boundary to write back.  No launch of a stack finds its input
+//      in L2 anyway (profiles/xcd_pmc.tsv), so dropping the line costs the next launch nothing.  Visibility is unchanged: the
+//      kernel boundary still releases.  hipcc does not count an asm store (nothing reads it back in the kernel, and a wave's
+//      stores complete after it ends), and the trailing s_nop 1 keeps the data registers from being rewritten before the
+//      store has read them.
+// Modes 2 and 4 of the C ABI (whole rows through LDS, plain and written through) are not built.
+template <int ST>
+__device__ __forceinline__ void store_out(float *p, float4_t v) {
+  static_assert(ST == 1 || ST == 3, "store modes: 1 plain, 3 written through");
+  if constexpr (ST == 3)
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+  else
+    *reinterpret_cast<float4_t *>(p) = v;
+}
+
 }  // namespace gwen

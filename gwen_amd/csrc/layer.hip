@@ -42,6 +42,13 @@
 // Contraction (exact = 1): v_mfma_f32_16x16x4_f32 on an fp32 tile (k-permutation k = 8q+2(lane>>4)+s,
 //   row pitch Fin+4 floats => conflict-free 8-B reads): bit-exact fp32 fmaf chains.
 // Blocks are remapped so that the blocks sharing an XCD (blockIdx % 8) own neighbouring rows.
+// Stores (template argument ST, gather_rows.h store_out): the D tile leaves as one 16-byte store per lane, 16 rows x 64 B
+//   per wave instruction.  ST = 1: plain stores.  ST = 3: the same instruction with the sc1 bit -- written through: the
+//   line goes to memory at the store and leaves the XCD's L2, so the launch leaves no dirty output for its boundary to
+//   write back (the next launch reads its input from beyond L2 either way).  Values, addresses, registers and LDS are
+//   those of ST = 1.  Which shapes run 3: layer_store_mode (measured per kernel in the step, profiles/store_*).  Whole
+//   rows through an LDS out tile (modes 2 / 4 of the C ABI) are not built; the lab that prices them is
+//   tools/experiments/store_lab.patch.
 #include "common.h"
 #include "dispatch.h"
 #include "gather_rows.h"
@@ -104,8 +111,10 @@ constexpr bool layer_prologue(int fin, int fout, int ns) { return !(fin == 16 &&
 // PK: packed W (packw.hip; narrow forward kernels on a bf16 split only): `W` points to the weight's bf16 images in fragment
 // order, cut once per weight version, and this wave's B fragments are plain 16-byte loads at the top of the kernel -- no
 // raw fp32 W, no split.  false compiles to the code the kernel had.
+// ST: store mode of the epilogue (gather_rows.h, store_out): 1 = plain 16-byte stores, the code the kernel had; 3 = the same
+// addresses written through (sc1).  Narrow forward kernels on the uniform layout and a bf16 split only.
 template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1, int IM = 1,
-          bool PK = false>
+          bool PK = false, int ST = 1>
 __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void k_layer(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W,
@@ -115,6 +124,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
   static_assert(IM == 1 || (IM == 2 && UNI && !BWD && FIN <= 64 && FOUT <= 64), "index records: narrow forward, uniform layout");
   static_assert(!PK || (NS > 0 && !BWD && FIN <= 64 && FOUT <= 64), "packed W: narrow forward on a bf16 split");
+  static_assert(ST == 1 || (ST == 3 && UNI && NS > 0 && !BWD && FIN <= 64 && FOUT <= 64), "store modes: narrow forward, uniform layout");
   constexpr bool SPLIT = NS > 0;
   constexpr int NI = SPLIT ? NS : 1;
   __shared__ __attribute__((aligned(16))) char lds_raw[C::lds_bytes];
@@ -288,7 +298,7 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
         for (int t = 0; t < 4; ++t) o[t] = y[t] > 0.0f ? o[t] : 0.0f;
       }
     }
-    if (r < N) *reinterpret_cast<float4_t *>(om + (int64_t)r * ldo + j * 16 + 4 * mh) = o;
+    if (r < N) gwen::store_out<ST>(om + (int64_t)r * ldo + j * 16 + 4 * mh, o);
     if constexpr (BWD && !kPersist) {
       if (bsum_out && r < N) cs = cs + o;
     }
@@ -360,13 +370,13 @@ constexpr bool rows_ok(int fin, int fout, int br, bool pk = false) {
 // call makes no HIP query, so the launchers stay capturable.  The UNIFORM kernel is probed whichever layout is launched:
 // the block-rows choice of launch() on a non-uniform layout has always been made with the uniform kernel's occupancy.
 // The index mode is part of the instantiation: a record kernel holds fewer registers.
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK, int ST = 1>
 int resident_blocks(int64_t &resident) {
   static int per_cu = 0;
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK>),
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK, ST>),
         Cfg<FIN, FOUT, NS, BRMIN>::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
@@ -374,11 +384,11 @@ int resident_blocks(int64_t &resident) {
   return GWEN_OK;
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK, int ST = 1>
 int launch_rows(const LayerArgs &a) {
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
   int64_t resident = 0;
-  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM, PK>(resident); if (rc != GWEN_OK) return rc; }
+  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM, PK, ST>(resident); if (rc != GWEN_OK) return rc; }
   if (a.probe) { *a.probe = (int)(resident / 256); return GWEN_OK; }
   int64_t blocks = (a.N + C::BR - 1) / C::BR;
   const int64_t chunks_pm = blocks;                        // chunks of BR rows per member (bsum_out: one partial row each)
@@ -392,7 +402,10 @@ int launch_rows(const LayerArgs &a) {
     GWEN_LAUNCH_CHECK();
     return (int)GWEN_OK;
   };
-  if constexpr (IM == 2) {                     // index records: the forward on the uniform layout, nothing else
+  if constexpr (ST != 1) {                     // store modes: the forward on the uniform layout, nothing else
+    if (a.bwd || a.rowptr) return GWEN_EINVAL;
+    return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK, ST>);
+  } else if constexpr (IM == 2) {              // index records: the forward on the uniform layout, nothing else
     if (a.bwd || a.rowptr) return GWEN_EINVAL;
     return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, 2, PK>);
   }
@@ -408,7 +421,7 @@ int launch_rows(const LayerArgs &a) {
 }
 
 // block_rows: 0 = the choice below; else forced (rows_ok, checked by the extern "C" caller)
-template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1, bool PK = false>
+template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1, bool PK = false, int ST = 1>
 int launch(const LayerArgs &a, int block_rows) {
   static_assert(GE == 8 || narrow(FIN, FOUT), "7 gathered entries: narrow layers only");
   static_assert(IM == 1 || narrow(FIN, FOUT), "index records: narrow layers only");
@@ -435,7 +448,7 @@ int launch(const LayerArgs &a, int block_rows) {
     int rc = GWEN_OK, br = block_rows;
     auto fits = [&](int c, int64_t work) {                 // the grid of c-row blocks is co-resident (or rc says why not)
       int64_t res = 0;
-      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK>(res); });
+      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK, ST>(res); });
       return rc != GWEN_OK || (work + c - 1) / c <= res;
     };
     if (br == 0) {
@@ -449,7 +462,7 @@ int launch(const LayerArgs &a, int block_rows) {
       }
       if (rc != GWEN_OK) return rc;
     }
-    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK>(a); });
+    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK, ST>(a); });
   }
 }
 
@@ -511,6 +524,21 @@ extern "C" int gwen_gcn_layer_packed_mode(int64_t Fin, int64_t Fout, int exact) 
   return layer_packed(Fin, Fout, gwen::images_of(exact)) ? 2 : 1;
 }
 
+// The library's store mode per (Fin, Fout, images) on the uniform layout (gather_rows.h, store_out): 3, the epilogue's
+// 16-byte stores written through, only where the kernel measured faster on the MI355X by the rule of the depth and index
+// tables ("Stores"; profiles/store_*).  The modes exist for the narrow forward kernels on a bf16 split, on the
+// uniform layout, at the shape's own depth and index mode; everything else has mode 1 only.
+// The three K4 launches of the c2 step on bf16x6, the only split that was measured (profiles/store_kernel_ab.tsv).
+static constexpr int layer_store_mode(int64_t fin, int64_t fout, int ns) {
+  return ns == 3 && ((fin == 64 && fout == 64) || (fin == 32 && fout == 64) || (fin == 16 && fout == 32)) ? 3 : 1;
+}
+
+extern "C" int gwen_gcn_layer_store_mode(int64_t Fin, int64_t Fout, int exact) {
+  if (!gwen_gcn_layer_supported(Fin, Fout) || exact < 0 || exact > 2) return 0;
+  if (!narrow(Fin, Fout) || gwen::images_of(exact) == 0) return 1;
+  return layer_store_mode(Fin, Fout, gwen::images_of(exact));
+}
+
 // entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
 // kernels turn into one gather less per row; every other shape and layout gathers whole groups.
 // depth, block_rows, index_mode: 0 = the library's choice (layer_depth; the co-resident grid of launch();
@@ -519,6 +547,9 @@ extern "C" int gwen_gcn_layer_packed_mode(int64_t Fin, int64_t Fout, int exact) 
 // Wp, packed: the gwen_gcn_packw_f32 images of W and whether they are read.  1: W is read and split in the kernel; 2: the
 // images are read (W may be NULL) -- narrow layers on a bf16 split only, GWEN_EINVAL elsewhere or without images;
 // 0: the library's choice -- the images where they are given and gwen_gcn_layer_packed_mode says 2.  No value changes.
+// store_mode: 0 = the library's choice (layer_store_mode, one member only); 1 = plain stores; 3 = the same stores written
+// through -- narrow layers on a bf16 split, on the uniform layout, at the library's depth and index mode for the shape,
+// GWEN_EINVAL elsewhere; 2 and 4 (whole-row stores through LDS) are not built: GWEN_EINVAL.  No value changes.
 // probe: not NULL = launch nothing and store the blocks per CU that hipOccupancyMaxActiveBlocksPerMultiprocessor reports for
 // the kernel this call would launch (the uniform-layout kernel, as resident_blocks has always asked)
 static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -526,14 +557,21 @@ static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *v
                        int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
                        int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
                        int exact, int entries, int depth, int block_rows, int index_mode,
-                       const void *Wp, int packed, gwen_stream_t stream_, int *probe) {
+                       const void *Wp, int packed, int store_mode, gwen_stream_t stream_, int *probe) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
+  if (store_mode < 0 || store_mode > 4) return GWEN_EINVAL;
   if (packed < 0 || packed > 2) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
   if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
   if (index_mode == 2 && (rowptr || !narrow(Fin, Fout))) return GWEN_EINVAL;    // records: uniform layout, narrow layers
+  // store modes: narrow layers on a bf16 split, uniform layout, the shape's own depth and index mode; row stores: not built
+  const bool can_store = narrow(Fin, Fout) && gwen::images_of(exact) > 0 && !rowptr &&
+                         (depth == 0 || depth == gwen_gcn_layer_depth(Fin, Fout, exact)) &&
+                         (index_mode == 0 || index_mode == gwen_gcn_layer_index_mode(Fin, Fout, exact));
+  if (store_mode > 1 && (!can_store || store_mode != 3)) return GWEN_EINVAL;
+  if (store_mode == 0) store_mode = can_store && members == 1 ? gwen_gcn_layer_store_mode(Fin, Fout, exact) : 1;
   const bool can_pack = narrow(Fin, Fout) && gwen::images_of(exact) > 0;        // packed W: narrow layers, bf16 splits
   if (packed == 2 && (!can_pack || !Wp)) return GWEN_EINVAL;
   if (packed == 0) packed = Wp && can_pack && gwen_gcn_layer_packed_mode(Fin, Fout, exact) == 2 ? 2 : 1;
@@ -560,10 +598,16 @@ static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *v
           return gwen::dispatch(gwen::ints<1, 2>{}, index_mode, [&](auto iv) {
             return gwen::dispatch(gwen::ints<1, 2>{}, packed, [&](auto pv) {
               constexpr bool PK = decltype(pv)::value == 2;
-              if constexpr (!PK || NS > 0)
-                return launch<FI, FO, NS, decltype(gev)::value, decltype(dv)::value, decltype(iv)::value, PK>(a, block_rows);
-              else
+              constexpr int GE = decltype(gev)::value, D = decltype(dv)::value, IM = decltype(iv)::value;
+              if constexpr (!PK || NS > 0) {
+                // the written-through kernels: at the depth and index mode the library launches for the shape
+                if constexpr (NS > 0 && D == layer_depth(FI, FO, NS) && IM == layer_index_mode(FI, FO, NS)) {
+                  if (store_mode == 3) return launch<FI, FO, NS, GE, D, IM, PK, 3>(a, block_rows);
+                }
+                return store_mode == 1 ? launch<FI, FO, NS, GE, D, IM, PK>(a, block_rows) : (int)GWEN_EINVAL;
+              } else {
                 return (int)GWEN_EINVAL;
+              }
             });
           });
         });
@@ -574,14 +618,24 @@ static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *v
   });
 }
 
+extern "C" int gwen_gcn_layer_tuned4_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W, const float *bias, float *out,
+                                         int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                         int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                         int exact, int entries, int depth, int block_rows, int index_mode,
+                                         const void *Wp, int packed, gwen_stream_t stream_, int store_mode) {
+  return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
+                     entries, depth, block_rows, index_mode, Wp, packed, store_mode, stream_, nullptr);
+}
+
 extern "C" int gwen_gcn_layer_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val,
                                          const float *x, const float *W, const float *bias, float *out,
                                          int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
                                          int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
                                          int exact, int entries, int depth, int block_rows, int index_mode,
                                          const void *Wp, int packed, gwen_stream_t stream_) {
-  return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
-                     entries, depth, block_rows, index_mode, Wp, packed, stream_, nullptr);
+  return gwen_gcn_layer_tuned4_f32(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o,
+                                   relu, exact, entries, depth, block_rows, index_mode, Wp, packed, stream_, 0);
 }
 
 extern "C" int gwen_gcn_layer_blocks_per_cu(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -592,7 +646,7 @@ extern "C" int gwen_gcn_layer_blocks_per_cu(const int32_t *rowptr, const int32_t
                                             const void *Wp, int packed, int *blocks_per_cu) {
   if (!blocks_per_cu || N <= 0 || members <= 0) return GWEN_EINVAL;
   return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
-                     entries, depth, block_rows, index_mode, Wp, packed, nullptr, blocks_per_cu);
+                     entries, depth, block_rows, index_mode, Wp, packed, 0, nullptr, blocks_per_cu);
 }
 
 extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,

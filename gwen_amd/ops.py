@@ -189,13 +189,14 @@ def layer_supported(fin: int, fout: int) -> bool:
 
 def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
                 relu: bool = False, exact: bool = False, contract: Optional[str] = None,
-                depth: int = 0, block_rows: int = 0, index_mode: int = 0) -> Tensor:
+                depth: int = 0, block_rows: int = 0, index_mode: int = 0, store_mode: int = 0) -> Tensor:
     """K4: act((A~ x) W^T + b) in one launch (widths in {16,32,64,128,256}).  ``contract``: "bf16x6", "3xbf16" or
     "fp32"; when None, ``exact`` picks between "fp32" (True) and "3xbf16" (False).  ``depth`` (gather passes in
     flight per wave: 1 or 2) and ``block_rows`` (64 / 96 / 112 / 128 where the widths allow) are scheduling choices
     that change no value; 0 = the library's.  So is ``index_mode`` (1: every lane loads its row's indices and weights;
     2: one record load per row, broadcast in the lane group -- widths up to 64 on a uniform layout only)
-    (gwen_gcn_layer_tuned2_f32)."""
+    and ``store_mode`` (1: plain output stores; 3: the same stores written through -- widths up to 64 on a bf16 split and a
+    uniform layout only; 2 and 4 are reserved) (gwen_gcn_layer_tuned4_f32)."""
     _require(x, "x")
     _require(weight, "weight")
     x = x.contiguous()
@@ -214,11 +215,12 @@ def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tenso
     dev = x.device
     g_rowptr, g_col, g_val = graph.grouped()
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_layer_tuned2_f32(
+        rc = _lib.lib().gwen_gcn_layer_tuned4_f32(
             _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), _ptr(weight), _ptr(bias),
             _ptr(out), n, fin, fout, fin, fout, m, n_src * fin, n * fout, int(relu),
-            _dense_code(contract, exact), graph.entries(), int(depth), int(block_rows), int(index_mode), _stream(dev))
-    _lib.check(rc, "gwen_gcn_layer_tuned2_f32")
+            _dense_code(contract, exact), graph.entries(), int(depth), int(block_rows), int(index_mode), None, 0,
+            _stream(dev), int(store_mode))
+    _lib.check(rc, "gwen_gcn_layer_tuned4_f32")
     return out
 
 
@@ -308,10 +310,11 @@ def small_layer(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tenso
 
 def chain(graph: GraphCSR, x: Tensor, w1: Optional[Tensor], w2: Optional[Tensor], bias: Optional[Tensor],
           relu: bool, pre: bool, contract: str = "3xbf16", depth: int = 0, block_rows: int = 0,
-          index_mode: int = 0) -> Tensor:
+          index_mode: int = 0, store_mode: int = 0) -> Tensor:
     """K5.  pre=False: act((A~ x) w1^T + bias) w2^T;  pre=True: act(A~ x + bias) w1^T  (inference only); pre=True
     with w1 = None: act(A~ x + bias), the propagation on the grouped layout.  ``contract``: "3xbf16" or "bf16x6".
-    ``depth`` / ``block_rows`` / ``index_mode``: as ``layer_fused`` (gwen_gcn_chain_tuned2_f32); they change no value."""
+    ``depth`` / ``block_rows`` / ``index_mode`` / ``store_mode``: as ``layer_fused`` (gwen_gcn_chain_tuned4_f32); they change
+    no value."""
     _require(x, "x")
     x = x.contiguous()
     m, n, fin = _rows2d(x)
@@ -322,12 +325,12 @@ def chain(graph: GraphCSR, x: Tensor, w1: Optional[Tensor], w2: Optional[Tensor]
     g_rowptr, g_col, g_val = graph.grouped()
     dev = x.device
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_chain_tuned2_f32(
+        rc = _lib.lib().gwen_gcn_chain_tuned4_f32(
             _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), None if w1 is None else _ptr(w1.contiguous()),
             None if w2 is None else _ptr(w2.contiguous()), None if bias is None else _ptr(bias.contiguous()),
             _ptr(out), n, fin, f1, f2, int(pre), int(relu), m, n * fin, n * fw, _dense_code(contract),
-            graph.entries(), int(depth), int(block_rows), int(index_mode), _stream(dev))
-    _lib.check(rc, "gwen_gcn_chain_tuned2_f32")
+            graph.entries(), int(depth), int(block_rows), int(index_mode), None, None, 0, _stream(dev), int(store_mode))
+    _lib.check(rc, "gwen_gcn_chain_tuned4_f32")
     return out
 
 

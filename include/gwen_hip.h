@@ -290,6 +290,22 @@ int gwen_gcn_layer_blocks_per_cu(const int32_t *rowptr, const int32_t *col, cons
                                  int index_mode, const void *Wp, int packed, int *blocks_per_cu);
 /* what packed = 0 does with an image: 1 = W is split in the kernel, 2 = the image is read (0: unsupported widths / exact) */
 int gwen_gcn_layer_packed_mode(int64_t Fin, int64_t Fout, int exact);
+/* gwen_gcn_layer_tuned3_f32 with the store mode of the epilogue: a fifth choice that CHANGES NO VALUE;
+ * gwen_gcn_layer_tuned3_f32 forwards with 0.
+ * store_mode: 1 = plain 16-byte stores of the MFMA result fragments; 3 = the same stores WRITTEN THROUGH (the line goes to
+ *   memory at the store and leaves the L2, so the launch leaves no dirty lines behind) -- Fin, Fout <= 64 on
+ *   GWEN_CONTRACT_BF16X3 / _BF16X6, uniform layout (rowptr NULL), depth and index_mode 0 or the library's for the shape;
+ *   elsewhere GWEN_EINVAL.  2 and 4 (whole rows through LDS, plain and written through) are reserved and not built:
+ *   GWEN_EINVAL.  0 = the library's choice (gwen_gcn_layer_store_mode, with one member; 1 otherwise).  Outside 0..4:
+ *   GWEN_EINVAL.  All of these are refused before any HIP call. */
+int gwen_gcn_layer_tuned4_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                              int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                              int64_t mstride_o, int relu, int exact, int entries, int depth, int block_rows,
+                              int index_mode, const void *Wp, int packed, gwen_stream_t stream, int store_mode);
+/* what store_mode = 0 runs on a uniform layout with one member: 1 .. 4, and 1 wherever the modes do not exist
+ * (0: unsupported widths / exact) */
+int gwen_gcn_layer_store_mode(int64_t Fin, int64_t Fout, int exact);
 
 /* ---------------------------------------------------------------------------------------------
  * K8  K4's contract for WIDE layers on locality-ordered bounded-degree graphs (meshes), tile-staged:
@@ -404,6 +420,16 @@ int gwen_gcn_chain_blocks_per_cu(const int32_t *rowptr, const int32_t *col, cons
                                  int *blocks_per_cu);
 /* what packed = 0 does with images: 1 or 2 as gwen_gcn_layer_packed_mode (0: gwen_gcn_chain_supported says no) */
 int gwen_gcn_chain_packed_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
+/* store_mode: as gwen_gcn_layer_tuned4_f32 -- no value changes; gwen_gcn_chain_tuned3_f32 forwards with 0.  3 needs Fin,
+ * F1 <= 64 (F1 = 0, the plain gather, included), the uniform layout, and depth and index_mode 0 or the library's. */
+int gwen_gcn_chain_tuned4_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W1, const float *W2, const float *bias, float *out, int64_t N,
+                              int64_t Fin, int64_t F1, int64_t F2, int pre, int relu, int64_t members,
+                              int64_t mstride_x, int64_t mstride_o, int contract, int entries, int depth,
+                              int block_rows, int index_mode, const void *W1p, const void *W2p, int packed,
+                              gwen_stream_t stream, int store_mode);
+/* what store_mode = 0 runs on a uniform layout with one member: 1 .. 4 (0: gwen_gcn_chain_supported says no) */
+int gwen_gcn_chain_store_mode(int64_t Fin, int64_t F1, int64_t F2, int pre, int contract);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-stack forward == GNNModel.forward (/root/reference/src/gwen/models_gnn.py:292-303 ->

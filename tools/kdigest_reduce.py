@@ -9,7 +9,12 @@ Per object: the number of kernels and the SHA-256 of its sorted listing lines '<
 the digest is taken over the kernels whose packed-W flag is off (k_layer: last template argument; k_chain: the one before
 the images), their names written without that argument -- so equal digests say that every kernel of the parent is in the
 change byte for byte, and the script fails when they are not.  Then the listing lines of the kernels whose names match one
-of the regular expressions, both trees."""
+of the regular expressions, both trees.
+
+    tools/kdigest_reduce.py --store parent.tsv change.tsv [regex ...] > profiles/store_kernel_digests.tsv
+
+The same for the store mode (k_layer, k_gather: last template argument; k_chain: the one before the images): "off" is
+ST = 1, whose kernels must be the parent's byte for byte; the column headers keep their names."""
 import hashlib
 import re
 import sys
@@ -26,7 +31,16 @@ def load(path):
     return out
 
 
+STORE = False                          # --store: the flag is the store mode, off = 1
+
+
 def flag_off_name(name):
+    if STORE:
+        m = re.match(r"(k_layer<.*|k_gather<.*), 1>$", name)
+        if m:
+            return m.group(1) + ">"
+        m = re.match(r"(k_chain<.*), 1, (\d+)>$", name)
+        return m.group(1) + ", " + m.group(2) + ">" if m else name
     m = re.match(r"(k_layer<.*), false>$", name)
     if m:
         return m.group(1) + ">"
@@ -35,6 +49,8 @@ def flag_off_name(name):
 
 
 def packed(name):
+    if STORE:
+        return bool(re.search(r"(k_layer<.*|k_gather<.*), [2-4]>$|k_chain<.*, [2-4], \d+>$", name))
     return bool(re.search(r"k_layer<.*, true>$|k_chain<.*, true, \d+>$", name))
 
 
@@ -58,6 +74,9 @@ def main(parent_path, change_path, patterns):
 
 
 if __name__ == "__main__":
+    if "--store" in sys.argv:
+        STORE = True
+        sys.argv.remove("--store")
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     main(sys.argv[1], sys.argv[2], sys.argv[3:])
