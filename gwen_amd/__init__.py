@@ -27,6 +27,7 @@ from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
 from .models_gnn import (DownConvLayers, GCNConvLayers, GNNConfig, GNNModel, UpConvLayers,
                          loss_func)
+from .models_cnn import BaseNet, Decoder, Encoder, UNet
 
 __all__ = [
     "GCNConv", "Linear", "GraphedForward", "KernelEvents", "StackForward", "event_bracket_overhead", "GraphCSR", "GraphCache", "default_cache", "prepare_graph", "Mesh",
@@ -37,5 +38,6 @@ __all__ = [
     "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
     "Regridder", "nearest_neighbours", "mesh_cells", "mesh_dual_cells", "latlon_cells", "cell_areas", "cell_overlaps", "checkpointed_step", "CRPSLoss", "EnsembleVarRegLoss", "MaskedLoss",
     "SphericalHarmonics", "SFNO", "SFNOBlock", "SpectralConv", "spectral_conv", "spectral_conv_supported",
+    "BaseNet", "Encoder", "Decoder", "UNet",
 ]
 __version__ = "0.1.0"

@@ -104,6 +104,7 @@ CONSERVE_COVERED, CONSERVE_CELL = 0, 1               # GWEN_CONSERVE_*
 SHT_GRIDS = {"equiangular": 0, "equiangular-centred": 1, "gauss": 2}     # GWEN_SHT_* (include/gwen_hip.h)
 SHT_OP_ANALYSIS, SHT_OP_SYNTHESIS, SHT_OP_VECTOR_ANALYSIS, SHT_OP_VECTOR_SYNTHESIS = 0, 1, 2, 3     # GWEN_SHT_OP_*
 SHT_LONGITUDE = {"direct": 0, "fft": 1}                                   # GWEN_SHT_LON_*
+CONV_AFFINE, CONV_RELU, CONV_POOL = 1, 2, 4                               # GWEN_CONV_*
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
 
@@ -303,6 +304,15 @@ SIGNATURES = {
     "gwen_spectral_conv_supported": (_int, [_i64, _i64, _int]),
     "gwen_spectral_conv_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "gwen_spectral_conv_grad_weight_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),
+    "gwen_conv3x3_pack_bytes": (_i64, [_i64, _i64, _int]),
+    "gwen_conv3x3_pack_f32": (_int, [_vp, _i64, _i64, _int, _int, _vp, _vp]),
+    "gwen_conv3x3_plan": (_int, [_i64] * 4 + [_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gwen_conv3x3_workspace_floats": (_i64, [_i64] * 5 + [_int]),
+    "gwen_conv3x3_f32": (_int, [_vp] * 6 + [_i64] * 7 + [_int, _int, _vp, _i64, _vp]),
+    "gwen_upsample2x_f32": (_int, [_vp] * 4 + [_i64] * 6 + [_int, _vp]),
+    "gwen_channel_stats_workspace_bytes": (_i64, [_i64, _i64]),
+    "gwen_channel_stats_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "gwen_affine_relu_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
 }
 
 

@@ -7,13 +7,14 @@ from __future__ import annotations
 
 import ctypes
 import math
+import weakref
 from typing import Optional
 
 import torch
 from torch import Tensor
 
 from . import _lib
-from .graph import GraphCSR, _ptr, _stream
+from .graph import GraphCSR, _ptr, _stream, _version_of
 
 
 def _require(t: Tensor, name: str) -> None:
@@ -662,3 +663,162 @@ def gcn_layer(x: Tensor, weight: Tensor, bias: Optional[Tensor], graph: GraphCSR
     if x.device != weight.device or x.device != graph.device:
         raise RuntimeError("x, weight and the graph must be on the same device")
     return GCNLayerFunction.apply(x, weight, bias, graph, relu, order, packed)
+
+
+# ---- U-Net kernels (csrc/conv.hip): channels-last activations [B, H, W, C], a channel slice of a wider buffer allowed ----
+
+def _nhwc(t: Tensor, name: str):
+    """(B, H, W, C, row pitch) of a channels-last activation: dense over B, H, W with the channels contiguous inside
+    rows of ``pitch >= C`` elements -- a contiguous tensor or a slice ``buf[..., c0:c1]`` of one."""
+    _require(t, name)
+    if t.dim() != 4:
+        raise ValueError(f"{name} must be channels-last [B, H, W, C], got {tuple(t.shape)}")
+    b, h, w, c = t.shape
+    if t.numel() == 0:
+        return b, h, w, c, max(c, 1)
+    ld = t.stride(2) if w > 1 else (t.stride(1) if h > 1 else (t.stride(0) if b > 1 else c))
+    ok = (c == 1 or t.stride(3) == 1) and ld >= c and (w == 1 or t.stride(2) == ld) \
+        and (h == 1 or t.stride(1) == w * ld) and (b == 1 or t.stride(0) == h * w * ld)
+    if not ok:
+        raise ValueError(f"{name} must be channels-last rows with one pitch (a contiguous tensor or a channel slice of "
+                         f"one); got shape {tuple(t.shape)}, strides {t.stride()}")
+    return b, h, w, c, ld
+
+
+def _affine_pair(affine, c: int, dev):
+    if affine is None:
+        return None, None
+    s, t = affine
+    for name, v in (("affine scale", s), ("affine shift", t)):
+        _require(v, name)
+        if tuple(v.shape) != (c,) or v.device != dev:
+            raise ValueError(f"{name} must be [{c}] on {dev}")
+    return s.contiguous(), t.contiguous()
+
+
+_CONV_PACKED: dict = {}   # id(weight) -> (weak reference, {(contract, transposed): (key, image)}); repacked when the version moves
+
+
+def conv3x3_pack(weight: Tensor, transposed: bool = False, contract: Optional[str] = None) -> Tensor:
+    """The packed image of a 3x3 weight (gwen_conv3x3_pack_f32), cached per weight ``_version`` as the K4 / K5 packed W
+    is: ``weight`` [Cout, Cin, 3, 3] (Conv2d) or, ``transposed``, [Cin, Cout, 3, 3] (ConvTranspose2d)."""
+    _require(weight, "weight")
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise ValueError(f"weight must be [., ., 3, 3], got {tuple(weight.shape)}")
+    code = _dense_code(contract or "bf16x6")
+    cout, cin = (weight.size(1), weight.size(0)) if transposed else (weight.size(0), weight.size(1))
+    ver = _version_of(weight)
+    key = (weight.data_ptr(), ver, tuple(weight.shape), weight.device)
+    ident, slot = id(weight), (code, bool(transposed))
+    entry = _CONV_PACKED.get(ident)
+    if entry is not None and entry[0]() is not weight:           # the id of a weight that went away, reused
+        entry = None
+    hit = None if entry is None else entry[1].get(slot)
+    if ver is not None and hit is not None and hit[0] == key:
+        return hit[1]
+    nbytes = int(_lib.lib().gwen_conv3x3_pack_bytes(cin, cout, code))
+    if nbytes == 0:
+        raise ValueError(f"conv3x3: channels must be in [1, 2048] and the contract a split one; got Cin {cin}, Cout "
+                         f"{cout}, contract {contract!r}")
+    w = weight.detach().contiguous()
+    img = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=weight.device)
+    with torch.cuda.device(weight.device):
+        rc = _lib.lib().gwen_conv3x3_pack_f32(_ptr(w), cin, cout, int(transposed), code, _ptr(img), _stream(weight.device))
+    _lib.check(rc, "gwen_conv3x3_pack_f32")
+    # the entry lives as long as the weight object does (an id may be reused afterwards: the weak reference tells);
+    # one image per (contraction, layout) of it, so two tiers on one weight do not repack each other
+    if entry is None:
+        entry = (weakref.ref(weight, lambda _r, i=ident: _CONV_PACKED.pop(i, None)), {})
+        _CONV_PACKED[ident] = entry
+    entry[1][slot] = (key, img)
+    return img
+
+
+def conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, transposed: bool = False, pool: bool = False,
+            affine=None, relu: bool = False, contract: Optional[str] = None, out: Optional[Tensor] = None) -> Tensor:
+    """3x3 / stride 1 / padding 1 convolution of channels-last ``x`` [B, H, W, Cin] (gwen_conv3x3_f32): conv + bias, then
+    ``pool`` (2x2 / stride 2 max, floor rule), then ``affine`` = (scale, shift) per output channel, then ReLU, in one
+    launch.  ``transposed``: ``weight`` is a ConvTranspose2d's [Cin, Cout, 3, 3].  ``contract``: "bf16x6" (default,
+    fp32-class; "f16x3" means it too) or "3xbf16".  ``out``: where to write, [B, Ho, Wo, Cout], a channel slice allowed."""
+    b, h, w, cin, ldx = _nhwc(x, "x")
+    img = conv3x3_pack(weight, transposed, contract)
+    cout, wcin = (weight.size(1), weight.size(0)) if transposed else (weight.size(0), weight.size(1))
+    if wcin != cin:
+        raise ValueError(f"x has {cin} channels but weight expects {wcin}")
+    dev = x.device
+    if weight.device != dev:
+        raise RuntimeError("x and weight must be on the same device")
+    if bias is not None:
+        _require(bias, "bias")
+        if tuple(bias.shape) != (cout,):
+            raise ValueError(f"bias must be [{cout}]")
+        bias = bias.detach().contiguous()
+    s, t = _affine_pair(affine, cout, dev)
+    ho, wo = (h // 2, w // 2) if pool else (h, w)
+    if out is None:
+        out = torch.empty(b, ho, wo, cout, dtype=torch.float32, device=dev)
+    ob, oh, ow, oc, ldo = _nhwc(out, "out")
+    if (ob, oh, ow, oc) != (b, ho, wo, cout) or out.device != dev:
+        raise ValueError(f"out must be [{b}, {ho}, {wo}, {cout}] on {dev}, got {tuple(out.shape)}")
+    flags = (_lib.CONV_AFFINE if affine is not None else 0) | (_lib.CONV_RELU if relu else 0) | (_lib.CONV_POOL if pool else 0)
+    # the slices' raw sums (low resolutions); -1: they would reach 4 GiB, and the launcher answers GWEN_ERANGE
+    nws = max(int(_lib.lib().gwen_conv3x3_workspace_floats(b, h, w, cin, cout, flags)), 0)
+    ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws > 0 else None
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_conv3x3_f32(_ptr(x), _ptr(img), _ptr(bias), _ptr(s), _ptr(t), _ptr(out), b, h, w, cin, cout,
+                                         ldx, ldo, flags, _dense_code(contract or "bf16x6"), _ptr(ws), nws, _stream(dev))
+    _lib.check(rc, "gwen_conv3x3_f32")
+    return out
+
+
+def upsample2x(x: Tensor, affine=None, relu: bool = False, out: Optional[Tensor] = None) -> Tensor:
+    """Bilinear x2 with align_corners=True of channels-last ``x`` [B, H, W, C] (gwen_upsample2x_f32), then ``affine`` =
+    (scale, shift) per channel, then ReLU.  ``out``: [B, 2H, 2W, C], a channel slice of a wider buffer allowed."""
+    b, h, w, c, ldx = _nhwc(x, "x")
+    dev = x.device
+    s, t = _affine_pair(affine, c, dev)
+    if out is None:
+        out = torch.empty(b, 2 * h, 2 * w, c, dtype=torch.float32, device=dev)
+    ob, oh, ow, oc, ldo = _nhwc(out, "out")
+    if (ob, oh, ow, oc) != (b, 2 * h, 2 * w, c) or out.device != dev:
+        raise ValueError(f"out must be [{b}, {2 * h}, {2 * w}, {c}] on {dev}, got {tuple(out.shape)}")
+    flags = (_lib.CONV_AFFINE if affine is not None else 0) | (_lib.CONV_RELU if relu else 0)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_upsample2x_f32(_ptr(x), _ptr(s), _ptr(t), _ptr(out), b, h, w, c, ldx, ldo, flags, _stream(dev))
+    _lib.check(rc, "gwen_upsample2x_f32")
+    return out
+
+
+def channel_stats(x: Tensor):
+    """(mean, biased variance) per channel over every row of channels-last ``x`` [..., C] (a channel slice allowed), as
+    fp64 tensors [C] (gwen_channel_stats_f64: fp64 sums in a fixed order) -- train-mode BatchNorm's statistics."""
+    if x.dim() != 4:
+        _require(x, "x")
+        if x.dim() != 2 or (x.size(1) > 1 and x.stride(1) != 1) or x.stride(0) < x.size(1):
+            raise ValueError(f"channel_stats needs [rows, C] rows or channels-last [B, H, W, C]; got {tuple(x.shape)}")
+        rows, c, ld = x.size(0), x.size(1), (x.stride(0) if x.size(0) > 1 else x.size(1))
+    else:
+        b, h, w, c, ld = _nhwc(x, "x")
+        rows = b * h * w
+    dev = x.device
+    nbytes = int(_lib.lib().gwen_channel_stats_workspace_bytes(rows, c))
+    if nbytes == 0:
+        raise ValueError(f"channel_stats needs at least one row and 1 <= C <= 2048; got rows {rows}, C {c}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    stats = torch.empty(2, c, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_channel_stats_f64(_ptr(x), rows, c, ld, _ptr(stats[0]), _ptr(stats[1]), _ptr(ws), nbytes,
+                                               _stream(dev))
+    _lib.check(rc, "gwen_channel_stats_f64")
+    return stats[0], stats[1]
+
+
+def affine_relu_(x: Tensor, scale: Tensor, shift: Tensor) -> Tensor:
+    """x <- max(0, x * scale[c] + shift[c]) in place on channels-last ``x`` [B, H, W, C] (a channel slice allowed):
+    gwen_affine_relu_f32, the finish of train-mode BatchNorm + ReLU."""
+    b, h, w, c, ld = _nhwc(x, "x")
+    s, t = _affine_pair((scale, shift), c, x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().gwen_affine_relu_f32(_ptr(x), _ptr(s), _ptr(t), b * h * w, c, ld, _stream(x.device))
+    _lib.check(rc, "gwen_affine_relu_f32")
+    return x

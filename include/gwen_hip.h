@@ -1335,6 +1335,64 @@ int gwen_spectral_conv_f32(const float *coef, const float *W, float *out, int64_
 int gwen_spectral_conv_grad_weight_f32(const float *coef, const float *g, float *grad_W, int64_t batch, int64_t lmax,
                                        int64_t Cin, int64_t Cout, int contract, gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * U-Net kernels (csrc/conv.hip, gwen_amd.models_cnn).  Activations are channels-last fp32: [B, H, W, C] is a row matrix
+ * [B H W, C] with a row pitch ld >= C (in elements), so a kernel reads or writes a channel slice of a wider buffer.
+ *
+ *   gwen_conv3x3_pack_f32: W -> the bf16 fragment images gwen_conv3x3_f32 reads, gwen_conv3x3_pack_bytes(Cin, Cout,
+ *         contract) bytes (0 for unsupported arguments), 16-byte aligned: [Cin chunk of 32][tap ky 3 + kx][tile of 16
+ *         output channels][image][lane][8], channels beyond Cin / Cout as zeros.  transposed = 0: Conv2d weights
+ *         [Cout, Cin, 3, 3]; transposed = 1: ConvTranspose2d weights [Cin, Cout, 3, 3], which at stride 1 and
+ *         padding 1 is the convolution with Wc[co][ci][ky][kx] = Wt[ci][co][2 - ky][2 - kx].  One launch, on the device.
+ *   gwen_conv3x3_f32: out[b, y, x, co] = sum_{ky, kx, ci} Wc[co][ci][ky][kx] x[b, y + ky - 1, x + kx - 1, ci] (zero
+ *         outside the image) + bias[co] (bias may be NULL), as an implicit GEMM on a split contraction:
+ *         GWEN_CONTRACT_BF16X6 (fp32-class; GWEN_CONTRACT_F16X3 means it here, as in K3) or GWEN_CONTRACT_BF16X3, which
+ *         must be the one the image was packed for.  flags, a sum of
+ *           GWEN_CONV_POOL    2x2 / stride 2 max-pool of (conv + bias), floor rule: out is [B, H / 2, W / 2, Cout]
+ *                             and the un-pooled result is never written; a NaN in a window gives NaN;
+ *           GWEN_CONV_AFFINE  then v scale[co] + shift[co]  (after the pool: a negative scale does not commute with max);
+ *           GWEN_CONV_RELU    then max(0, v).
+ *         1 <= Cin, Cout <= 2048.  Channels beyond Cin and pixels outside the image enter as true zeros, whatever
+ *         the memory there holds.  out must not overlap x.  Where one image gives too few blocks to fill the chip
+ *         (low resolutions, many channels) Cin is cut into up to 16 slices, one block each, whose raw sums
+ *         [slice][B H W][Cout] go through workspace and are added in slice order by a second launch, which applies the
+ *         epilogue: gwen_conv3x3_workspace_floats(B, H, W, Cin, Cout, flags) floats (0: one launch, workspace may be
+ *         NULL; -1: the slices' sums would reach 4 GiB and gwen_conv3x3_f32 answers GWEN_ERANGE; a shorter workspace:
+ *         GWEN_ENOSPACE).  The cut depends on H, W, Cin, Cout and the pool flag only; gwen_conv3x3_plan reports it
+ *         (output-channel tiles of 16 per block, 1 .. 4, and slices of Cin, 1 .. 16) -- the launcher and the size
+ *         function read the same plan, and a split never runs without its workspace.  More than 2^24 - 1 pixel
+ *         tiles of 8 x 16 in a batch: GWEN_ERANGE.
+ *   gwen_upsample2x_f32: bilinear x 2 with align_corners = True (source position o (n - 1) / (2 n - 1); n = 1 copies),
+ *         out [B, 2 Hin, 2 Win, C], then the affine and ReLU of flags (GWEN_CONV_AFFINE, GWEN_CONV_RELU).
+ *   gwen_channel_stats_f64: mean[c] and the biased variance var[c] of the rows of x [rows, C] (pitch ld), from sums
+ *         of x and x^2 in fp64, added in a fixed order in two stages (row chunks, then the chunks); workspace of
+ *         gwen_channel_stats_workspace_bytes(rows, C) bytes, 8-byte aligned (GWEN_ENOSPACE if shorter).  rows >= 1.
+ *   gwen_affine_relu_f32: x[r, c] = max(0, x[r, c] scale[c] + shift[c]) in place.
+ *
+ * No atomics, 64-bit element offsets, results bitwise equal run to run; in gwen_conv3x3_f32 and gwen_upsample2x_f32 an
+ * image's output has the same bits whatever the batch around it.  Bad sizes, flags, contracts (GWEN_CONTRACT_F32
+ * included), missing or misaligned pointers: GWEN_EINVAL; an input or output of 4 GiB or more: GWEN_ERANGE; both
+ * before any HIP call.  Empty outputs return GWEN_OK and write nothing.  No host synchronisation.
+ * ------------------------------------------------------------------------------------------- */
+#define GWEN_CONV_AFFINE 1
+#define GWEN_CONV_RELU 2
+#define GWEN_CONV_POOL 4
+int64_t gwen_conv3x3_pack_bytes(int64_t Cin, int64_t Cout, int contract);
+int gwen_conv3x3_pack_f32(const float *W, int64_t Cin, int64_t Cout, int transposed, int contract, void *packed,
+                          gwen_stream_t stream);
+int gwen_conv3x3_plan(int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flags, int *column_tiles, int *slices);
+int64_t gwen_conv3x3_workspace_floats(int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int flags);
+int gwen_conv3x3_f32(const float *x, const void *packed, const float *bias, const float *scale, const float *shift,
+                     float *out, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t ldx, int64_t ldo,
+                     int flags, int contract, float *workspace, int64_t workspace_floats, gwen_stream_t stream);
+int gwen_upsample2x_f32(const float *x, const float *scale, const float *shift, float *out, int64_t B, int64_t Hin,
+                        int64_t Win, int64_t C, int64_t ldx, int64_t ldo, int flags, gwen_stream_t stream);
+int64_t gwen_channel_stats_workspace_bytes(int64_t rows, int64_t C);
+int gwen_channel_stats_f64(const float *x, int64_t rows, int64_t C, int64_t ld, double *mean, double *var,
+                           void *workspace, int64_t workspace_bytes, gwen_stream_t stream);
+int gwen_affine_relu_f32(float *x, const float *scale, const float *shift, int64_t rows, int64_t C, int64_t ld,
+                         gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
