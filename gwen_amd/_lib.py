@@ -313,6 +313,13 @@ SIGNATURES = {
     "gwen_channel_stats_workspace_bytes": (_i64, [_i64, _i64]),
     "gwen_channel_stats_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "gwen_affine_relu_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "gwen_conv3x3_argmax_f32": (_int, [_vp] * 6 + [_i64] * 7 + [_int, _int, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "gwen_conv3x3_grad_weight_plan": (_int, [_i64] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    "gwen_conv3x3_grad_weight_workspace_floats": (_i64, [_i64] * 5),
+    "gwen_conv3x3_grad_weight_f32": (_int, [_vp] * 3 + [_i64] * 7 + [_int, _int, _vp, _i64, _vp]),
+    "gwen_upsample2x_backward_f32": (_int, [_vp] * 3 + [_i64] * 7 + [_vp]),
+    "gwen_norm_relu_backward_f32": (_int, [_vp] * 8 + [_i64] * 6 + [_int, _vp, _i64, _vp]),
+    "gwen_unpool2x2_f32": (_int, [_vp] * 3 + [_i64] * 6 + [_vp]),
 }
 
 

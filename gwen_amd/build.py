@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libgwen_hip.so")
 SOURCES = ["api.hip", "prep.hip", "propagate.hip", "linear.hip", "layer.hip", "chain.hip", "packw.hip", "forward.hip", "grad.hip",
            "interact.hip", "interact_rows.hip", "interact_bwd.hip", "small.hip", "tiles.hip", "cluster.hip", "wide.hip", "hash.hip", "backward.hip", "loss.hip", "ensemble.hip",
            "noise.hip", "forcing.hip", "layernorm.hip", "attention.hip", "products.hip", "gridgraph.hip", "regrid.hip", "refloss.hip", "conserve.hip",
-           "sht.hip", "spectral_conv.hip", "conv.hip"]
+           "sht.hip", "spectral_conv.hip", "conv.hip", "conv_bwd.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 

@@ -1,6 +1,7 @@
 // U-Net kernels (gwen_amd.models_cnn; the reference's second model family, its src/gwen/models_cnn.py):
 //   gwen_conv3x3_f32        3x3 / stride 1 / padding 1 convolution as an implicit GEMM on the split contractions of
 //                           split.h, with bias, per-channel affine, ReLU and a 2x2 / stride 2 max-pool in the epilogue;
+//   gwen_conv3x3_argmax_f32 the same launch that also keeps the pool's argmax and the pooled value (the backward's);
 //   gwen_conv3x3_pack_f32   Conv2d or ConvTranspose2d weights -> the B fragments the conv kernel reads, tap by tap;
 //   gwen_upsample2x_f32     bilinear x2, align_corners = True, with the same affine + ReLU;
 //   gwen_channel_stats_f64  per-channel mean / biased variance in fp64 (train-mode BatchNorm);
@@ -20,17 +21,9 @@
 // blocks to fill the chip, a fixed number of blocks one slice of Cin each, their raw sums added in slice order by
 // k_conv3x3_finish (conv_plan below; the cut depends on one image's shape only): bitwise reproducible, and the same
 // bits for an image whatever the batch around it.  No atomics; element offsets are 64-bit.
-#include "common.h"
-#include "split.h"
+#include "conv_common.h"
 
 namespace {
-
-using gwen::bf16x4;
-using gwen::bf16x8;
-
-constexpr int TH = 8, TW = 16, PH = TH + 2, PW = TW + 2, kPatch = PH * PW, CK = 32, PITCH = 48, kThreads = 256;
-constexpr int kFrag = 64 * 8;                 // bf16 elements of one packed fragment (64 lanes x 8)
-constexpr int64_t kMaxC = 2048;
 
 struct ConvArgs {
   const float *x;
@@ -42,11 +35,24 @@ struct ConvArgs {
   float *part;           // split over Cin: slice z = blockIdx.z writes its raw sums to part[z][B H W][Cout]; else NULL
   int32_t cpz;           // 32-channel chunks per slice
   int64_t rows;          // B H W
+  uint8_t *argmax;       // gwen_conv3x3_argmax_f32: the pool's winner per output element [B, H/2, W/2, Cout], and
+  float *pre;            // (optional) the pooled value + bias before affine and ReLU, pitch ldp
+  int64_t ldp;
 };
 
 __device__ inline float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }     // NaN wins, as torch's pool
+// max_nan's comparison with the index carried along, in window order (0,0) (0,1) (1,0) (1,1): the first strictly
+// largest value wins, a NaN replaces whatever came before it (torch's max_pool2d rule)
+__device__ inline int argmax_nan(float v0, float v1, float v2, float v3) {
+  float m = v0;
+  int i = 0;
+  if (v1 > m || v1 != v1) { m = v1; i = 1; }
+  if (v2 > m || v2 != v2) { m = v2; i = 2; }
+  if (v3 > m || v3 != v3) { m = v3; i = 3; }
+  return i;
+}
 
-template <int NS, int NCT, bool VEC>
+template <int NS, int NCT, bool VEC, bool AM = false>
 __global__ __launch_bounds__(kThreads) void k_conv3x3(const ConvArgs a) {
   __shared__ __attribute__((aligned(16))) __bf16 img[NS * kPatch * PITCH];
   constexpr int kImg = kPatch * PITCH;
@@ -164,6 +170,12 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3(const ConvArgs a) {
         if (py >= Hp || px >= Wp) continue;
         float v = max_nan(max_nan(acc[0][ct][2 * q], acc[0][ct][2 * q + 1]),
                           max_nan(acc[1][ct][2 * q], acc[1][ct][2 * q + 1])) + bv;
+        if constexpr (AM) {
+          const int64_t o = (b * Hp + py) * Wp + px;
+          a.argmax[o * a.Cout + c] = (uint8_t)argmax_nan(acc[0][ct][2 * q], acc[0][ct][2 * q + 1], acc[1][ct][2 * q],
+                                                         acc[1][ct][2 * q + 1]);
+          if (a.pre) a.pre[o * a.ldp + c] = v;
+        }
         if (affine) v = v * sc + sh;
         if (relu) v = v < 0.0f ? 0.0f : v;
         a.out[((b * Hp + py) * Wp + px) * a.ldo + c] = v;
@@ -176,7 +188,9 @@ __global__ __launch_bounds__(kThreads) void k_conv3x3(const ConvArgs a) {
 __global__ __launch_bounds__(256) void k_conv3x3_finish(const float *__restrict__ part, const float *__restrict__ bias,
                                                        const float *__restrict__ scale, const float *__restrict__ shift,
                                                        float *__restrict__ out, int64_t total, int64_t rows, int32_t H,
-                                                       int32_t W, int32_t Cout, int64_t ldo, int32_t nz, int32_t flags) {
+                                                       int32_t W, int32_t Cout, int64_t ldo, int32_t nz, int32_t flags,
+                                                       uint8_t *__restrict__ argmax, float *__restrict__ pre,
+                                                       int64_t ldp) {
   const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (idx >= total) return;
   const bool pool = flags & GWEN_CONV_POOL;
@@ -192,12 +206,16 @@ __global__ __launch_bounds__(256) void k_conv3x3_finish(const float *__restrict_
     return s;
   };
   float v;
-  if (pool)
-    v = max_nan(max_nan(sum_at(2 * oy, 2 * ox), sum_at(2 * oy, 2 * ox + 1)),
-                max_nan(sum_at(2 * oy + 1, 2 * ox), sum_at(2 * oy + 1, 2 * ox + 1)));
-  else
+  if (pool) {
+    const float v0 = sum_at(2 * oy, 2 * ox), v1 = sum_at(2 * oy, 2 * ox + 1);
+    const float v2 = sum_at(2 * oy + 1, 2 * ox), v3 = sum_at(2 * oy + 1, 2 * ox + 1);
+    v = max_nan(max_nan(v0, v1), max_nan(v2, v3));
+    if (argmax) argmax[pix * Cout + c] = (uint8_t)argmax_nan(v0, v1, v2, v3);
+  } else {
     v = sum_at(oy, ox);
+  }
   if (bias) v = v + bias[c];
+  if (pre) pre[pix * ldp + c] = v;
   if (flags & GWEN_CONV_AFFINE) v = v * scale[c] + shift[c];
   if (flags & GWEN_CONV_RELU) v = v < 0.0f ? 0.0f : v;
   out[pix * ldo + c] = v;
@@ -255,14 +273,6 @@ __global__ __launch_bounds__(256) void k_upsample2x(const float *__restrict__ in
 
 // stage 1: block (chunk of rows, 64 channels), thread (channel, row lane g of 4): rows g, g + 4, .. of the chunk in
 // order, then the four lanes in order; stage 2: the chunks in order.  Sums of x and x^2 in fp64.
-constexpr int kStatLanes = 4;
-inline int64_t stat_chunk_rows(int64_t rows) {
-  int64_t r = (rows + 511) / 512;
-  r = (r + kStatLanes - 1) / kStatLanes * kStatLanes;
-  return r < 32 ? 32 : r;
-}
-inline int64_t stat_chunks(int64_t rows) { const int64_t r = stat_chunk_rows(rows); return (rows + r - 1) / r; }
-
 __global__ __launch_bounds__(256) void k_stats_partial(const float *__restrict__ x, double *__restrict__ part,
                                                       int64_t rows, int32_t C, int64_t ld, int64_t chunk_rows) {
   __shared__ double sh[2][kStatLanes][64];
@@ -308,16 +318,12 @@ __global__ __launch_bounds__(256) void k_affine_relu(float *__restrict__ x, cons
   *p = v < 0.0f ? 0.0f : v;
 }
 
-inline bool split_contract(int contract) {
-  return contract == GWEN_CONTRACT_BF16X3 || contract == GWEN_CONTRACT_BF16X6 || contract == GWEN_CONTRACT_F16X3;
-}
-constexpr int64_t k4GiB = int64_t(1) << 32;
-// rows x ld fp32 elements addressable below 4 GiB (larger tensors: GWEN_ERANGE, a follow-up)
-inline bool fits(int64_t rows, int64_t ld) { return rows == 0 || ld <= k4GiB / 4 / rows; }
-
 template <int NS, int NCT>
 int launch_conv(const ConvArgs &a, bool vec, dim3 grid, hipStream_t st) {
-  if (vec) k_conv3x3<NS, NCT, true><<<grid, kThreads, 0, st>>>(a);
+  if (a.argmax && !a.part) {                                 // (a split call's argmax is k_conv3x3_finish's)
+    if (vec) k_conv3x3<NS, NCT, true, true><<<grid, kThreads, 0, st>>>(a);
+    else k_conv3x3<NS, NCT, false, true><<<grid, kThreads, 0, st>>>(a);
+  } else if (vec) k_conv3x3<NS, NCT, true><<<grid, kThreads, 0, st>>>(a);
   else k_conv3x3<NS, NCT, false><<<grid, kThreads, 0, st>>>(a);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
@@ -402,18 +408,21 @@ extern "C" int64_t gwen_conv3x3_workspace_floats(int64_t B, int64_t H, int64_t W
   return conv_workspace(conv_plan(H, W, Cin, Cout, flags & GWEN_CONV_POOL), B, H, W, Cout);
 }
 
-extern "C" int gwen_conv3x3_f32(const float *x, const void *packed, const float *bias, const float *scale,
-                                const float *shift, float *out, int64_t B, int64_t H, int64_t W, int64_t Cin,
-                                int64_t Cout, int64_t ldx, int64_t ldo, int flags, int contract, float *workspace,
-                                int64_t workspace_floats, gwen_stream_t stream) {
+namespace {
+// gwen_conv3x3_f32 (argmax and pre NULL) and gwen_conv3x3_argmax_f32 (argmax given): one plan, one accumulation
+int conv3x3_run(const float *x, const void *packed, const float *bias, const float *scale, const float *shift,
+                float *out, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t ldx, int64_t ldo,
+                int flags, int contract, float *workspace, int64_t workspace_floats, uint8_t *argmax, float *pre,
+                int64_t ldp, bool want_argmax, gwen_stream_t stream) {
   if (B < 0 || H < 0 || W < 0 || gwen_conv3x3_pack_bytes(Cin, Cout, contract) == 0 || ldx < Cin || ldo < Cout)
     return GWEN_EINVAL;
   if (flags < 0 || flags > (GWEN_CONV_AFFINE | GWEN_CONV_RELU | GWEN_CONV_POOL)) return GWEN_EINVAL;
   if ((flags & GWEN_CONV_AFFINE) && (!scale || !shift)) return GWEN_EINVAL;
+  if (want_argmax && (!(flags & GWEN_CONV_POOL) || ldp < Cout)) return GWEN_EINVAL;
   if (H >= (1 << 30) || W >= (1 << 30) || (H > 0 && W > 0 && B > INT64_MAX / H / W)) return GWEN_ERANGE;
   const bool pool = flags & GWEN_CONV_POOL;
   const int64_t Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-  if (!fits(B * H * W, ldx) || !fits(B * Ho * Wo, ldo)) return GWEN_ERANGE;
+  if (!fits(B * H * W, ldx) || !fits(B * Ho * Wo, ldo) || (want_argmax && !fits(B * Ho * Wo, ldp))) return GWEN_ERANGE;
   if (B * Ho * Wo == 0) return GWEN_OK;
   // the plan decides the grid AND the workspace: a split (nz > 1) never runs without its slabs
   const ConvPlan p = conv_plan(H, W, Cin, Cout, pool);
@@ -424,8 +433,10 @@ extern "C" int gwen_conv3x3_f32(const float *x, const void *packed, const float 
   if (tiles >= (1 << 24)) return GWEN_ERANGE;
   if (!x || !packed || !out || x == out || !gwen_aligned(x, 4) || !gwen_aligned(out, 4) || !gwen_aligned(packed, 16))
     return GWEN_EINVAL;
+  if (want_argmax && (!argmax || (pre && (!gwen_aligned(pre, 4) || pre == out || pre == x)))) return GWEN_EINVAL;
   if (need > 0 && (!workspace || workspace_floats < need || !gwen_aligned(workspace, 4))) return GWEN_ENOSPACE;
   ConvArgs a;
+  a.argmax = argmax; a.pre = pre; a.ldp = ldp;
   a.x = x; a.P = static_cast<const __bf16 *>(packed); a.bias = bias; a.scale = scale; a.shift = shift; a.out = out;
   a.H = (int32_t)H; a.W = (int32_t)W; a.Cin = (int32_t)Cin; a.Cout = (int32_t)Cout;
   // pooled: only the rows and columns some window covers (the floor rule's last odd row / column starts no tile)
@@ -442,9 +453,28 @@ extern "C" int gwen_conv3x3_f32(const float *x, const void *packed, const float 
   if (rc != GWEN_OK || p.nz <= 1) return rc;
   const int64_t total = B * Ho * Wo * Cout;
   k_conv3x3_finish<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(workspace, bias, scale, shift, out, total, a.rows,
-                                                                   (int32_t)H, (int32_t)W, (int32_t)Cout, ldo, p.nz, flags);
+                                                                   (int32_t)H, (int32_t)W, (int32_t)Cout, ldo, p.nz, flags,
+                                                                   argmax, pre, ldp);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
+}
+}  // namespace
+
+extern "C" int gwen_conv3x3_f32(const float *x, const void *packed, const float *bias, const float *scale,
+                                const float *shift, float *out, int64_t B, int64_t H, int64_t W, int64_t Cin,
+                                int64_t Cout, int64_t ldx, int64_t ldo, int flags, int contract, float *workspace,
+                                int64_t workspace_floats, gwen_stream_t stream) {
+  return conv3x3_run(x, packed, bias, scale, shift, out, B, H, W, Cin, Cout, ldx, ldo, flags, contract, workspace,
+                     workspace_floats, nullptr, nullptr, Cout, false, stream);
+}
+
+extern "C" int gwen_conv3x3_argmax_f32(const float *x, const void *packed, const float *bias, const float *scale,
+                                       const float *shift, float *out, int64_t B, int64_t H, int64_t W, int64_t Cin,
+                                       int64_t Cout, int64_t ldx, int64_t ldo, int flags, int contract,
+                                       float *workspace, int64_t workspace_floats, uint8_t *argmax, float *pre,
+                                       int64_t ldp, gwen_stream_t stream) {
+  return conv3x3_run(x, packed, bias, scale, shift, out, B, H, W, Cin, Cout, ldx, ldo, flags, contract, workspace,
+                     workspace_floats, argmax, pre, pre ? ldp : Cout, true, stream);
 }
 
 extern "C" int gwen_upsample2x_f32(const float *x, const float *scale, const float *shift, float *out, int64_t B,

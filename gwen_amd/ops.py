@@ -1,7 +1,8 @@
 """Tensor-level wrappers over the C ABI (include/gwen_hip.h) and the autograd Function of one layer.
 
 torch is used for device memory, the current HIP stream and autograd bookkeeping only; every
-arithmetic step of the layer runs in libgwen_hip.so.
+arithmetic step of the layer runs in libgwen_hip.so.  The U-Net's raw ops, forward (csrc/conv.hip) and backward
+(csrc/conv_bwd.hip: conv3x3_grad_weight, upsample2x_backward, norm_relu_backward, unpool2x2), are at the end.
 """
 from __future__ import annotations
 
@@ -735,11 +736,17 @@ def conv3x3_pack(weight: Tensor, transposed: bool = False, contract: Optional[st
 
 
 def conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, transposed: bool = False, pool: bool = False,
-            affine=None, relu: bool = False, contract: Optional[str] = None, out: Optional[Tensor] = None) -> Tensor:
+            affine=None, relu: bool = False, contract: Optional[str] = None, out: Optional[Tensor] = None,
+            argmax: bool = False):
     """3x3 / stride 1 / padding 1 convolution of channels-last ``x`` [B, H, W, Cin] (gwen_conv3x3_f32): conv + bias, then
     ``pool`` (2x2 / stride 2 max, floor rule), then ``affine`` = (scale, shift) per output channel, then ReLU, in one
     launch.  ``transposed``: ``weight`` is a ConvTranspose2d's [Cin, Cout, 3, 3].  ``contract``: "bf16x6" (default,
-    fp32-class; "f16x3" means it too) or "3xbf16".  ``out``: where to write, [B, Ho, Wo, Cout], a channel slice allowed."""
+    fp32-class; "f16x3" means it too) or "3xbf16".  ``out``: where to write, [B, Ho, Wo, Cout], a channel slice allowed.
+    ``argmax`` (with ``pool`` only; gwen_conv3x3_argmax_f32): returns ``(out, argmax, pre)`` -- the same bits in ``out``,
+    the window's winner as uint8 [B, Ho, Wo, Cout] (0 .. 3 in the order (0,0) (0,1) (1,0) (1,1), torch's rule) and the
+    pooled value + bias before the affine and the ReLU: what the backward keeps."""
+    if argmax and not pool:
+        raise ValueError("conv3x3: argmax needs pool=True")
     b, h, w, cin, ldx = _nhwc(x, "x")
     img = conv3x3_pack(weight, transposed, contract)
     cout, wcin = (weight.size(1), weight.size(0)) if transposed else (weight.size(0), weight.size(1))
@@ -764,6 +771,15 @@ def conv3x3(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, transposed
     # the slices' raw sums (low resolutions); -1: they would reach 4 GiB, and the launcher answers GWEN_ERANGE
     nws = max(int(_lib.lib().gwen_conv3x3_workspace_floats(b, h, w, cin, cout, flags)), 0)
     ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws > 0 else None
+    if argmax:
+        am = torch.empty(b, ho, wo, cout, dtype=torch.uint8, device=dev)
+        pre = torch.empty(b, ho, wo, cout, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().gwen_conv3x3_argmax_f32(_ptr(x), _ptr(img), _ptr(bias), _ptr(s), _ptr(t), _ptr(out), b, h, w,
+                                                    cin, cout, ldx, ldo, flags, _dense_code(contract or "bf16x6"),
+                                                    _ptr(ws), nws, _ptr(am), _ptr(pre), cout, _stream(dev))
+        _lib.check(rc, "gwen_conv3x3_argmax_f32")
+        return out, am, pre
     with torch.cuda.device(dev):
         rc = _lib.lib().gwen_conv3x3_f32(_ptr(x), _ptr(img), _ptr(bias), _ptr(s), _ptr(t), _ptr(out), b, h, w, cin, cout,
                                          ldx, ldo, flags, _dense_code(contract or "bf16x6"), _ptr(ws), nws, _stream(dev))
@@ -822,3 +838,110 @@ def affine_relu_(x: Tensor, scale: Tensor, shift: Tensor) -> Tensor:
         rc = _lib.lib().gwen_affine_relu_f32(_ptr(x), _ptr(s), _ptr(t), b * h * w, c, ld, _stream(x.device))
     _lib.check(rc, "gwen_affine_relu_f32")
     return x
+
+
+# ---- U-Net backward (csrc/conv_bwd.hip) ----
+
+def conv3x3_grad_weight_plan(b: int, h: int, w: int, cin: int, cout: int):
+    """(channel tiles of 16 x 16 per block, pixel chunks) of ``conv3x3_grad_weight`` at these shapes."""
+    tiles, chunks = ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().gwen_conv3x3_grad_weight_plan(b, h, w, cin, cout, ctypes.byref(tiles), ctypes.byref(chunks)),
+               "gwen_conv3x3_grad_weight_plan")
+    return tiles.value, chunks.value
+
+
+def conv3x3_grad_weight(g: Tensor, x: Tensor, transposed: bool = False, contract: Optional[str] = None) -> Tensor:
+    """The 3x3 weight gradient (gwen_conv3x3_grad_weight_f32): ``g`` [B, H, W, Cout] the gradient of the convolution's
+    output, ``x`` [B, H, W, Cin] its input, both channels-last, channel slices allowed.  Returns the layer's weight
+    shape: [Cout, Cin, 3, 3], or ``transposed`` a ConvTranspose2d's [Cin, Cout, 3, 3].  ``contract`` as ``conv3x3``."""
+    b, h, w, cout, ldg = _nhwc(g, "g")
+    xb, xh, xw, cin, ldx = _nhwc(x, "x")
+    if (xb, xh, xw) != (b, h, w) or x.device != g.device:
+        raise ValueError(f"g {tuple(g.shape)} and x {tuple(x.shape)} must agree in [B, H, W] and device")
+    dev = g.device
+    gw = torch.empty((cin, cout, 3, 3) if transposed else (cout, cin, 3, 3), dtype=torch.float32, device=dev)
+    code = _dense_code(contract or "bf16x6")
+    nws = max(int(_lib.lib().gwen_conv3x3_grad_weight_workspace_floats(b, h, w, cin, cout)), 0)
+    ws = torch.empty(nws, dtype=torch.float32, device=dev) if nws > 0 else None
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_conv3x3_grad_weight_f32(_ptr(g), _ptr(x), _ptr(gw), b, h, w, cin, cout, ldg, ldx,
+                                                     int(transposed), code, _ptr(ws), nws, _stream(dev))
+    _lib.check(rc, "gwen_conv3x3_grad_weight_f32")
+    return gw
+
+
+def upsample2x_backward(g: Tensor, mask_from: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """The adjoint of ``upsample2x`` (gwen_upsample2x_backward_f32, a gather): ``g`` [B, 2H, 2W, C] -> [B, H, W, C].
+    ``mask_from``: a tensor of g's shape; g counts only where it is > 0 (the ReLU after the upsample)."""
+    b, h2, w2, c, ldg = _nhwc(g, "g")
+    if h2 % 2 or w2 % 2:
+        raise ValueError(f"g must be [B, 2H, 2W, C], got {tuple(g.shape)}")
+    h, w = h2 // 2, w2 // 2
+    dev = g.device
+    ldm = c
+    if mask_from is not None:
+        mb, mh, mw, mc, ldm = _nhwc(mask_from, "mask_from")
+        if (mb, mh, mw, mc) != (b, h2, w2, c) or mask_from.device != dev:
+            raise ValueError(f"mask_from must have g's shape {tuple(g.shape)}, got {tuple(mask_from.shape)}")
+    if out is None:
+        out = torch.empty(b, h, w, c, dtype=torch.float32, device=dev)
+    ob, oh, ow, oc, ldo = _nhwc(out, "out")
+    if (ob, oh, ow, oc) != (b, h, w, c) or out.device != dev:
+        raise ValueError(f"out must be [{b}, {h}, {w}, {c}] on {dev}, got {tuple(out.shape)}")
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_upsample2x_backward_f32(_ptr(g), _ptr(mask_from), _ptr(out), b, h, w, c, ldg, ldm, ldo,
+                                                     _stream(dev))
+    _lib.check(rc, "gwen_upsample2x_backward_f32")
+    return out
+
+
+def norm_relu_backward(g_y: Tensor, y: Tensor, pre: Tensor, weight: Tensor, mean: Tensor, rstd: Tensor, train: bool):
+    """Backward of ``y = relu(weight * xhat + bias)``, ``xhat = (pre - mean) * rstd`` per channel over channels-last
+    [B, H, W, C] tensors (channel slices allowed): ``(g_pre, g_weight, g_bias)`` (gwen_norm_relu_backward_f32).
+    ``mean`` / ``rstd``: fp64 [C], the batch's (``train``) or the running ones.  g_weight and g_bias come back as fp64
+    [C] (fp64 sums in a fixed two-stage order, as ``channel_stats``); g_pre is fp32, contiguous."""
+    b, h, w, c, ldg = _nhwc(g_y, "g_y")
+    dev = g_y.device
+    lds = []
+    for name, t in (("y", y), ("pre", pre)):
+        tb, th, tw, tc, ld = _nhwc(t, name)
+        if (tb, th, tw, tc) != (b, h, w, c) or t.device != dev:
+            raise ValueError(f"{name} must have g_y's shape {tuple(g_y.shape)}, got {tuple(t.shape)}")
+        lds.append(ld)
+    _require(weight, "weight")
+    for name, t in (("mean", mean), ("rstd", rstd)):
+        if t.dtype != torch.float64 or tuple(t.shape) != (c,) or t.device != dev:
+            raise ValueError(f"{name} must be a float64 [{c}] tensor on {dev}")
+    if tuple(weight.shape) != (c,) or weight.device != dev:
+        raise ValueError(f"weight must be [{c}] on {dev}")
+    rows = b * h * w
+    nbytes = int(_lib.lib().gwen_channel_stats_workspace_bytes(rows, c))
+    if nbytes == 0:
+        raise ValueError(f"norm_relu_backward needs at least one row and 1 <= C <= 2048; got rows {rows}, C {c}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    sums = torch.empty(2, c, dtype=torch.float64, device=dev)
+    g_pre = torch.empty(b, h, w, c, dtype=torch.float32, device=dev)
+    weight, mean, rstd = weight.detach().contiguous(), mean.contiguous(), rstd.contiguous()
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_norm_relu_backward_f32(_ptr(g_y), _ptr(y), _ptr(pre), _ptr(weight), _ptr(mean), _ptr(rstd),
+                                                    _ptr(g_pre), _ptr(sums), rows, c, ldg, lds[0], lds[1], c,
+                                                    int(bool(train)), _ptr(ws), nbytes, _stream(dev))
+    _lib.check(rc, "gwen_norm_relu_backward_f32")
+    return g_pre, sums[1], sums[0]
+
+
+def unpool2x2(g_p: Tensor, argmax: Tensor, h: int, w: int) -> Tensor:
+    """The 2x2 max-pool's backward (gwen_unpool2x2_f32): ``g_p`` [B, h // 2, w // 2, C] goes to each window's winner
+    (``argmax`` of ``conv3x3(..., argmax=True)``) in a zero-filled [B, h, w, C]."""
+    b, hp, wp, c, ldg = _nhwc(g_p, "g_p")
+    if (hp, wp) != (h // 2, w // 2):
+        raise ValueError(f"g_p must be [B, {h // 2}, {w // 2}, C], got {tuple(g_p.shape)}")
+    if argmax.dtype != torch.uint8 or tuple(argmax.shape) != (b, hp, wp, c) or argmax.device != g_p.device:
+        raise ValueError(f"argmax must be a uint8 tensor of g_p's shape {tuple(g_p.shape)} on its device")
+    argmax = argmax.contiguous()
+    dev = g_p.device
+    out = torch.empty(b, h, w, c, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().gwen_unpool2x2_f32(_ptr(g_p), _ptr(argmax), _ptr(out), b, h, w, c, ldg, c, _stream(dev))
+    _lib.check(rc, "gwen_unpool2x2_f32")
+    return out

@@ -1393,6 +1393,58 @@ int gwen_channel_stats_f64(const float *x, int64_t rows, int64_t C, int64_t ld, 
 int gwen_affine_relu_f32(float *x, const float *scale, const float *shift, int64_t rows, int64_t C, int64_t ld,
                          gwen_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * U-Net backward (csrc/conv.hip, csrc/conv_bwd.hip; gwen_amd.models_cnn with grad=True).  Same conventions as above:
+ * channels-last fp32 rows with a pitch, no atomics, a fixed summation order (bitwise reproducible), 64-bit element
+ * offsets, no host synchronisation, tensors of 4 GiB or more GWEN_ERANGE, bad arguments GWEN_EINVAL before any HIP call.
+ * The data gradient of a 3x3 convolution is gwen_conv3x3_f32 with the weight packed as the OTHER layer type.
+ *
+ *   gwen_conv3x3_argmax_f32: gwen_conv3x3_f32 (same plan, same accumulation, the same bits in out) that also keeps
+ *         what the backward needs of the pool.  Only legal with GWEN_CONV_POOL (else GWEN_EINVAL).  argmax (required):
+ *         uint8 [B, H / 2, W / 2, Cout], packed -- the winner of the window in the order (0,0) (0,1) (1,0) (1,1): the
+ *         first strictly largest value, a NaN replacing whatever came before it (torch's max_pool2d rule).  pre
+ *         (optional, pitch ldp >= Cout): the pooled value + bias before the affine and the ReLU.
+ *   gwen_conv3x3_grad_weight_f32: gw[co][ci][ky][kx] = sum_{b, y, x} g[b, y, x, co] x[b, y + ky - 1, x + kx - 1, ci]
+ *         (zeros outside the image), g [B, H, W, Cout] pitch ldg, x [B, H, W, Cin] pitch ldx, gw a Conv2d's
+ *         [Cout, Cin, 3, 3]; transposed = 1 writes a ConvTranspose2d's [Cin, Cout, 3, 3] with the taps flipped
+ *         (Cin = the channels of x, the layer's input).  Split contractions only, both operands split on the fly.
+ *         The pixel tiles of 8 x 16 are cut into chunks, each writing its raw sums once to a slab of workspace
+ *         ([chunks][9 Cin Cout] floats); the slabs are added in chunk order (gwen_reduce_chunks_batched).
+ *         gwen_conv3x3_grad_weight_workspace_floats: the floats needed (0: one chunk, workspace may be NULL; -1: out
+ *         of range -- the slabs or an input would reach 4 GiB -- and the launcher answers GWEN_ERANGE; shorter:
+ *         GWEN_ENOSPACE).  gwen_conv3x3_grad_weight_plan reports the cut: channel tiles of 16 x 16 per block (1, 2
+ *         or 4) and pixel chunks.  The launcher and the size function read the same plan; the cut is a function of
+ *         the shapes only.  An empty batch or image writes zeros.
+ *   gwen_upsample2x_backward_f32: out [B, Hin, Win, C] = the adjoint of gwen_upsample2x_f32 applied to g
+ *         [B, 2 Hin, 2 Win, C]: every input pixel sums the output pixels that read it in ascending (oy, ox), with the
+ *         forward's own weights.  mask (optional, the shape of g, pitch ldm): g counts only where mask > 0.
+ *   gwen_norm_relu_backward_f32: y = relu(gamma xhat + beta), xhat = (pre - mean) rstd, over rows x C.  g_z = g_y
+ *         [y > 0]; sums[0][c] = g_beta = sum g_z and sums[1][c] = g_gamma = sum g_z xhat in fp64 (two stages in a fixed
+ *         order, as gwen_channel_stats_f64; workspace of gwen_channel_stats_workspace_bytes(rows, C) bytes);
+ *         g_pre = gamma rstd (g_z - g_beta / rows - xhat g_gamma / rows) (train = 1, mean and rstd the batch's) or
+ *         gamma rstd g_z (train = 0, the running statistics) in fp32.  g_pre overlaps no input.
+ *   gwen_unpool2x2_f32: out [B, H, W, C] = g_p [B, H / 2, W / 2, C] at each window's argmax, zeros elsewhere (the
+ *         last odd row / column included).
+ * ------------------------------------------------------------------------------------------- */
+int gwen_conv3x3_argmax_f32(const float *x, const void *packed, const float *bias, const float *scale,
+                            const float *shift, float *out, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout,
+                            int64_t ldx, int64_t ldo, int flags, int contract, float *workspace,
+                            int64_t workspace_floats, uint8_t *argmax, float *pre, int64_t ldp, gwen_stream_t stream);
+int gwen_conv3x3_grad_weight_plan(int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int *channel_tiles,
+                                  int64_t *pixel_chunks);
+int64_t gwen_conv3x3_grad_weight_workspace_floats(int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout);
+int gwen_conv3x3_grad_weight_f32(const float *g, const float *x, float *gw, int64_t B, int64_t H, int64_t W,
+                                 int64_t Cin, int64_t Cout, int64_t ldg, int64_t ldx, int transposed, int contract,
+                                 float *workspace, int64_t workspace_floats, gwen_stream_t stream);
+int gwen_upsample2x_backward_f32(const float *g, const float *mask, float *out, int64_t B, int64_t Hin, int64_t Win,
+                                 int64_t C, int64_t ldg, int64_t ldm, int64_t ldo, gwen_stream_t stream);
+int gwen_norm_relu_backward_f32(const float *g_y, const float *y, const float *pre, const float *weight,
+                                const double *mean, const double *rstd, float *g_pre, double *sums, int64_t rows,
+                                int64_t C, int64_t ldg, int64_t ldy, int64_t ldp, int64_t ldo, int train,
+                                void *workspace, int64_t workspace_bytes, gwen_stream_t stream);
+int gwen_unpool2x2_f32(const float *g_p, const uint8_t *argmax, float *out, int64_t B, int64_t H, int64_t W, int64_t C,
+                       int64_t ldg, int64_t ldo, gwen_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
