@@ -76,6 +76,16 @@ class ShtCall(C.Structure):
                 ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class ShtRingsCall(C.Structure):
+    """gwen_sht_rings_call (include/gwen_hip.h)."""
+    _fields_ = [("op", C.c_int32), ("adjoint", C.c_int32), ("in0", C.c_void_p), ("in1", C.c_void_p),
+                ("in_f64", C.c_int32), ("out0", C.c_void_p), ("out1", C.c_void_p), ("out_f64", C.c_int32),
+                ("nodes", C.c_void_p), ("lat_w", C.c_void_p), ("twiddle", C.c_void_p), ("seed", C.c_void_p),
+                ("ring_nlon", C.c_void_p), ("ring_start", C.c_void_p), ("batch", C.c_int64), ("nlat", C.c_int64),
+                ("points", C.c_int64), ("max_nlon", C.c_int64), ("lmax", C.c_int64), ("C", C.c_int64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 ORDER_AUTO, ORDER_TRANSFORM_FIRST, ORDER_AGGREGATE_FIRST, ORDER_FUSED, ORDER_FUSED_EXACT = -1, 0, 1, 2, 3
 CONTRACT_BF16X3, CONTRACT_F32, CONTRACT_BF16X6, CONTRACT_F16X3 = 0, 1, 2, 3          # GWEN_CONTRACT_* (include/gwen_hip.h)
 CONTRACT_NAMES = {"3xbf16": CONTRACT_BF16X3, "bf16x3": CONTRACT_BF16X3, "fp32": CONTRACT_F32, "bf16x6": CONTRACT_BF16X6,
@@ -301,6 +311,8 @@ SIGNATURES = {
                                   + [_int, _vp, C.c_size_t, _vp]),
     "gwen_sht_transform": (_int, [C.POINTER(ShtCall)]),
     "gwen_sht_fft_supported": (_int, [_i64]),
+    "gwen_sht_rings_transform": (_int, [C.POINTER(ShtRingsCall)]),
+    "gwen_sht_rings_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
     "gwen_spectral_conv_supported": (_int, [_i64, _i64, _int]),
     "gwen_spectral_conv_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "gwen_spectral_conv_grad_weight_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),

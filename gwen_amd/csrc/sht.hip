@@ -18,6 +18,9 @@
 // k_sht_lon_fft_inv of sht_fft.h, one fp64 FFT a ring and channel in LDS: the same ring, the same numbers up to rounding.
 // lon_fwd() and lon_inv() below are the one place where the four launchers choose.
 //
+// On a reduced Gaussian grid (gwen_sht_rings_transform: a ring length of its own on every latitude) they are
+// k_sht_rings_lon_fwd and k_sht_rings_lon_inv ("reduced grids" below): the same direct sums, one ring a block.
+//
 // The vector transforms, (u, v) <-> (vort, div), run the same longitude kernels on u and on v (ring [2, chunk, ...]) and
 // two latitude kernels of their own, k_vsht_lat_fwd and k_vsht_lat_inv ("vector harmonics" below).
 #include "common.h"
@@ -318,6 +321,143 @@ __global__ __launch_bounds__(kThreads) void k_sht_lon_inv(const double *__restri
     if (i0 + k < nlon) xo[(int64_t)(i0 + k) * C] = (TOut)(acc[k] * w);
 }
 
+// ---- reduced grids: rings of unequal length (gwen_sht_rings_transform) ----------------------------------------------
+// Ring j holds ring_nlon[j] longitudes 2 pi i / ring_nlon[j], the rows ring_start[j] ... of an item's P points, and
+// carries the orders m <= M_j = min(lmax, (ring_nlon[j] - 1) / 2); tw is one table a ring, end to end, tw[ring_start[j] +
+// i] = (cos, sin)(2 pi i / ring_nlon[j]).  The sums are those of k_sht_lon_fwd and k_sht_lon_inv term for term -- one
+// thread's fma chain in ascending i or m, the table index stepping by (idx += m) mod ring_nlon[j] -- so rings of one
+// length give the bits of the regular grid.  What changes is who shares a wave: a block owns one ring, 64 (item, channel)
+// lanes and 64 orders (longitudes), so the ring's length, start and M_j are block-uniform and the table indices and
+// twiddles stay in scalar registers.  The forward kernel stores zeros in the columns of the orders above M_j (the
+// latitude kernels read every column, and the workspace arrives uninitialised); the inverse kernel does not read them.
+
+// The ring of the b-th row of blocks: from the equator outwards, nlat / 2, nlat / 2 - 1, nlat / 2 + 1, ...  On a reduced
+// Gaussian grid that is the longest rings first, so the short polar rings fill the tail of the launch.
+__device__ __forceinline__ int ring_of(int b, int nlat) {
+  const int h = nlat >> 1;
+  return b & 1 ? h - ((b + 1) >> 1) : h + (b >> 1);
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(kThreads) void k_sht_rings_lon_fwd(const TIn *__restrict__ x, const dpair *__restrict__ tw,
+                                                                const int *__restrict__ ring_nlon,
+                                                                const int64_t *__restrict__ ring_start,
+                                                                double *__restrict__ ring, int64_t lanes, int64_t P,
+                                                                int nlat, int L, int C, int mtiles, int ltiles) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int blk = (int)blockIdx.x;
+  const int mt = blk % mtiles;
+  blk /= mtiles;
+  const int lt = blk % ltiles;
+  const int j = ring_of(blk / ltiles, nlat);
+  const int nlon = ring_nlon[j];
+  const int M = L < ((nlon - 1) >> 1) ? L : (nlon - 1) >> 1;
+  const int m0 = __builtin_amdgcn_readfirstlane((mt * 4 + wave) * kLonK);
+  if (m0 > L) return;
+  const int64_t q = (int64_t)lt * 64 + lane;
+  const int64_t qq = q < lanes ? q : lanes - 1;           // a lane past the end reads the last one and stores nothing
+  const int64_t item = qq / C;
+  const int c = (int)(qq - item * C);
+  double *out = ring + ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
+  if (m0 > M) {                                           // a wave of truncated orders (all of them >= 1): zeros, and done
+    if (q >= lanes) return;
+#pragma unroll
+    for (int k = 0; k < kLonK; ++k) {
+      const int m = m0 + k;
+      if (m > L) continue;
+      out[(int64_t)m * C] = 0.0;
+      out[-(int64_t)m * C] = 0.0;
+    }
+    return;
+  }
+  int mk[kLonK], idx[kLonK];
+  double ac[kLonK], as[kLonK];
+#pragma unroll
+  for (int k = 0; k < kLonK; ++k) {
+    mk[k] = m0 + k <= M ? m0 + k : 0;                     // an order past M_j walks order 0 and is stored as zero
+    idx[k] = 0;
+    ac[k] = 0.0;
+    as[k] = 0.0;
+  }
+  const int64_t start = ring_start[j];
+  const dpair *twj = tw + start;
+  const TIn *xp = x + (item * P + start) * C + c;
+#pragma unroll 2
+  for (int i = 0; i < nlon; ++i) {
+    const double xv = (double)xp[(int64_t)i * C];
+#pragma unroll
+    for (int k = 0; k < kLonK; ++k) {
+      const dpair t = twj[idx[k]];
+      ac[k] = fma(xv, t.x, ac[k]);
+      as[k] = fma(xv, t.y, as[k]);
+      idx[k] += mk[k];
+      if (idx[k] >= nlon) idx[k] -= nlon;
+    }
+  }
+  if (q >= lanes) return;
+#pragma unroll
+  for (int k = 0; k < kLonK; ++k) {
+    const int m = m0 + k;
+    if (m > L) continue;
+    out[(int64_t)m * C] = m <= M ? ac[k] : 0.0;
+    if (m > 0) out[-(int64_t)m * C] = m <= M ? as[k] : 0.0;
+  }
+}
+
+template <typename TOut>
+__global__ __launch_bounds__(kThreads) void k_sht_rings_lon_inv(const double *__restrict__ ring,
+                                                                const dpair *__restrict__ tw,
+                                                                const int *__restrict__ ring_nlon,
+                                                                const int64_t *__restrict__ ring_start,
+                                                                const double *__restrict__ lat_w, TOut *__restrict__ x,
+                                                                int64_t lanes, int64_t P, int nlat, int L, int C,
+                                                                int itiles, int ltiles) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int blk = (int)blockIdx.x;
+  const int it = blk % itiles;
+  blk /= itiles;
+  const int lt = blk % ltiles;
+  const int j = ring_of(blk / ltiles, nlat);
+  const int nlon = ring_nlon[j];
+  const int M = L < ((nlon - 1) >> 1) ? L : (nlon - 1) >> 1;
+  const int i0 = __builtin_amdgcn_readfirstlane((it * 4 + wave) * kLonK);
+  if (i0 >= nlon) return;
+  const int64_t q = (int64_t)lt * 64 + lane;
+  const int64_t qq = q < lanes ? q : lanes - 1;
+  const int64_t item = qq / C;
+  const int c = (int)(qq - item * C);
+  int step[kLonK], idx[kLonK];
+  double acc[kLonK];
+#pragma unroll
+  for (int k = 0; k < kLonK; ++k) {
+    step[k] = i0 + k < nlon ? i0 + k : 0;
+    idx[k] = 0;
+    acc[k] = 0.0;
+  }
+  const int64_t start = ring_start[j];
+  const dpair *twj = tw + start;
+  const double *gp = ring + ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
+#pragma unroll 2
+  for (int m = 0; m <= M; ++m) {
+    const double gc = gp[(int64_t)m * C];
+    const double gs = m ? gp[-(int64_t)m * C] : 0.0;
+#pragma unroll
+    for (int k = 0; k < kLonK; ++k) {
+      const dpair w = twj[idx[k]];
+      acc[k] = fma(gc, w.x, acc[k]);
+      acc[k] = fma(gs, w.y, acc[k]);
+      idx[k] += step[k];
+      if (idx[k] >= nlon) idx[k] -= nlon;
+    }
+  }
+  if (q >= lanes) return;
+  const double w = lat_w ? lat_w[j] : 1.0;
+  TOut *xo = x + (item * P + start) * C + c;
+#pragma unroll
+  for (int k = 0; k < kLonK; ++k)
+    if (i0 + k < nlon) xo[(int64_t)(i0 + k) * C] = (TOut)(acc[k] * w);
+}
+
 // S_l = sum_m c_lm^2, m = -l ... l in that order; one thread per (item, l, channel)
 __global__ __launch_bounds__(kThreads) void k_sht_power(const double *__restrict__ coef, double *__restrict__ power,
                                                         int64_t total, int L, int C) {
@@ -583,7 +723,30 @@ struct Shape {
   int longitude;                 // GWEN_SHT_LON_*
   sht_fft::Plan fft;             // longitude == GWEN_SHT_LON_FFT: the butterfly schedule and the channel tile
   int fft_ctiles;
+  int64_t points;                // grid points of an item: nlat nlon, or the sum of the ring lengths
+  const int *ring_nlon;          // a reduced grid (check_rings_shape): the device tables of the ring lengths [nlat] and
+  const int64_t *ring_start;     // starts [nlat + 1]; nlon is then the longest ring.  NULL on a regular grid
 };
+
+// The device tables and the point count of a reduced grid, the fields of gwen_sht_rings_call that gwen_sht_call lacks.
+struct Rings {
+  const int *nlon;
+  const int64_t *start;
+  int64_t points;
+};
+
+// the sizes and tile counts of checked arguments; nlon is the longest ring of a reduced grid
+void set_sizes(Shape &s, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {
+  s.nlat = (int)nlat;
+  s.nlon = (int)nlon;
+  s.L = (int)lmax;
+  s.C = (int)C;
+  s.ctiles = (int)((C + kCT - 1) / kCT);
+  s.mtiles = (s.L + 4 * kLonK) / (4 * kLonK);
+  s.itiles = (s.nlon + 4 * kLonK - 1) / (4 * kLonK);
+  s.jtiles = (s.nlat + kJT - 1) / kJT;
+  s.item_bytes = nlat * (2 * lmax + 1) * C * (int64_t)sizeof(double);
+}
 
 // sizes only; 0 = fine
 int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, Shape &s,
@@ -595,19 +758,14 @@ int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, S
   if (lmax > (grid == GWEN_SHT_GAUSS ? nlat - 1 : (nlat - 1) / 2)) return GWEN_EINVAL;
   if (nlon < 2 * lmax + 1) return GWEN_EINVAL;
   if (nlat * nlon > INT32_MAX || C > INT32_MAX) return GWEN_ERANGE;      // (lmax + 1)^2 <= 2^20
-  s.nlat = (int)nlat;
-  s.nlon = (int)nlon;
-  s.L = (int)lmax;
-  s.C = (int)C;
-  s.ctiles = (int)((C + kCT - 1) / kCT);
-  s.mtiles = (s.L + 4 * kLonK) / (4 * kLonK);
-  s.itiles = (s.nlon + 4 * kLonK - 1) / (4 * kLonK);
-  s.jtiles = (s.nlat + kJT - 1) / kJT;
-  s.item_bytes = nlat * (2 * lmax + 1) * C * (int64_t)sizeof(double);
+  set_sizes(s, nlat, nlon, lmax, C);
   const int64_t lon = ((nlat * C + 63) / 64 + 1) * (int64_t)(s.mtiles > s.itiles ? s.mtiles : s.itiles);
   const int64_t lat = s.ctiles * (lmax + 1) * (int64_t)s.jtiles;
   s.item_blocks = lon > lat ? lon : lat;
   s.longitude = longitude;
+  s.points = nlat * nlon;
+  s.ring_nlon = nullptr;
+  s.ring_start = nullptr;
   if (longitude == GWEN_SHT_LON_FFT) {
     if (!sht_fft::supported(nlon)) return GWEN_EINVAL;
     s.fft = sht_fft::make_plan(s.nlon, s.C);
@@ -616,6 +774,28 @@ int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, S
     s.item_blocks = (nlat + sht_fft::kXcds - 1) * (int64_t)s.fft_ctiles;
     if (lat > s.item_blocks) s.item_blocks = lat;
   }
+  return 0;
+}
+
+// A reduced grid: nlat Gauss latitudes, `points` grid points in rings of at most max_nlon.  Sizes only; 0 = fine.  What
+// the tables hold is the caller's business.
+int check_rings_shape(const Rings &r, int64_t nlat, int64_t max_nlon, int64_t lmax, int64_t C, Shape &s) {
+  if (nlat < 1 || nlat > kMaxLat || max_nlon < 1 || C < 1) return GWEN_EINVAL;
+  if (lmax < 0 || lmax > kLMax || lmax > nlat - 1) return GWEN_EINVAL;
+  if (max_nlon < 2 * lmax + 1) return GWEN_EINVAL;
+  if (r.points > INT32_MAX || max_nlon > INT32_MAX || C > INT32_MAX) return GWEN_ERANGE;
+  // every ring has a point and none more than max_nlon, which one of them has
+  if (r.points < nlat - 1 + max_nlon || r.points > nlat * max_nlon) return GWEN_EINVAL;
+  set_sizes(s, nlat, max_nlon, lmax, C);
+  // blocks (ring, 64 (item, channel) lanes, 64 orders or longitudes): at most ceil(C / 64) lane tiles an item
+  const int64_t lon = nlat * ((C + 63) / 64) * (int64_t)(s.mtiles > s.itiles ? s.mtiles : s.itiles);
+  const int64_t lat = s.ctiles * (lmax + 1) * (int64_t)s.jtiles;
+  s.item_blocks = lon > lat ? lon : lat;
+  s.longitude = GWEN_SHT_LON_DIRECT;
+  s.fft_ctiles = 0;
+  s.points = r.points;
+  s.ring_nlon = r.nlon;
+  s.ring_start = r.start;
   return 0;
 }
 
@@ -634,6 +814,14 @@ int chunk_items(const Shape &s, size_t workspace_bytes, int64_t batch, int64_t &
 template <typename TIn>
 int lon_fwd(const Shape &s, const TIn *x, const double *tw, double *ring, int64_t nb, hipStream_t st) {
   const int64_t rows = nb * s.nlat * s.C;
+  if (s.ring_nlon) {
+    const int64_t lanes = nb * s.C, ltiles = (lanes + 63) / 64;      // nlat ltiles mtiles <= nb item_blocks
+    k_sht_rings_lon_fwd<TIn><<<dim3((unsigned)(s.nlat * ltiles * s.mtiles)), dim3(kThreads), 0, st>>>(
+        x, reinterpret_cast<const dpair *>(tw), s.ring_nlon, s.ring_start, ring, lanes, s.points, s.nlat, s.L, s.C,
+        s.mtiles, (int)ltiles);
+    GWEN_LAUNCH_CHECK();
+    return 0;
+  }
   if (s.longitude == GWEN_SHT_LON_DIRECT) {
     k_sht_lon_fwd<TIn><<<dim3((unsigned)((rows + 63) / 64 * s.mtiles)), dim3(kThreads), 0, st>>>(
         x, reinterpret_cast<const dpair *>(tw), ring, rows, s.nlon, s.L, s.C, s.mtiles);
@@ -655,6 +843,14 @@ template <typename TOut>
 int lon_inv(const Shape &s, const double *ring, const double *tw, const double *lat_w, TOut *x, int64_t nb,
             hipStream_t st) {
   const int64_t rows = nb * s.nlat * s.C;
+  if (s.ring_nlon) {
+    const int64_t lanes = nb * s.C, ltiles = (lanes + 63) / 64;
+    k_sht_rings_lon_inv<TOut><<<dim3((unsigned)(s.nlat * ltiles * s.itiles)), dim3(kThreads), 0, st>>>(
+        ring, reinterpret_cast<const dpair *>(tw), s.ring_nlon, s.ring_start, lat_w, x, lanes, s.points, s.nlat, s.L,
+        s.C, s.itiles, (int)ltiles);
+    GWEN_LAUNCH_CHECK();
+    return 0;
+  }
   if (s.longitude == GWEN_SHT_LON_DIRECT) {
     k_sht_lon_inv<TOut><<<dim3((unsigned)((rows + 63) / 64 * s.itiles)), dim3(kThreads), 0, st>>>(
         ring, reinterpret_cast<const dpair *>(tw), lat_w, x, rows, s.nlat, s.nlon, s.L, s.C, s.itiles);
@@ -685,7 +881,7 @@ int analysis(const Shape &s, const TIn *x, TOut *coef, const double *nodes, cons
   const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    if (const int rc = lon_fwd(s, x + b0 * s.nlat * (int64_t)s.nlon * s.C, tw, ring, nb, st)) return rc;
+    if (const int rc = lon_fwd(s, x + b0 * s.points * s.C, tw, ring, nb, st)) return rc;
     k_sht_lat_fwd<TOut><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1))), dim3(kThreads), lds, st>>>(
         ring, reinterpret_cast<const dpair *>(nodes), lat_w, seed, coef + b0 * T * s.C, s.nlat, s.L, s.C, s.ctiles);
     GWEN_LAUNCH_CHECK();
@@ -702,19 +898,24 @@ int synthesis(const Shape &s, const TIn *coef, TOut *x, const double *nodes, con
     k_sht_lat_inv<TIn><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1) * s.jtiles)), dim3(kThreads), 0, st>>>(
         coef + b0 * T * s.C, reinterpret_cast<const dpair *>(nodes), seed, ring, s.nlat, s.L, s.C, s.ctiles, s.jtiles);
     GWEN_LAUNCH_CHECK();
-    if (const int rc = lon_inv(s, ring, tw, lat_w, x + b0 * s.nlat * (int64_t)s.nlon * s.C, nb, st)) return rc;
+    if (const int rc = lon_inv(s, ring, tw, lat_w, x + b0 * s.points * s.C, nb, st)) return rc;
   }
   return 0;
 }
 
+bool rings_tables_ok(const Rings &r) { return r.nlon && r.start && gwen_aligned(r.nlon, 4) && gwen_aligned(r.start, 8); }
+
 int check_call(const void *a, int a_f64, const void *b, int b_f64, const double *nodes, const double *tw,
                const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C,
-               int longitude, const void *workspace, size_t workspace_bytes, Shape &s, int64_t &chunk) {
-  const int rc = check_shape(grid, nlat, nlon, lmax, C, s, longitude);
+               int longitude, const void *workspace, size_t workspace_bytes, const Rings *rings, Shape &s,
+               int64_t &chunk) {
+  const int rc = rings ? check_rings_shape(*rings, nlat, nlon, lmax, C, s)
+                       : check_shape(grid, nlat, nlon, lmax, C, s, longitude);
   if (rc) return rc;
   if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1)) return GWEN_EINVAL;
   chunk = 0;
   if (batch == 0) return 0;
+  if (rings && !rings_tables_ok(*rings)) return GWEN_EINVAL;
   if (!a || !b || !nodes || !tw || !seed || !workspace) return GWEN_EINVAL;
   if (!gwen_aligned(a, a_f64 ? 8 : 4) || !gwen_aligned(b, b_f64 ? 8 : 4) || !gwen_aligned(nodes, 16) ||
       !gwen_aligned(tw, 16) || !gwen_aligned(seed, 8) || !gwen_aligned(workspace, 8))
@@ -739,7 +940,7 @@ int vector_analysis(const Shape &s, const TIn *u, const TIn *v, TOut *vort, TOut
   const int64_t item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    const int64_t xo = b0 * s.nlat * (int64_t)s.nlon * s.C;
+    const int64_t xo = b0 * s.points * s.C;
     double *ring_v = ring + nb * item;
     if (const int rc = lon_fwd(s, u + xo, tw, ring, nb, st)) return rc;
     if (const int rc = lon_fwd(s, v + xo, tw, ring_v, nb, st)) return rc;
@@ -764,7 +965,7 @@ int vector_synthesis(const Shape &s, const TIn *vort, const TIn *div, TOut *u, T
         vort ? vort + b0 * T * s.C : nullptr, div ? div + b0 * T * s.C : nullptr,
         reinterpret_cast<const dpair *>(nodes), seed, ring, ring_v, s.nlat, s.L, s.C, s.ctiles, s.jtiles, adjoint);
     GWEN_LAUNCH_CHECK();
-    const int64_t xo = b0 * s.nlat * (int64_t)s.nlon * s.C;
+    const int64_t xo = b0 * s.points * s.C;
     if (const int rc = lon_inv(s, ring, tw, lat_w, u + xo, nb, st)) return rc;
     if (const int rc = lon_inv(s, ring_v, tw, lat_w, v + xo, nb, st)) return rc;
   }
@@ -776,14 +977,16 @@ int vector_synthesis(const Shape &s, const TIn *vort, const TIn *div, TOut *u, T
 int check_vector_call(const void *a0, const void *a1, int a_optional, int a_f64, const void *b0, const void *b1, int b_f64,
                       const double *nodes, const double *lat_w, const double *tw, const double *seed, int grid,
                       int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint, int longitude,
-                      const void *workspace, size_t workspace_bytes, Shape &s, int64_t &chunk) {
-  const int rc = check_shape(grid, nlat, nlon, lmax, C, s, longitude);
+                      const void *workspace, size_t workspace_bytes, const Rings *rings, Shape &s, int64_t &chunk) {
+  const int rc = rings ? check_rings_shape(*rings, nlat, nlon, lmax, C, s)
+                       : check_shape(grid, nlat, nlon, lmax, C, s, longitude);
   if (rc) return rc;
   s.item_bytes *= 2;
   if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1) || (adjoint != 0 && adjoint != 1))
     return GWEN_EINVAL;
   chunk = 0;
   if (batch == 0) return 0;
+  if (rings && !rings_tables_ok(*rings)) return GWEN_EINVAL;
   if (a_optional ? !a0 && !a1 : !a0 || !a1) return GWEN_EINVAL;
   if (!b0 || !b1 || !nodes || !tw || !seed || !workspace) return GWEN_EINVAL;
   if (!gwen_aligned(a0, a_f64 ? 8 : 4) || !gwen_aligned(a1, a_f64 ? 8 : 4) || !gwen_aligned(b0, b_f64 ? 8 : 4) ||
@@ -793,12 +996,13 @@ int check_vector_call(const void *a0, const void *a1, int a_optional, int a_f64,
   return chunk_items(s, workspace_bytes, batch, chunk);
 }
 
-// The four transforms behind gwen_sht_transform, each after its checks.
-int scalar_analysis(const gwen_sht_call &k) {
+// The four transforms behind gwen_sht_transform and gwen_sht_rings_transform, each after its checks.  rings: the tables of
+// a reduced grid (k.nlon is then its longest ring, k.grid and k.longitude are not read), or NULL.
+int scalar_analysis(const gwen_sht_call &k, const Rings *rings) {
   Shape s;
   int64_t chunk;
   const int rc = check_call(k.in0, k.in_f64, k.out0, k.out_f64, k.nodes, k.twiddle, k.seed, k.grid, k.batch, k.nlat,
-                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, s, chunk);
+                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, rings, s, chunk);
   if (rc || k.batch == 0) return rc;
   if (k.lat_w && !gwen_aligned(k.lat_w, 8)) return GWEN_EINVAL;
   hipStream_t st = gwen_stream(k.stream);
@@ -810,11 +1014,11 @@ int scalar_analysis(const gwen_sht_call &k) {
   return k.out_f64 ? run((const float *)k.in0, (double *)k.out0) : run((const float *)k.in0, (float *)k.out0);
 }
 
-int scalar_synthesis(const gwen_sht_call &k) {
+int scalar_synthesis(const gwen_sht_call &k, const Rings *rings) {
   Shape s;
   int64_t chunk;
   const int rc = check_call(k.in0, k.in_f64, k.out0, k.out_f64, k.nodes, k.twiddle, k.seed, k.grid, k.batch, k.nlat,
-                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, s, chunk);
+                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, rings, s, chunk);
   if (rc || k.batch == 0) return rc;
   if (k.lat_w && !gwen_aligned(k.lat_w, 8)) return GWEN_EINVAL;
   hipStream_t st = gwen_stream(k.stream);
@@ -826,12 +1030,12 @@ int scalar_synthesis(const gwen_sht_call &k) {
   return k.out_f64 ? run((const float *)k.in0, (double *)k.out0) : run((const float *)k.in0, (float *)k.out0);
 }
 
-int vector_analysis_call(const gwen_sht_call &k) {
+int vector_analysis_call(const gwen_sht_call &k, const Rings *rings) {
   Shape s;
   int64_t chunk;
   const int rc = check_vector_call(k.in0, k.in1, 0, k.in_f64, k.out0, k.out1, k.out_f64, k.nodes, k.lat_w, k.twiddle,
                                    k.seed, k.grid, k.batch, k.nlat, k.nlon, k.lmax, k.C, k.adjoint, k.longitude,
-                                   k.workspace, k.workspace_bytes, s, chunk);
+                                   k.workspace, k.workspace_bytes, rings, s, chunk);
   if (rc || k.batch == 0) return rc;
   hipStream_t st = gwen_stream(k.stream);
   double *ring = static_cast<double *>(k.workspace);
@@ -845,12 +1049,12 @@ int vector_analysis_call(const gwen_sht_call &k) {
                    : run((const float *)k.in0, (const float *)k.in1, (float *)k.out0, (float *)k.out1);
 }
 
-int vector_synthesis_call(const gwen_sht_call &k) {
+int vector_synthesis_call(const gwen_sht_call &k, const Rings *rings) {
   Shape s;
   int64_t chunk;
   const int rc = check_vector_call(k.in0, k.in1, 1, k.in_f64, k.out0, k.out1, k.out_f64, k.nodes, k.lat_w, k.twiddle,
                                    k.seed, k.grid, k.batch, k.nlat, k.nlon, k.lmax, k.C, k.adjoint, k.longitude,
-                                   k.workspace, k.workspace_bytes, s, chunk);
+                                   k.workspace, k.workspace_bytes, rings, s, chunk);
   if (rc || k.batch == 0) return rc;
   hipStream_t st = gwen_stream(k.stream);
   double *ring = static_cast<double *>(k.workspace);
@@ -895,6 +1099,16 @@ gwen_sht_call direct_call(int op, const void *in0, const void *in1, int in_f64, 
   return k;
 }
 
+int transform(const gwen_sht_call &k, const Rings *rings) {
+  switch (k.op) {
+    case GWEN_SHT_OP_ANALYSIS: return scalar_analysis(k, rings);
+    case GWEN_SHT_OP_SYNTHESIS: return scalar_synthesis(k, rings);
+    case GWEN_SHT_OP_VECTOR_ANALYSIS: return vector_analysis_call(k, rings);
+    case GWEN_SHT_OP_VECTOR_SYNTHESIS: return vector_synthesis_call(k, rings);
+  }
+  return GWEN_EINVAL;
+}
+
 }  // namespace
 
 extern "C" {
@@ -903,13 +1117,25 @@ int gwen_sht_fft_supported(int64_t nlon) { return sht_fft::supported(nlon) ? 1 :
 
 int gwen_sht_transform(const gwen_sht_call *call) {
   if (!call) return GWEN_EINVAL;
-  switch (call->op) {
-    case GWEN_SHT_OP_ANALYSIS: return scalar_analysis(*call);
-    case GWEN_SHT_OP_SYNTHESIS: return scalar_synthesis(*call);
-    case GWEN_SHT_OP_VECTOR_ANALYSIS: return vector_analysis_call(*call);
-    case GWEN_SHT_OP_VECTOR_SYNTHESIS: return vector_synthesis_call(*call);
-  }
-  return GWEN_EINVAL;
+  return transform(*call, nullptr);
+}
+
+int gwen_sht_rings_transform(const gwen_sht_rings_call *call) {
+  if (!call) return GWEN_EINVAL;
+  const gwen_sht_call k = direct_call(call->op, call->in0, call->in1, call->in_f64, call->out0, call->out1, call->out_f64,
+                                      call->nodes, call->lat_w, call->twiddle, call->seed, GWEN_SHT_GAUSS, call->batch,
+                                      call->nlat, call->max_nlon, call->lmax, call->C, call->adjoint, call->workspace,
+                                      call->workspace_bytes, call->stream);
+  const Rings rings = {call->ring_nlon, call->ring_start, call->points};
+  return transform(k, &rings);
+}
+
+int64_t gwen_sht_rings_workspace_bytes(int vector, int64_t nlat, int64_t points, int64_t max_nlon, int64_t lmax,
+                                       int64_t C) {
+  Shape s;
+  const Rings rings = {nullptr, nullptr, points};
+  if ((vector != 0 && vector != 1) || check_rings_shape(rings, nlat, max_nlon, lmax, C, s)) return 0;
+  return vector ? 2 * s.item_bytes : s.item_bytes;
 }
 
 int64_t gwen_sht_vector_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {

@@ -35,6 +35,29 @@ Convention (include/gwen_hip.h, "Spherical harmonic transforms"; tests/sht_ref.p
               ``sum_l E_l = sum_p q_p (u^2 + v^2) / 2``.  ``gradient``, ``laplacian`` and ``inverse_laplacian`` follow.
               Users of a sphere of radius ``a`` scale by ``1/a`` and ``1/a^2``.
 
+Reduced Gaussian grids (``SphericalHarmonics.reduced``, ``SphericalHarmonics.octahedral``; the octahedral ``O96 / O320 /
+O640`` and the classic ``N320`` grids of IFS, ERA5 and AIFS) keep everything above and change the rings:
+
+    grid      ``nlat`` Gauss-Legendre latitudes, the nodes and weights ``w_j`` of ``"gauss"``, south to north, and an
+              integer vector ``ring_nlon[nlat]``: ring ``j`` holds the longitudes ``2 pi i / ring_nlon[j]``,
+              ``i = 0 ... ring_nlon[j] - 1``, starting at longitude 0.  Field rows are ring-major: ring ``j`` starts at row
+              ``ring_start[j] = sum_{k<j} ring_nlon[k]`` of ``P = ring_start[nlat]`` points.  A point of ring ``j`` weighs
+              ``q = w_j / ring_nlon[j]``; the weights sum to 1.  ``octahedral_nlon(N)`` gives the ``2 N`` ring lengths
+              ``4 i + 16``, ``i = 1 ... N``, from each pole to the equator; a classic reduced grid is the user's own list
+              (the ``pl`` array of a GRIB file).
+    orders    ring ``j`` carries the orders ``m <= M_j = min(lmax, (ring_nlon[j] - 1) // 2)``: the analysis takes the orders
+              above ``M_j`` of that ring as zero and the synthesis leaves them out, one masked operator, so the adjoint
+              relations of the regular grids hold exactly.  Where every ``ring_nlon[j] >= 2 lmax + 1`` nothing is
+              truncated, and rings of one length reproduce ``SphericalHarmonics(nlat, nlon, grid="gauss")`` bit for bit.
+    limits    ``nlat <= 2048``, ``lmax <= min(1023, nlat - 1)``, ``max(ring_nlon) >= 2 lmax + 1``, ``P <= 2^31 - 1``.
+    accuracy  how well ``analysis(synthesis(c))`` returns ``c`` is a property of the pair (ring lengths, ``lmax``) and not
+              of the code: the short polar rings alias what they cannot carry.  A numpy fp64 restatement
+              (tests/sht_rings_ref.py) of the round trip of unit-normal coefficients gave, as the largest error,
+                  O8, lmax 7: 4e-15     O8, lmax 11 (M_j down to 9): 6e-15     O16, lmax 15: 4e-14
+                  O16, lmax 23: 2e-8    O16, lmax 31: 6e-3
+              -- round-off at the cubic pairing ``lmax = N - 1`` (the default of ``octahedral``), degrading beyond it.
+    longitude only ``"direct"``: octahedral ring lengths mostly have prime factors above 5, which the FFT does not take.
+
 Everything is accumulated in fp64 by two HIP kernels a transform (csrc/sht.hip): the sums along every latitude ring
 against an ``nlon``-entry twiddle table, and a contraction over the latitudes with ``Pbar_l^m`` generated on the fly (the
 vector transforms: the ring sums of ``u`` and of ``v``, and one contraction against ``m Q`` and ``D``).  The ring sums
@@ -149,6 +172,54 @@ def check_sizes(grid: str, nlat: int, nlon: int, lmax: Optional[int], longitude:
     return lmax
 
 
+def octahedral_nlon(N: int) -> np.ndarray:
+    """int64 ``[2 N]``: the ring lengths of the octahedral reduced Gaussian grid ``O<N>``, south to north -- ``4 i + 16``,
+    ``i = 1 ... N``, from each pole to the equator (20 at the poles, ``4 N + 16`` either side of the equator)."""
+    N = int(N)
+    if N < 1:
+        raise ValueError(f"N must be >= 1 (got {N})")
+    half = 4 * np.arange(1, N + 1, dtype=np.int64) + 16
+    return np.concatenate([half, half[::-1]])
+
+
+def check_rings(ring_nlon, lmax: int, longitude: str = "direct") -> np.ndarray:
+    """The ring lengths of a reduced grid as an int64 array after every size check (module docstring, "limits");
+    ValueError naming the offending value otherwise.  No device is touched."""
+    if longitude not in LONGITUDE:
+        raise ValueError(f"longitude must be one of {LONGITUDE} (got {longitude!r})")
+    if longitude != "direct":
+        raise ValueError(f'a reduced grid takes longitude="direct" only: the FFT needs ring lengths 2^a 3^b 5^c '
+                         f"(got longitude = {longitude!r})")
+    rings = np.asarray(ring_nlon)
+    if rings.ndim != 1 or rings.size < 1:
+        raise ValueError(f"ring_nlon must be a list of at least one ring length (got shape {rings.shape})")
+    if not np.issubdtype(rings.dtype, np.integer):
+        raise ValueError(f"ring_nlon must hold integers (got dtype {rings.dtype})")
+    if int(rings.min()) < 1:
+        j = int(rings.argmin())
+        raise ValueError(f"every ring needs at least one point (ring_nlon[{j}] = {int(rings[j])})")
+    nlat, most = rings.size, int(rings.max())
+    if nlat > MAX_NLAT:
+        raise ValueError(f"nlat <= {MAX_NLAT} (got {nlat} rings)")
+    if most > 2 ** 31 - 1:
+        raise ValueError(f"max(ring_nlon) = {most} does not fit int32")
+    rings = rings.astype(np.int64)
+    if int(rings.sum()) > 2 ** 31 - 1:
+        raise ValueError(f"sum(ring_nlon) = {int(rings.sum())} does not fit int32")
+    if lmax is None:
+        raise ValueError("a reduced grid needs lmax")
+    lmax = int(lmax)
+    if lmax < 0:
+        raise ValueError(f"lmax must be >= 0 (got {lmax})")
+    if lmax > MAX_LMAX:
+        raise ValueError(f"lmax <= {MAX_LMAX}: beyond it the recurrence needs rescaling (got {lmax})")
+    if lmax > nlat - 1:
+        raise ValueError(f"the gauss quadrature on {nlat} latitudes is exact up to lmax = {nlat - 1} (got {lmax})")
+    if most < 2 * lmax + 1:
+        raise ValueError(f"max(ring_nlon) >= 2 lmax + 1 = {2 * lmax + 1} (got {most})")
+    return rings
+
+
 def degree_index(lmax: int) -> np.ndarray:
     """int64 ``[(lmax + 1)^2]``: the degree ``l`` of every coefficient row."""
     return np.repeat(np.arange(lmax + 1, dtype=np.int64), 2 * np.arange(lmax + 1) + 1)
@@ -185,32 +256,71 @@ class SphericalHarmonics:
     (one item must: ValueError otherwise); the results do not depend on it.  A vector transform holds the intermediate
     of ``u`` and of ``v``, twice as much an item.  ``longitude`` chooses the longitude stage of every transform of the
     object, the adjoints behind autograd included: ``"direct"`` sums or ``"fft"`` (module docstring; ValueError where
-    ``fft_supported(nlon)`` is false)."""
+    ``fft_supported(nlon)`` is false).
+
+    ``SphericalHarmonics.reduced(ring_nlon, ...)`` and ``SphericalHarmonics.octahedral(N, ...)`` make the object of a
+    reduced Gaussian grid (module docstring): ``grid == "reduced-gauss"``, ``nlon is None``, ``rows`` is the number of
+    points and every method below works as it does on a regular grid.  ``ring_nlon`` and ``ring_start`` (numpy int64,
+    ``[nlat]`` and ``[nlat + 1]``) are there on every object, constant ``nlon`` on a regular grid."""
 
     def __init__(self, nlat: int, nlon: int, device, lmax: Optional[int] = None, grid: str = "equiangular",
                  workspace_bytes: int = 1 << 30, longitude: str = "direct"):
         self.lmax = check_sizes(grid, nlat, nlon, lmax, longitude)
         self.nlat, self.nlon, self.grid, self.longitude = int(nlat), int(nlon), grid, longitude
+        self._setup(np.full(self.nlat, self.nlon, dtype=np.int64), device, workspace_bytes)
+
+    @classmethod
+    def reduced(cls, ring_nlon, device, lmax: int, workspace_bytes: int = 1 << 30,
+                longitude: str = "direct") -> "SphericalHarmonics":
+        """The transforms of the reduced Gaussian grid with ``ring_nlon[j]`` longitudes on Gauss latitude ``j``, south to
+        north, truncated at ``lmax`` (module docstring, "Reduced Gaussian grids"; ``check_rings`` has the limits)."""
+        rings = check_rings(ring_nlon, lmax, longitude)
+        self = cls.__new__(cls)
+        self.lmax = int(lmax)
+        self.nlat, self.nlon, self.grid, self.longitude = int(rings.size), None, "reduced-gauss", longitude
+        self._setup(rings, device, workspace_bytes)
+        return self
+
+    @classmethod
+    def octahedral(cls, N: int, device, lmax: Optional[int] = None, workspace_bytes: int = 1 << 30,
+                   longitude: str = "direct") -> "SphericalHarmonics":
+        """``reduced(octahedral_nlon(N), ...)``: the octahedral grid ``O<N>``.  ``lmax`` defaults to ``N - 1``, the cubic
+        pairing, at which the round trip of a band-limited field is at round-off."""
+        rings = octahedral_nlon(N)
+        return cls.reduced(rings, device, int(N) - 1 if lmax is None else lmax, workspace_bytes, longitude)
+
+    def _setup(self, rings: np.ndarray, device, workspace_bytes: int) -> None:
+        """The tables of ``nlat`` rings of ``rings[j]`` longitudes; a regular grid keeps one ring's twiddle table, a
+        reduced one holds every ring's end to end."""
+        reduced = self.nlon is None
         self.workspace_bytes = int(workspace_bytes)
         if self.workspace_bytes < 1:
             raise ValueError(f"workspace_bytes must be positive (got {workspace_bytes})")
         from .gridgraph import _device
         self.device = _device(device)
-        self.rows = self.nlat * self.nlon
+        self.ring_nlon = rings
+        self.ring_start = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(rings, dtype=np.int64)])
+        self.rows = int(self.ring_start[-1])
         self.num_coefficients = (self.lmax + 1) ** 2
-        lat, w = quadrature(grid, self.nlat)
+        lat, w = quadrature("gauss" if reduced else self.grid, self.nlat)
         self._lat_deg = lat
         phi = np.deg2rad(lat)
         nodes = np.stack([np.sin(phi), np.cos(phi)], axis=1)
-        i = np.arange(self.nlon, dtype=np.float64)
-        tw = np.stack([np.cos(2.0 * np.pi * i / self.nlon), np.sin(2.0 * np.pi * i / self.nlon)], axis=1)
+        tables = []
+        for n in (rings if reduced else rings[:1]):
+            i = np.arange(int(n), dtype=np.float64)
+            tables.append(np.stack([np.cos(2.0 * np.pi * i / int(n)), np.sin(2.0 * np.pi * i / int(n))], axis=1))
+        tw = np.concatenate(tables, axis=0)
         seed = sectoral_seeds(self.lmax)
         dev = self.device
         self._nodes = torch.from_numpy(np.ascontiguousarray(nodes)).to(dev)
         self._twiddle = torch.from_numpy(np.ascontiguousarray(tw)).to(dev)
         self._seed = torch.from_numpy(np.ascontiguousarray(seed)).to(dev)
-        self._lat_w = torch.from_numpy(np.ascontiguousarray(w / self.nlon)).to(dev)
-        self._weights = torch.from_numpy(np.repeat(w / self.nlon, self.nlon).astype(np.float32)).to(dev)
+        self._lat_w = torch.from_numpy(np.ascontiguousarray(w / rings)).to(dev)
+        self._weights = torch.from_numpy(np.repeat(w / rings, rings).astype(np.float32)).to(dev)
+        if reduced:
+            self._ring_nlon = torch.from_numpy(rings.astype(np.int32)).to(dev)
+            self._ring_start = torch.from_numpy(self.ring_start).to(dev)
         self._degrees = torch.from_numpy(degree_index(self.lmax)).to(dev)
         big = (self._degrees * (self._degrees + 1)).to(torch.float64)
         self._lap = -big[:, None]                                # [T, 1]: the Laplacian's factor of every row
@@ -220,7 +330,7 @@ class SphericalHarmonics:
     # ---- tables -----------------------------------------------------------------------------------------------------
     @property
     def weights(self) -> Tensor:
-        """fp32 ``[nlat * nlon]``: the quadrature weight ``q`` of every grid point (sums to 1) -- the ``node_weights`` of
+        """fp32 ``[rows]``: the quadrature weight ``q`` of every grid point (sums to 1) -- the ``node_weights`` of
         ``gwen_amd.losses`` and ``gwen_amd.products``."""
         return self._weights
 
@@ -231,8 +341,13 @@ class SphericalHarmonics:
 
     @property
     def positions(self) -> np.ndarray:
-        """float64 ``[nlat * nlon, 3]`` unit vectors, the form of ``latlon_grid(...)[0]`` (a ``Regridder`` target)."""
+        """float64 ``[rows, 3]`` unit vectors, the form of ``latlon_grid(...)[0]`` (``grid_pos=``, a ``Regridder`` source
+        or target)."""
         from .gridgraph import sphere_points
+        if self.nlon is None:
+            lat = np.repeat(self._lat_deg, self.ring_nlon)
+            lon = np.concatenate([(360.0 / int(n)) * np.arange(int(n), dtype=np.float64) for n in self.ring_nlon])
+            return sphere_points(lat, lon)
         lon = (360.0 / self.nlon) * np.arange(self.nlon, dtype=np.float64)
         return sphere_points(self._lat_deg[:, None], lon[None, :])
 
@@ -244,6 +359,10 @@ class SphericalHarmonics:
         return l * l + l + m
 
     # ---- launches ---------------------------------------------------------------------------------------------------
+    def _rows_name(self) -> str:
+        """What the row count of a field is called in an error message."""
+        return "points" if self.nlon is None else "nlat * nlon"
+
     def _check(self, name: str, t, rows: int, what: str, dtypes) -> None:
         """Shapes (ValueError), then dtypes (TypeError), then devices (RuntimeError), as ``losses._check``."""
         check_rows(name, t, rows, what)
@@ -257,8 +376,12 @@ class SphericalHarmonics:
 
     def _workspace(self, batch: int, c: int, vector: bool = False) -> Tensor:
         from . import _lib
-        size = _lib.lib().gwen_sht_vector_workspace_bytes if vector else _lib.lib().gwen_sht_workspace_bytes
-        item = int(size(_lib.SHT_GRIDS[self.grid], self.nlat, self.nlon, self.lmax, c))
+        if self.nlon is None:
+            item = int(_lib.lib().gwen_sht_rings_workspace_bytes(int(vector), self.nlat, self.rows,
+                                                                 int(self.ring_nlon.max()), self.lmax, c))
+        else:
+            size = _lib.lib().gwen_sht_vector_workspace_bytes if vector else _lib.lib().gwen_sht_workspace_bytes
+            item = int(size(_lib.SHT_GRIDS[self.grid], self.nlat, self.nlon, self.lmax, c))
         if item > self.workspace_bytes:
             raise ValueError(f"workspace_bytes = {self.workspace_bytes} is below one item's intermediate ({item} bytes)")
         items = min(max(batch, 1), self.workspace_bytes // item)
@@ -280,13 +403,27 @@ class SphericalHarmonics:
         return out
 
     def _transform(self, op: int, ins, outs, weighted: bool, adjoint: bool, batch: int, c: int, ws: Tensor) -> None:
-        """``gwen_sht_transform``: one of the four transforms with this object's tables and longitude stage."""
+        """``gwen_sht_transform`` (``gwen_sht_rings_transform`` on a reduced grid): one of the four transforms with this
+        object's tables and longitude stage."""
         from . import _lib
 
         def ptr(t):                                              # a structure's pointer field takes an int or None
             return None if t is None else t.data_ptr()
 
         src = ins[0] if ins[0] is not None else ins[1]
+        if self.nlon is None:
+            call = _lib.ShtRingsCall(
+                op=op, adjoint=int(adjoint), in0=ptr(ins[0]), in1=ptr(ins[1]), in_f64=int(src.dtype == torch.float64),
+                out0=ptr(outs[0]), out1=ptr(outs[1]), out_f64=int(outs[0].dtype == torch.float64),
+                nodes=ptr(self._nodes), lat_w=ptr(self._lat_w) if weighted else None, twiddle=ptr(self._twiddle),
+                seed=ptr(self._seed), ring_nlon=ptr(self._ring_nlon), ring_start=ptr(self._ring_start), batch=batch,
+                nlat=self.nlat, points=self.rows, max_nlon=int(self.ring_nlon.max()), lmax=self.lmax, C=c,
+                workspace=ptr(ws), workspace_bytes=ws.numel() * 8,
+                stream=torch.cuda.current_stream(self.device).cuda_stream)
+            with torch.cuda.device(self.device):
+                rc = _lib.lib().gwen_sht_rings_transform(call)
+            _lib.check(rc, f"gwen_sht_rings_transform(op={op})")
+            return
         call = _lib.ShtCall(
             op=op, longitude=_lib.SHT_LONGITUDE[self.longitude], in0=ptr(ins[0]), in1=ptr(ins[1]),
             in_f64=int(src.dtype == torch.float64), out0=ptr(outs[0]), out1=ptr(outs[1]),
@@ -313,7 +450,7 @@ class SphericalHarmonics:
     def analysis(self, x: Tensor, dtype=torch.float32) -> Tensor:
         """``x [..., nlat * nlon, C]`` fp32 -> coefficients ``[..., T, C]`` in ``dtype`` (float32 or float64, rounded once
         from the fp64 sums).  Differentiable in ``x``."""
-        self._check("x", x, self.rows, "nlat * nlon", (torch.float32,))
+        self._check("x", x, self.rows, self._rows_name(), (torch.float32,))
         _check_out_dtype(dtype)
         return _Analysis.apply(x, self, dtype)
 
@@ -333,7 +470,7 @@ class SphericalHarmonics:
         if (x is None) == (coeffs is None):
             raise ValueError("power_spectrum takes exactly one of x and coeffs")
         if x is not None:
-            self._check("x", x, self.rows, "nlat * nlon", (torch.float32,))
+            self._check("x", x, self.rows, self._rows_name(), (torch.float32,))
         else:
             self._check("coeffs", coeffs, self.num_coefficients, "T", (torch.float32, torch.float64))
         _check_out_dtype(dtype)
@@ -409,7 +546,7 @@ class SphericalHarmonics:
     def vector_analysis(self, u: Tensor, v: Tensor, dtype=torch.float32) -> Tuple[Tensor, Tensor]:
         """The eastward and northward components ``u, v [..., nlat * nlon, C]`` fp32 -> spectral vorticity and
         divergence ``[..., T, C]`` in ``dtype``; row 0 of both is 0.  Differentiable in ``u`` and ``v``."""
-        self._check_pair(("u", "v"), (u, v), self.rows, "nlat * nlon", (torch.float32,))
+        self._check_pair(("u", "v"), (u, v), self.rows, self._rows_name(), (torch.float32,))
         _check_out_dtype(dtype)
         return _VectorAnalysis.apply(u, v, self, dtype)
 
@@ -453,7 +590,7 @@ class SphericalHarmonics:
             raise ValueError("kinetic_energy_spectrum takes exactly one of the pairs (u, v) and (vort, div)")
         wind = given[0]
         if wind:
-            self._check_pair(("u", "v"), (u, v), self.rows, "nlat * nlon", (torch.float32,))
+            self._check_pair(("u", "v"), (u, v), self.rows, self._rows_name(), (torch.float32,))
         else:
             self._check_pair(("vort", "div"), (vort, div), self.num_coefficients, "T", (torch.float32, torch.float64))
         _check_out_dtype(dtype)

@@ -1309,6 +1309,52 @@ int gwen_sht_transform(const gwen_sht_call *call);
 int gwen_sht_fft_supported(int64_t nlon);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spherical harmonic transforms on a reduced Gaussian grid (csrc/sht.hip, gwen_amd.spectral.SphericalHarmonics.reduced):
+ * the nlat Gauss-Legendre latitudes, south to north, with a ring length of its own on every latitude (the octahedral and
+ * the classic reduced grids of IFS, ERA5, AIFS).  Basis, coefficient rows, ops, dtype flags, lat_w, adjoint, workspace
+ * layout, chunking, reproducibility and NaN containment are those of gwen_sht_transform; the latitude kernels are the same.
+ *
+ *   ring_nlon [nlat] int32: ring j holds the longitudes 2 pi i / ring_nlon[j], i = 0 ... ring_nlon[j] - 1.
+ *   ring_start [nlat + 1] int64, 8-byte aligned: ring_start[j] = sum_{k < j} ring_nlon[k]; ring_start[nlat] = points.
+ *   x (u, v) [batch, points, C]: rows ring-major, row ring_start[j] + i is longitude i of ring j.
+ *   twiddle [points, 2] fp64, 16-byte aligned: one table a ring, end to end, twiddle[ring_start[j] + i] =
+ *         (cos, sin)(2 pi i / ring_nlon[j]); ring j indexes its own by (m i) mod ring_nlon[j].
+ *   nodes, seed, lat_w: as above; the quadrature weight of ring j is w_j / ring_nlon[j].
+ *   max_nlon: the longest ring.  Sizes: 1 <= nlat <= 2048, 0 <= lmax <= min(1023, nlat - 1), max_nlon >= 2 lmax + 1,
+ *         nlat - 1 + max_nlon <= points <= nlat max_nlon, points < 2^31.  Element offsets are 64-bit.
+ *   Truncation: ring j carries the orders m <= M_j = min(lmax, (ring_nlon[j] - 1) / 2).  The longitude sums of an
+ *         analysis store zeros in the workspace columns of the orders above M_j (the workspace may arrive holding
+ *         anything); those of a synthesis do not read them.  Both are one masked operator, so lat_w and adjoint give the
+ *         adjoints as they do above.  Where every ring_nlon[j] >= 2 lmax + 1 nothing is truncated, and rings of one
+ *         length nlon give the bits of gwen_sht_transform(GWEN_SHT_GAUSS, GWEN_SHT_LON_DIRECT) on nlat x nlon.
+ *   The longitude stage is always the direct sums: one thread's fp64 fma chain in ascending i (analysis) or m (synthesis).
+ *   The scalar fields are validated before any HIP call -- GWEN_EINVAL for a bad size, flag or op, a NULL call, a missing
+ *   or misaligned pointer (the two ring tables included); GWEN_ERANGE for points, max_nlon or C >= 2^31; GWEN_ENOSPACE
+ *   for a workspace below one item.  The CONTENTS of the device tables are the caller's responsibility: ring lengths that
+ *   do not add up to ring_start, a length above max_nlon or a start beyond points make the kernels read and write out
+ *   of bounds.  gwen_sht_rings_workspace_bytes(vector, ...): the size of ONE item of a scalar (vector = 0) or a vector
+ *   (1) transform, 0 for bad sizes.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct gwen_sht_rings_call {
+  int32_t op;      /* GWEN_SHT_OP_* */
+  int32_t adjoint; /* the vector transforms' flag; the scalar ones ignore it */
+  const void *in0, *in1;
+  int32_t in_f64;
+  void *out0, *out1;
+  int32_t out_f64;
+  const double *nodes, *lat_w, *twiddle, *seed;
+  const int32_t *ring_nlon;
+  const int64_t *ring_start;
+  int64_t batch, nlat, points, max_nlon, lmax, C;
+  void *workspace;
+  size_t workspace_bytes;
+  gwen_stream_t stream;
+} gwen_sht_rings_call;
+int gwen_sht_rings_transform(const gwen_sht_rings_call *call);
+int64_t gwen_sht_rings_workspace_bytes(int vector, int64_t nlat, int64_t points, int64_t max_nlon, int64_t lmax,
+                                       int64_t C);
+
+/* ---------------------------------------------------------------------------------------------
  * Spectral convolution (csrc/spectral_conv.hip, gwen_amd.sfno): the learned map of a spherical Fourier neural operator.
  *
  *   coef [batch, T, Cin], T = (lmax + 1)^2, rows as the transforms above: degree l owns rows l^2 .. l^2 + 2l.
