@@ -160,6 +160,10 @@ SIGNATURES = {
     "gwen_gcn_layer_tuned4_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                          _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int, _vp, _int]),
     "gwen_gcn_layer_store_mode": (_int, [_i64, _i64, _int]),
+    "gwen_gcn_layer_tuned5_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                                         _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int, _vp, _int,
+                                         _int]),
+    "gwen_gcn_layer_row_stores": (_int, [_i64, _i64, _int]),
     "gwen_gcn_layer_blocks_per_cu": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
                                             _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _vp, _int,
                                             C.POINTER(C.c_int)]),

@@ -433,7 +433,8 @@ __device__ inline void gather_passes(const int32_t *__restrict__ rowptr,
 //      kernel boundary still releases.  hipcc does not count an asm store (nothing reads it back in the kernel, and a wave's
 //      stores complete after it ends), and the trailing s_nop 1 keeps the data registers from being rewritten before the
 //      store has read them.
-// Modes 2 and 4 of the C ABI (whole rows through LDS, plain and written through) are not built.
+// Modes 2 and 4 of the C ABI stay reserved numbers (refused).  Whole rows through an LDS out tile are not a store mode but
+// a switch of their own beside it, k_layer's RS (layer.hip, "Row stores"): its row stores go through store_out<3>.
 template <int ST>
 __device__ __forceinline__ void store_out(float *p, float4_t v) {
   static_assert(ST == 1 || ST == 3, "store modes: 1 plain, 3 written through");

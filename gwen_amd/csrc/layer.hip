@@ -46,9 +46,16 @@
 //   per wave instruction.  ST = 1: plain stores.  ST = 3: the same instruction with the sc1 bit -- written through: the
 //   line goes to memory at the store and leaves the XCD's L2, so the launch leaves no dirty output for its boundary to
 //   write back (the next launch reads its input from beyond L2 either way).  Values, addresses, registers and LDS are
-//   those of ST = 1.  Which shapes run 3: layer_store_mode (measured per kernel in the step, profiles/store_*).  Whole
-//   rows through an LDS out tile (modes 2 / 4 of the C ABI) are not built; the lab that prices them is
-//   tools/experiments/store_lab.patch.
+//   those of ST = 1.  Which shapes run 3: layer_store_mode (measured per kernel in the step, profiles/store_*).
+//   Row stores (template argument RS, with ST = 3 only): the D tiles leave through an fp32 out tile in LDS as whole rows,
+//   every wave instruction one run of 1024 / (4 Fout) consecutive rows -- one contiguous KiB where ldo == Fout.  The
+//   wave holds its D tiles (bias and ReLU applied: the values of RS = false, bit for bit) until every wave of the block
+//   is through its MFMAs; a barrier; the out tile is written OVER the images, which are dead by then; a second barrier;
+//   the row stores, masked to rows < N at the store only.  The out tile has no pad: the 16-byte chunk c of row r lies
+//   at chunk c ^ swz(r) of the row (out_chunk), which keeps the D-tile writes (8 consecutive rows, one chunk) and the
+//   row reads (consecutive chunks) free of bank conflicts.  The row layout is this switch, orthogonal to the store
+//   mode; mode numbers 2 / 4 of the C ABI stay reserved and refused.  Which shapes run it: layer_row_stores (measured
+//   per kernel in the step, profiles/rowstore_*); the lab that priced it beforehand is tools/experiments/store_lab.patch.
 #include "common.h"
 #include "dispatch.h"
 #include "gather_rows.h"
@@ -94,6 +101,41 @@ struct Cfg {
   static_assert(BR % RB == 0 && BR % kTile == 0, "a block is whole gather passes and whole row tiles");
 };
 
+// Row stores (k_layer's RS): the out tile of a block, [BR][Fout] fp32 with no pad, lies over the images; it is the larger
+// of the two where the images are small (16 -> 32 at 64 rows: 8 192 B over 6 144).
+constexpr size_t out_tile_bytes(size_t images, int br, int fout) {
+  return images > (size_t)br * fout * 4 ? images : (size_t)br * fout * 4;
+}
+
+// Where the 16-byte chunk c of row r of the out tile lies, in chunks from the tile's start: chunk c ^ swz(r) of its row.
+// Banks (64 x 4 B; a 16-byte write is served in groups of 8 consecutive lanes over 32 banks = 8 chunks, a 16-byte read in
+// groups of 16 lanes over 64 banks = 16 chunks):
+//   D-tile write: the 8 lanes of a group hold 8 consecutive rows (mi = 0 .. 7 or 8 .. 15) and ONE chunk c.  Rows are 16 / 8 /
+//     4 chunks long (Fout = 64 / 32 / 16), so 8 chunks hold half a row, one row, two rows.  Fout >= 32: the 8 rows differ in
+//     r & 7, so c ^ (r & 7) takes 8 different values mod 8.  Fout = 16: the four rows of one parity share their half of the
+//     8 chunks and differ in (r >> 1) & 3, the two parities lie in the two halves.
+//   row read: lane l reads chunk l % CR of row l / CR; a group is lanes {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} (+ 32).
+//     Fout = 64: a group holds the chunk quads {0, 3} of an even row and {1, 2} of the odd row behind it (or the other way
+//     round); r and r + 1 differ in bit 0 only, so the swizzle permutes the quads of both rows alike (bit 2 up) and
+//     chunks inside a quad (bits 0, 1): the 16 chunks stay distinct.  Fout = 32: quads {0}, {1} of rows r, r + 1 and {1},
+//     {0} of rows r + 2, r + 3 with r a multiple of 4; rows r and r + 2 share one half of the 16 chunks and bit 2 of the
+//     swizzle, so their quads stay apart.  Fout = 16: four whole rows with four different r & 3: any permutation inside a
+//     row keeps them apart.
+template <int FOUT>
+__device__ __forceinline__ int out_chunk(int r, int c) {
+  constexpr int CR = FOUT / 4;
+  const int swz = FOUT == 16 ? (r >> 1) & 3 : r & 7;
+  return r * CR + (c ^ swz);
+}
+
+// Waves per SIMD asked of the register allocator for a row-store kernel; 0 = nothing is asked (no attribute is emitted, so
+// every other kernel compiles as it did).  16 -> 32 on bf16x6 at 64 rows, 7 entries, W split in the kernel: left alone the
+// row-store form takes 61 VGPRs + 4 AGPRs = 68 against 60 + 4, i.e. 7 blocks per CU where the kernel it replaces has 8;
+// asked for 8 waves it takes 60 with the accumulator among them, no spill (profiles/rowstore_resource_usage.tsv).
+constexpr int rs_waves(bool rs, int fin, int fout, int ns, int brmin, int ge, bool pk) {
+  return rs && fin == 16 && fout == 32 && ns == 3 && brmin == 64 && ge == 7 && !pk ? 8 : 0;
+}
+
 // Which narrow forward shapes (Fin, Fout, images) run the two-round-trip prologue of the header: straight-line body,
 // unconditional bias load, W split pinned in the shadow of the first row loads.  false keeps the order the kernel had
 // (W and bias waited for and W split in front of the first index request), instruction for instruction.
@@ -113,9 +155,13 @@ constexpr bool layer_prologue(int fin, int fout, int ns) { return !(fin == 16 &&
 // raw fp32 W, no split.  false compiles to the code the kernel had.
 // ST: store mode of the epilogue (gather_rows.h, store_out): 1 = plain 16-byte stores, the code the kernel had; 3 = the same
 // addresses written through (sc1).  Narrow forward kernels on the uniform layout and a bf16 split only.
+// RS: row stores (the header, "Row stores"): the block's output leaves as whole rows through an out tile in LDS.  With
+// ST = 3 only, so in the narrow forward, where a block has one chunk (the straight-line form, and 16 -> 32 on bf16x6
+// without packed W, whose chunk loop runs once); false compiles to the code the kernel had.
 template <int FIN, int FOUT, int NS, int BRMIN, bool UNI = false, bool BWD = false, int GE = 8, int D = 1, int IM = 1,
-          bool PK = false, int ST = 1>
-__global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void k_layer(
+          bool PK = false, int ST = 1, bool RS = false>
+__global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256)))
+__attribute__((amdgpu_waves_per_eu(rs_waves(RS, FIN, FOUT, NS, BRMIN, GE, PK)))) void k_layer(
     const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ val, const float *__restrict__ x, const float *__restrict__ W,
     const float *__restrict__ bias, float *__restrict__ out, int32_t N, int64_t ldo,
@@ -125,9 +171,10 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   static_assert(IM == 1 || (IM == 2 && UNI && !BWD && FIN <= 64 && FOUT <= 64), "index records: narrow forward, uniform layout");
   static_assert(!PK || (NS > 0 && !BWD && FIN <= 64 && FOUT <= 64), "packed W: narrow forward on a bf16 split");
   static_assert(ST == 1 || (ST == 3 && UNI && NS > 0 && !BWD && FIN <= 64 && FOUT <= 64), "store modes: narrow forward, uniform layout");
+  static_assert(!RS || ST == 3, "row stores: with ST = 3 (narrow forward: one chunk per block, every thread at every barrier)");
   constexpr bool SPLIT = NS > 0;
   constexpr int NI = SPLIT ? NS : 1;
-  __shared__ __attribute__((aligned(16))) char lds_raw[C::lds_bytes];
+  __shared__ __attribute__((aligned(16))) char lds_raw[RS ? out_tile_bytes(C::lds_bytes, C::BR, FOUT) : C::lds_bytes];
   __shared__ float bred[BWD && FIN * FOUT < 128 * 128 ? 16 * 16 : 1];    // BWD, narrow: the waves' column sums of a chunk
   float *tile = reinterpret_cast<float *>(lds_raw);                      // exact: [BR][PF] fp32
   __bf16 *timg = reinterpret_cast<__bf16 *>(lds_raw);                    // split: NS images [BR][PB]
@@ -258,6 +305,56 @@ __global__ __launch_bounds__((FOUT > 128 ? 1024 : (FOUT > 64 ? 512 : 256))) void
   __syncthreads();
 
   // ---- phase 2: (tile) x (this wave's 16 columns of W^T), bias, ReLU, store ----------------------
+  if constexpr (RS) {
+    // Row stores.  The arithmetic below is the loop's further down, statement for statement; only where o goes differs.
+    constexpr int NTW = (C::NT + C::TSTEP - 1) / C::TSTEP;   // row tiles of a wave, at most
+    float4_t ot[NTW];
+#pragma unroll
+    for (int k = 0; k < NTW; ++k) {
+      const int tt = wave / C::NJ + k * C::TSTEP;
+      if (C::NT % C::TSTEP == 0 || tt < C::NT) {             // wave-uniform
+        f32x4 d = {0.f, 0.f, 0.f, 0.f};
+        const int arow = (tt * kTile + mi) * C::PB;
+#pragma unroll
+        for (int ks = 0; ks < C::KS; ++ks) {
+          using FT = typename BF<C::KF>::T;
+          FT a[NI];
+#pragma unroll
+          for (int s_ = 0; s_ < NI; ++s_)
+            a[s_] = *reinterpret_cast<const FT *>(timg + s_ * kImg + arow + C::KF * (4 * ks + mh));
+          d = gwen::mma_split<C::KF, NI>(bw[ks], a, d);
+        }
+        float4_t o = float4_t{d[0], d[1], d[2], d[3]} + bv4;
+        if (relu) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) o[t] = o[t] < 0.0f ? 0.0f : o[t];
+        }
+        ot[k] = o;
+      }
+    }
+    __syncthreads();                                         // every wave is through with the images: the out tile goes over them
+    float4_t *otile = reinterpret_cast<float4_t *>(lds_raw);   // [BR][FOUT / 4] chunks of 16 bytes, swizzled (out_chunk)
+#pragma unroll
+    for (int k = 0; k < NTW; ++k) {
+      const int tt = wave / C::NJ + k * C::TSTEP;
+      if (C::NT % C::TSTEP == 0 || tt < C::NT) otile[out_chunk<FOUT>(tt * kTile + mi, j * 4 + mh)] = ot[k];
+    }
+    __syncthreads();
+    // wave instruction i: rows i RW .. i RW + RW - 1 of the block, lane l the l-th 16 bytes of that run of rows
+    constexpr int CR = FOUT / 4, RW = 64 / CR, NINS = C::BR / RW;
+    static_assert(C::BR % RW == 0, "a block is whole runs of rows");
+    const int rr = lane / CR, rc = lane % CR;
+#pragma unroll
+    for (int i0 = 0; i0 < NINS; i0 += C::NWB) {
+      const int i = i0 + wave;
+      if (NINS % C::NWB == 0 || i < NINS) {                  // wave-uniform; no barrier follows
+        const int lr = i * RW + rr;
+        const float4_t o = otile[out_chunk<FOUT>(lr, rc)];
+        if (b0 + lr < N) gwen::store_out<3>(om + (int64_t)(b0 + lr) * ldo + rc * 4, o);
+      }
+    }
+    break;                                                   // kOnce: one chunk per block
+  }
   float4_t cs = {0.f, 0.f, 0.f, 0.f};                  // BWD + bsum_out: this lane's column sums over the wave's row tiles
 #pragma unroll
   for (int tt = wave / C::NJ; tt < C::NT; tt += C::TSTEP) {
@@ -370,13 +467,13 @@ constexpr bool rows_ok(int fin, int fout, int br, bool pk = false) {
 // call makes no HIP query, so the launchers stay capturable.  The UNIFORM kernel is probed whichever layout is launched:
 // the block-rows choice of launch() on a non-uniform layout has always been made with the uniform kernel's occupancy.
 // The index mode is part of the instantiation: a record kernel holds fewer registers.
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK, int ST = 1>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK, int ST = 1, bool RS = false>
 int resident_blocks(int64_t &resident) {
   static int per_cu = 0;
   if (per_cu == 0) {
     int nbk = 0;
     GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK, ST>),
+        &nbk, reinterpret_cast<const void *>(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK, ST, RS>),
         Cfg<FIN, FOUT, NS, BRMIN>::NWB * 64, 0));
     per_cu = nbk < 1 ? 1 : nbk;
   }
@@ -384,11 +481,11 @@ int resident_blocks(int64_t &resident) {
   return GWEN_OK;
 }
 
-template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK, int ST = 1>
+template <int FIN, int FOUT, int NS, int BRMIN, int GE, int D, int IM, bool PK, int ST = 1, bool RS = false>
 int launch_rows(const LayerArgs &a) {
   using C = Cfg<FIN, FOUT, NS, BRMIN>;
   int64_t resident = 0;
-  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM, PK, ST>(resident); if (rc != GWEN_OK) return rc; }
+  { const int rc = resident_blocks<FIN, FOUT, NS, BRMIN, GE, D, IM, PK, ST, RS>(resident); if (rc != GWEN_OK) return rc; }
   if (a.probe) { *a.probe = (int)(resident / 256); return GWEN_OK; }
   int64_t blocks = (a.N + C::BR - 1) / C::BR;
   const int64_t chunks_pm = blocks;                        // chunks of BR rows per member (bsum_out: one partial row each)
@@ -404,7 +501,7 @@ int launch_rows(const LayerArgs &a) {
   };
   if constexpr (ST != 1) {                     // store modes: the forward on the uniform layout, nothing else
     if (a.bwd || a.rowptr) return GWEN_EINVAL;
-    return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK, ST>);
+    return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, IM, PK, ST, RS>);
   } else if constexpr (IM == 2) {              // index records: the forward on the uniform layout, nothing else
     if (a.bwd || a.rowptr) return GWEN_EINVAL;
     return run(&k_layer<FIN, FOUT, NS, BRMIN, true, false, GE, D, 2, PK>);
@@ -421,7 +518,7 @@ int launch_rows(const LayerArgs &a) {
 }
 
 // block_rows: 0 = the choice below; else forced (rows_ok, checked by the extern "C" caller)
-template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1, bool PK = false, int ST = 1>
+template <int FIN, int FOUT, int NS, int GE, int D, int IM = 1, bool PK = false, int ST = 1, bool RS = false>
 int launch(const LayerArgs &a, int block_rows) {
   static_assert(GE == 8 || narrow(FIN, FOUT), "7 gathered entries: narrow layers only");
   static_assert(IM == 1 || narrow(FIN, FOUT), "index records: narrow layers only");
@@ -448,7 +545,7 @@ int launch(const LayerArgs &a, int block_rows) {
     int rc = GWEN_OK, br = block_rows;
     auto fits = [&](int c, int64_t work) {                 // the grid of c-row blocks is co-resident (or rc says why not)
       int64_t res = 0;
-      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK, ST>(res); });
+      rc = with_rows(c, [&](auto brv) { return resident_blocks<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK, ST, RS>(res); });
       return rc != GWEN_OK || (work + c - 1) / c <= res;
     };
     if (br == 0) {
@@ -462,7 +559,7 @@ int launch(const LayerArgs &a, int block_rows) {
       }
       if (rc != GWEN_OK) return rc;
     }
-    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK, ST>(a); });
+    return with_rows(br, [&](auto brv) { return launch_rows<FIN, FOUT, NS, decltype(brv)::value, GE, D, IM, PK, ST, RS>(a); });
   }
 }
 
@@ -539,6 +636,23 @@ extern "C" int gwen_gcn_layer_store_mode(int64_t Fin, int64_t Fout, int exact) {
   return layer_store_mode(Fin, Fout, gwen::images_of(exact));
 }
 
+// Whether the library's written-through epilogue leaves as whole rows through an LDS out tile (k_layer's RS) per (Fin, Fout,
+// images): on only where the launch measured faster in the step on the MI355X than the parent's launch, by more than the
+// parent's per-launch standard deviation, in both of two profiled pairs ("Stores"; profiles/rowstore_*).
+// Only bf16x6 with one member was measured.  Read only where the resolved store mode is 3.
+// 32 -> 64 (11.23 -> 10.69 and 11.25 -> 10.75 us, parent's sd 0.29 / 0.32) and 16 -> 32 (6.68 -> 6.06 and 6.70 -> 6.05, sd 0.32 /
+// 0.38) switch.  64 -> 64 does not: 13.43 -> 13.54 and 13.59 -> 13.61 -- five D tiles held over two barriers gain nothing at 80 rows.
+static constexpr bool layer_row_stores(int64_t fin, int64_t fout, int ns) {
+  return ns == 3 && ((fin == 32 && fout == 64) || (fin == 16 && fout == 32));
+}
+
+extern "C" int gwen_gcn_layer_row_stores(int64_t Fin, int64_t Fout, int exact) {
+  if (!gwen_gcn_layer_supported(Fin, Fout) || exact < 0 || exact > 2) return 0;
+  if (!narrow(Fin, Fout) || gwen::images_of(exact) == 0) return 1;
+  const int ns = gwen::images_of(exact);
+  return layer_store_mode(Fin, Fout, ns) == 3 && layer_row_stores(Fin, Fout, ns) ? 2 : 1;
+}
+
 // entries = 7: a promise of the caller (uniform layout, every row at most 7 stored entries) that the narrow
 // kernels turn into one gather less per row; every other shape and layout gathers whole groups.
 // depth, block_rows, index_mode: 0 = the library's choice (layer_depth; the co-resident grid of launch();
@@ -549,7 +663,11 @@ extern "C" int gwen_gcn_layer_store_mode(int64_t Fin, int64_t Fout, int exact) {
 // 0: the library's choice -- the images where they are given and gwen_gcn_layer_packed_mode says 2.  No value changes.
 // store_mode: 0 = the library's choice (layer_store_mode, one member only); 1 = plain stores; 3 = the same stores written
 // through -- narrow layers on a bf16 split, on the uniform layout, at the library's depth and index mode for the shape,
-// GWEN_EINVAL elsewhere; 2 and 4 (whole-row stores through LDS) are not built: GWEN_EINVAL.  No value changes.
+// GWEN_EINVAL elsewhere; 2 and 4 are reserved numbers: GWEN_EINVAL.  No value changes.
+// row_stores: how the written-through tile leaves (k_layer's RS).  1 = as the MFMA holds it, 16 rows x 64 B per wave
+// instruction; 2 = as whole rows through an LDS out tile -- only where mode 3 is admitted and the resolved store mode is 3,
+// GWEN_EINVAL elsewhere; 0 = the library's choice (layer_row_stores, one member and a resolved store mode of 3 only).  No
+// value changes.
 // probe: not NULL = launch nothing and store the blocks per CU that hipOccupancyMaxActiveBlocksPerMultiprocessor reports for
 // the kernel this call would launch (the uniform-layout kernel, as resident_blocks has always asked)
 static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -557,21 +675,25 @@ static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *v
                        int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
                        int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
                        int exact, int entries, int depth, int block_rows, int index_mode,
-                       const void *Wp, int packed, int store_mode, gwen_stream_t stream_, int *probe) {
+                       const void *Wp, int packed, int store_mode, int row_stores, gwen_stream_t stream_, int *probe) {
   if (entries != 7 && entries != 8) return GWEN_EINVAL;
   if (store_mode < 0 || store_mode > 4) return GWEN_EINVAL;
+  if (row_stores < 0 || row_stores > 2) return GWEN_EINVAL;
   if (packed < 0 || packed > 2) return GWEN_EINVAL;
   if (depth < 0 || depth > 2) return GWEN_EINVAL;
   if (index_mode < 0 || index_mode > 2) return GWEN_EINVAL;
   if (N < 0 || members < 0 || ldx < Fin || ldo < Fout || exact < 0 || exact > 2) return GWEN_EINVAL;
   if (!gwen_gcn_layer_supported(Fin, Fout)) return GWEN_EINVAL;
   if (index_mode == 2 && (rowptr || !narrow(Fin, Fout))) return GWEN_EINVAL;    // records: uniform layout, narrow layers
-  // store modes: narrow layers on a bf16 split, uniform layout, the shape's own depth and index mode; row stores: not built
+  // store modes: narrow layers on a bf16 split, uniform layout, the shape's own depth and index mode; 2 and 4: reserved
   const bool can_store = narrow(Fin, Fout) && gwen::images_of(exact) > 0 && !rowptr &&
                          (depth == 0 || depth == gwen_gcn_layer_depth(Fin, Fout, exact)) &&
                          (index_mode == 0 || index_mode == gwen_gcn_layer_index_mode(Fin, Fout, exact));
   if (store_mode > 1 && (!can_store || store_mode != 3)) return GWEN_EINVAL;
   if (store_mode == 0) store_mode = can_store && members == 1 ? gwen_gcn_layer_store_mode(Fin, Fout, exact) : 1;
+  if (row_stores == 2 && store_mode != 3) return GWEN_EINVAL;                   // row stores: the written-through kernels only
+  if (row_stores == 0)
+    row_stores = store_mode == 3 && members == 1 && layer_row_stores(Fin, Fout, gwen::images_of(exact)) ? 2 : 1;
   const bool can_pack = narrow(Fin, Fout) && gwen::images_of(exact) > 0;        // packed W: narrow layers, bf16 splits
   if (packed == 2 && (!can_pack || !Wp)) return GWEN_EINVAL;
   if (packed == 0) packed = Wp && can_pack && gwen_gcn_layer_packed_mode(Fin, Fout, exact) == 2 ? 2 : 1;
@@ -602,7 +724,9 @@ static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *v
               if constexpr (!PK || NS > 0) {
                 // the written-through kernels: at the depth and index mode the library launches for the shape
                 if constexpr (NS > 0 && D == layer_depth(FI, FO, NS) && IM == layer_index_mode(FI, FO, NS)) {
-                  if (store_mode == 3) return launch<FI, FO, NS, GE, D, IM, PK, 3>(a, block_rows);
+                  if (store_mode == 3)
+                    return row_stores == 2 ? launch<FI, FO, NS, GE, D, IM, PK, 3, true>(a, block_rows)
+                                           : launch<FI, FO, NS, GE, D, IM, PK, 3>(a, block_rows);
                 }
                 return store_mode == 1 ? launch<FI, FO, NS, GE, D, IM, PK>(a, block_rows) : (int)GWEN_EINVAL;
               } else {
@@ -618,14 +742,24 @@ static int layer_tuned(const int32_t *rowptr, const int32_t *col, const float *v
   });
 }
 
+extern "C" int gwen_gcn_layer_tuned5_f32(const int32_t *rowptr, const int32_t *col, const float *val,
+                                         const float *x, const float *W, const float *bias, float *out,
+                                         int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
+                                         int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
+                                         int exact, int entries, int depth, int block_rows, int index_mode,
+                                         const void *Wp, int packed, gwen_stream_t stream_, int store_mode, int row_stores) {
+  return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
+                     entries, depth, block_rows, index_mode, Wp, packed, store_mode, row_stores, stream_, nullptr);
+}
+
 extern "C" int gwen_gcn_layer_tuned4_f32(const int32_t *rowptr, const int32_t *col, const float *val,
                                          const float *x, const float *W, const float *bias, float *out,
                                          int64_t N, int64_t Fin, int64_t Fout, int64_t ldx, int64_t ldo,
                                          int64_t members, int64_t mstride_x, int64_t mstride_o, int relu,
                                          int exact, int entries, int depth, int block_rows, int index_mode,
                                          const void *Wp, int packed, gwen_stream_t stream_, int store_mode) {
-  return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
-                     entries, depth, block_rows, index_mode, Wp, packed, store_mode, stream_, nullptr);
+  return gwen_gcn_layer_tuned5_f32(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o,
+                                   relu, exact, entries, depth, block_rows, index_mode, Wp, packed, stream_, store_mode, 0);
 }
 
 extern "C" int gwen_gcn_layer_tuned3_f32(const int32_t *rowptr, const int32_t *col, const float *val,
@@ -646,7 +780,7 @@ extern "C" int gwen_gcn_layer_blocks_per_cu(const int32_t *rowptr, const int32_t
                                             const void *Wp, int packed, int *blocks_per_cu) {
   if (!blocks_per_cu || N <= 0 || members <= 0) return GWEN_EINVAL;
   return layer_tuned(rowptr, col, val, x, W, bias, out, N, Fin, Fout, ldx, ldo, members, mstride_x, mstride_o, relu, exact,
-                     entries, depth, block_rows, index_mode, Wp, packed, 0, nullptr, blocks_per_cu);
+                     entries, depth, block_rows, index_mode, Wp, packed, 0, 0, nullptr, blocks_per_cu);
 }
 
 extern "C" int gwen_gcn_layer_tuned2_f32(const int32_t *rowptr, const int32_t *col, const float *val,

@@ -191,14 +191,16 @@ def layer_supported(fin: int, fout: int) -> bool:
 
 def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
                 relu: bool = False, exact: bool = False, contract: Optional[str] = None,
-                depth: int = 0, block_rows: int = 0, index_mode: int = 0, store_mode: int = 0) -> Tensor:
+                depth: int = 0, block_rows: int = 0, index_mode: int = 0, store_mode: int = 0,
+                row_stores: int = 0) -> Tensor:
     """K4: act((A~ x) W^T + b) in one launch (widths in {16,32,64,128,256}).  ``contract``: "bf16x6", "3xbf16" or
     "fp32"; when None, ``exact`` picks between "fp32" (True) and "3xbf16" (False).  ``depth`` (gather passes in
     flight per wave: 1 or 2) and ``block_rows`` (64 / 96 / 112 / 128 where the widths allow) are scheduling choices
     that change no value; 0 = the library's.  So is ``index_mode`` (1: every lane loads its row's indices and weights;
     2: one record load per row, broadcast in the lane group -- widths up to 64 on a uniform layout only)
     and ``store_mode`` (1: plain output stores; 3: the same stores written through -- widths up to 64 on a bf16 split and a
-    uniform layout only; 2 and 4 are reserved) (gwen_gcn_layer_tuned4_f32)."""
+    uniform layout only; 2 and 4 are reserved) and ``row_stores`` (1: the written-through tile leaves as the MFMA holds it;
+    2: as whole rows through an LDS out tile -- only where the store mode is 3) (gwen_gcn_layer_tuned5_f32)."""
     _require(x, "x")
     _require(weight, "weight")
     x = x.contiguous()
@@ -217,12 +219,12 @@ def layer_fused(graph: GraphCSR, x: Tensor, weight: Tensor, bias: Optional[Tenso
     dev = x.device
     g_rowptr, g_col, g_val = graph.grouped()
     with torch.cuda.device(dev):
-        rc = _lib.lib().gwen_gcn_layer_tuned4_f32(
+        rc = _lib.lib().gwen_gcn_layer_tuned5_f32(
             _ptr(g_rowptr), _ptr(g_col), _ptr(g_val), _ptr(x), _ptr(weight), _ptr(bias),
             _ptr(out), n, fin, fout, fin, fout, m, n_src * fin, n * fout, int(relu),
             _dense_code(contract, exact), graph.entries(), int(depth), int(block_rows), int(index_mode), None, 0,
-            _stream(dev), int(store_mode))
-    _lib.check(rc, "gwen_gcn_layer_tuned4_f32")
+            _stream(dev), int(store_mode), int(row_stores))
+    _lib.check(rc, "gwen_gcn_layer_tuned5_f32")
     return out
 
 

@@ -306,6 +306,23 @@ int gwen_gcn_layer_tuned4_f32(const int32_t *rowptr, const int32_t *col, const f
 /* what store_mode = 0 runs on a uniform layout with one member: 1 .. 4, and 1 wherever the modes do not exist
  * (0: unsupported widths / exact) */
 int gwen_gcn_layer_store_mode(int64_t Fin, int64_t Fout, int exact);
+/* gwen_gcn_layer_tuned4_f32 with the row layout of the written-through epilogue: a sixth choice that CHANGES NO VALUE;
+ * gwen_gcn_layer_tuned4_f32 forwards with 0 and keeps its store_mode's meaning and refusals (2 and 4 stay reserved).
+ * row_stores: 1 = the result tile leaves as the MFMA holds it (16 rows x 64 B per wave instruction); 2 = it leaves as
+ *   WHOLE ROWS through an fp32 out tile in LDS (one run of 1024 / (4 Fout) consecutive rows per wave instruction: one
+ *   contiguous KiB where ldo == Fout; columns Fout .. ldo - 1 and rows >= N are never written) -- only where store mode 3
+ *   is admitted and the resolved store mode is 3; elsewhere GWEN_EINVAL.  0 = the library's choice
+ *   (gwen_gcn_layer_row_stores, with one member and a resolved store mode of 3; 1 otherwise).  Outside 0..2: GWEN_EINVAL.
+ *   All of these are refused before any HIP call. */
+int gwen_gcn_layer_tuned5_f32(const int32_t *rowptr, const int32_t *col, const float *val, const float *x,
+                              const float *W, const float *bias, float *out, int64_t N, int64_t Fin,
+                              int64_t Fout, int64_t ldx, int64_t ldo, int64_t members, int64_t mstride_x,
+                              int64_t mstride_o, int relu, int exact, int entries, int depth, int block_rows,
+                              int index_mode, const void *Wp, int packed, gwen_stream_t stream, int store_mode,
+                              int row_stores);
+/* what row_stores = 0 runs on a uniform layout with one member where store_mode = 0 runs mode 3: 1 or 2, and 1 wherever
+ * row stores do not exist or the library's store mode is not 3 (0: unsupported widths / exact) */
+int gwen_gcn_layer_row_stores(int64_t Fin, int64_t Fout, int exact);
 
 /* ---------------------------------------------------------------------------------------------
  * K8  K4's contract for WIDE layers on locality-ordered bounded-degree graphs (meshes), tile-staged:
