@@ -16,13 +16,17 @@
 //
 // With longitude = GWEN_SHT_LON_FFT (gwen_sht_transform) the two longitude kernels are k_sht_lon_fft_fwd and
 // k_sht_lon_fft_inv of sht_fft.h, one fp64 FFT a ring and channel in LDS: the same ring, the same numbers up to rounding.
-// lon_fwd() and lon_inv() below are the one place where the four launchers choose.
+// lon_fwd() and lon_inv() below are the one place where the launchers choose.
 //
 // On a reduced Gaussian grid (gwen_sht_rings_transform: a ring length of its own on every latitude) they are
-// k_sht_rings_lon_fwd and k_sht_rings_lon_inv ("reduced grids" below): the same direct sums, one ring a block.
+// k_sht_rings_lon_fwd and k_sht_rings_lon_inv ("reduced grids" below): the direct sums of the regular grid -- lon_sums()
+// and lon_synthesis(), the one copy of either loop -- one ring a block.
 //
 // The vector transforms, (u, v) <-> (vort, div), run the same longitude kernels on u and on v (ring [2, chunk, ...]) and
-// two latitude kernels of their own, k_vsht_lat_fwd and k_vsht_lat_inv ("vector harmonics" below).
+// the latitude kernels k_vsht_lat_fwd and k_vsht_lat_inv, with two Legendre tables and four columns where the scalar
+// ones have one and two ("the latitude stage" below).  The two inverse kernels are one body, lat_inv<V>.  The two forward
+// kernels call the same block decode, seed, coefficient staging and tile index and keep a body each: as one templated
+// body k_vsht_lat_fwd measured 2 - 4 % slower (DESIGN, "Spherical harmonics", the refactor's A/B).
 #include "common.h"
 #include "sht_fft.h"
 
@@ -51,16 +55,62 @@ __device__ __forceinline__ double powi(double c, int m) {
   return r;
 }
 
-// a, b of Pbar_l^m = a (mu Pbar_{l-1}^m - b Pbar_{l-2}^m), l > m (l = m + 1: a = sqrt(2m + 3), b = 0)
-__device__ __forceinline__ void recurrence_coefficients(int l, int m, double &a, double &b) {
-  const double dl = (double)l, dm = (double)m, dl1 = (double)(l - 1);
-  a = sqrt((4.0 * dl * dl - 1.0) / (dl * dl - dm * dm));
-  b = sqrt((dl1 * dl1 - dm * dm) / (4.0 * dl1 * dl1 - 1.0));
+// ---- the longitude stage: direct sums ---------------------------------------------------------------------------------
+// A lane owns one (ring, channel) row of x and a wave 16 orders m (forward) or 16 longitudes i (inverse): their table
+// steps, the table indices (m i) mod nlon and the twiddles are wave-uniform (scalar registers, scalar loads), and the
+// vector unit issues little but the 32 fma of a longitude (order).  The two loops below are what the regular and the
+// reduced grid share, so rings of one length give the bits of the regular grid; who shares a wave is the kernels' own.
+
+// (ac, as)[k] = sum_i xp[i C] (cos, sin)(2 pi step[k] i / nlon), i ascending; tw is the ring's table
+template <typename TIn>
+__device__ __forceinline__ void lon_sums(const TIn *xp, const dpair *tw, int nlon, int C, const int (&step)[kLonK],
+                                         double (&ac)[kLonK], double (&as)[kLonK]) {
+  int idx[kLonK];
+#pragma unroll
+  for (int k = 0; k < kLonK; ++k) {
+    idx[k] = 0;
+    ac[k] = 0.0;
+    as[k] = 0.0;
+  }
+#pragma unroll 2
+  for (int i = 0; i < nlon; ++i) {
+    const double xv = (double)xp[(int64_t)i * C];
+#pragma unroll
+    for (int k = 0; k < kLonK; ++k) {
+      const dpair t = tw[idx[k]];
+      ac[k] = fma(xv, t.x, ac[k]);
+      as[k] = fma(xv, t.y, as[k]);
+      idx[k] += step[k];
+      if (idx[k] >= nlon) idx[k] -= nlon;
+    }
+  }
 }
 
-// The longitude sums.  A lane owns one (ring, channel) row of x -- rows run over (item, latitude, channel), so every lane
-// works whatever C is -- and a wave owns 16 orders m: the orders, their table indices (m i) mod nlon and the twiddles are
-// wave-uniform (scalar registers, scalar loads), and the vector unit issues little but the 32 fma of a longitude.
+// acc[k] = sum_{m <= M} gp[m C] cos(2 pi m step[k] / nlon) + gp[-m C] sin(...), m ascending; gp is column 0 of a ring row
+__device__ __forceinline__ void lon_synthesis(const double *gp, const dpair *tw, int nlon, int M, int C,
+                                              const int (&step)[kLonK], double (&acc)[kLonK]) {
+  int idx[kLonK];
+#pragma unroll
+  for (int k = 0; k < kLonK; ++k) {
+    idx[k] = 0;
+    acc[k] = 0.0;
+  }
+#pragma unroll 2
+  for (int m = 0; m <= M; ++m) {
+    const double gc = gp[(int64_t)m * C];
+    const double gs = m ? gp[-(int64_t)m * C] : 0.0;
+#pragma unroll
+    for (int k = 0; k < kLonK; ++k) {
+      const dpair w = tw[idx[k]];
+      acc[k] = fma(gc, w.x, acc[k]);
+      acc[k] = fma(gs, w.y, acc[k]);
+      idx[k] += step[k];
+      if (idx[k] >= nlon) idx[k] -= nlon;
+    }
+  }
+}
+
+// Rows run over (item, latitude, channel), so every lane works whatever C is.
 template <typename TIn>
 __global__ __launch_bounds__(kThreads) void k_sht_lon_fwd(const TIn *__restrict__ x, const dpair *__restrict__ tw,
                                                           double *__restrict__ ring, int64_t rows, int nlon, int L, int C,
@@ -73,28 +123,11 @@ __global__ __launch_bounds__(kThreads) void k_sht_lon_fwd(const TIn *__restrict_
   const int c = (int)(rr - row * C);
   const int m0 = __builtin_amdgcn_readfirstlane((mt * 4 + wave) * kLonK);
   if (m0 > L) return;
-  int mk[kLonK], idx[kLonK];
+  int mk[kLonK];
   double ac[kLonK], as[kLonK];
 #pragma unroll
-  for (int k = 0; k < kLonK; ++k) {
-    mk[k] = m0 + k <= L ? m0 + k : 0;                     // an order past lmax walks order 0 and is not stored
-    idx[k] = 0;
-    ac[k] = 0.0;
-    as[k] = 0.0;
-  }
-  const TIn *xp = x + row * (int64_t)nlon * C + c;
-#pragma unroll 2
-  for (int i = 0; i < nlon; ++i) {
-    const double xv = (double)xp[(int64_t)i * C];
-#pragma unroll
-    for (int k = 0; k < kLonK; ++k) {
-      const dpair t = tw[idx[k]];
-      ac[k] = fma(xv, t.x, ac[k]);
-      as[k] = fma(xv, t.y, as[k]);
-      idx[k] += mk[k];
-      if (idx[k] >= nlon) idx[k] -= nlon;
-    }
-  }
+  for (int k = 0; k < kLonK; ++k) mk[k] = m0 + k <= L ? m0 + k : 0;   // past lmax: walks order 0, is not stored
+  lon_sums(x + row * (int64_t)nlon * C + c, tw, nlon, C, mk, ac, as);
   if (r >= rows) return;
   double *out = ring + (row * (int64_t)(2 * L + 1) + L) * C + c;
 #pragma unroll
@@ -106,179 +139,6 @@ __global__ __launch_bounds__(kThreads) void k_sht_lon_fwd(const TIn *__restrict_
   }
 }
 
-// Block (item, channel tile, order m): all latitudes, all degrees l >= m.  Dynamic LDS: two recurrence values per
-// latitude, the Legendre tile (column (j + l) & 63: conflict-free for the writer's 64 latitudes and for the readers' 4
-// degrees a wave), the ring tile and the recurrence coefficients of the tile's degrees.
-template <typename TOut>
-__global__ __launch_bounds__(kThreads) void k_sht_lat_fwd(const double *__restrict__ ring, const dpair *__restrict__ nodes,
-                                                          const double *__restrict__ lat_w,
-                                                          const double *__restrict__ seed, TOut *__restrict__ coef,
-                                                          int nlat, int L, int C, int ctiles) {
-  extern __shared__ double smem[];
-  double *st1 = smem;                                     // [nlat]  Pbar_{l-1}^m at the start of a degree tile
-  double *st2 = st1 + nlat;                               // [nlat]  Pbar_{l-2}^m
-  double *pt = st2 + nlat;                                // [kLT][kJT]
-  double *ft = pt + kLT * kJT;                            // [kJT][2][kCT]
-  double *ca = ft + kJT * 2 * kCT;                        // [kLT]
-  double *cb = ca + kLT;                                  // [kLT]
-  const int tid = threadIdx.x, cl = tid & (kCT - 1), lg = tid >> 4;
-  int64_t blk = blockIdx.x;
-  const int m = (int)(blk % (L + 1));
-  blk /= (L + 1);
-  const int ct = (int)(blk % ctiles);
-  const int64_t item = blk / ctiles;
-  const int c = ct * kCT + cl;
-  const int64_t T = (int64_t)(L + 1) * (L + 1);
-  const double sm = seed[m];
-  for (int j = tid; j < nlat; j += kThreads) {
-    st1[j] = sm * powi(nodes[j].y, m);
-    st2[j] = 0.0;
-  }
-  const double *fr = ring + item * (int64_t)nlat * (2 * L + 1) * C;
-  for (int l0 = m; l0 <= L; l0 += kLT) {
-    const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
-    __syncthreads();                                      // the tile before is done with ca, cb (and st1, st2 are set)
-    if (tid < nl && l0 + tid > m) {
-      double a, b;
-      recurrence_coefficients(l0 + tid, m, a, b);
-      ca[tid] = a;
-      cb[tid] = b;
-    }
-    double acc[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-    for (int j0 = 0; j0 < nlat; j0 += kJT) {
-      __syncthreads();
-      if (tid < kJT) {
-        const int j = j0 + tid;
-        if (j < nlat) {
-          double p1 = st1[j], p2 = st2[j];
-          const double mu = nodes[j].x, w = lat_w ? lat_w[j] : 1.0;
-          for (int t = 0; t < nl; ++t) {
-            if (l0 + t > m) {
-              const double p = ca[t] * (mu * p1 - cb[t] * p2);
-              p2 = p1;
-              p1 = p;
-            }
-            pt[t * kJT + ((tid + t) & (kJT - 1))] = p1 * w;
-          }
-          st1[j] = p1;
-          st2[j] = p2;
-        } else {
-          for (int t = 0; t < nl; ++t) pt[t * kJT + ((tid + t) & (kJT - 1))] = 0.0;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < kJT * 2 * kCT / kThreads; ++r) {
-        const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 1, jj = e >> 5;
-        const int j = j0 + jj, gc = ct * kCT + cc;
-        ft[e] = j < nlat && gc < C ? fr[((int64_t)j * (2 * L + 1) + (kk ? L - m : L + m)) * C + gc] : 0.0;
-      }
-      __syncthreads();
-      const int nj = nlat - j0 < kJT ? nlat - j0 : kJT;
-      for (int jj = 0; jj < nj; ++jj) {
-        const double fc = ft[(jj * 2 + 0) * kCT + cl], fs = ft[(jj * 2 + 1) * kCT + cl];
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-          const int t = lg + 16 * r;
-          const double p = t < nl ? pt[t * kJT + ((jj + t) & (kJT - 1))] : 0.0;
-          acc[r][0] = fma(p, fc, acc[r][0]);
-          acc[r][1] = fma(p, fs, acc[r][1]);
-        }
-      }
-    }
-    if (c < C) {
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const int l = l0 + lg + 16 * r;
-        if (l > L) continue;
-        TOut *o = coef + (item * T + (int64_t)l * l + l) * C + c;
-        o[(int64_t)m * C] = (TOut)acc[r][0];
-        if (m > 0) o[-(int64_t)m * C] = (TOut)acc[r][1];
-      }
-    }
-  }
-}
-
-// Block (item, channel tile, order m, 64 latitudes): the recurrence lives in the registers of the block's first 64
-// threads; thread (channel, 4 latitudes) sums over the degrees.
-template <typename TIn>
-__global__ __launch_bounds__(kThreads) void k_sht_lat_inv(const TIn *__restrict__ coef, const dpair *__restrict__ nodes,
-                                                          const double *__restrict__ seed, double *__restrict__ ring,
-                                                          int nlat, int L, int C, int ctiles, int jtiles) {
-  __shared__ double pt[kLT * kJT];
-  __shared__ double ctile[kLT * 2 * kCT];
-  __shared__ double ca[kLT], cb[kLT];
-  const int tid = threadIdx.x, cl = tid & (kCT - 1), jg = tid >> 4;
-  int64_t blk = blockIdx.x;
-  const int jt = (int)(blk % jtiles);
-  blk /= jtiles;
-  const int m = (int)(blk % (L + 1));
-  blk /= (L + 1);
-  const int ct = (int)(blk % ctiles);
-  const int64_t item = blk / ctiles;
-  const int c = ct * kCT + cl;
-  const int64_t T = (int64_t)(L + 1) * (L + 1);
-  const int j0 = jt * kJT;
-  const int jmine = j0 + tid;
-  double p1 = 0.0, p2 = 0.0, mu = 0.0;
-  if (tid < kJT && jmine < nlat) {
-    p1 = seed[m] * powi(nodes[jmine].y, m);
-    mu = nodes[jmine].x;
-  }
-  double acc[4][2];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r][0] = acc[r][1] = 0.0;
-  const TIn *cf = coef + item * T * C;
-  for (int l0 = m; l0 <= L; l0 += kLT) {
-    const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
-    __syncthreads();
-    if (tid < nl && l0 + tid > m) {
-      double a, b;
-      recurrence_coefficients(l0 + tid, m, a, b);
-      ca[tid] = a;
-      cb[tid] = b;
-    }
-#pragma unroll
-    for (int r = 0; r < kLT * 2 * kCT / kThreads; ++r) {
-      const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 1, t = e >> 5;
-      const int l = l0 + t, gc = ct * kCT + cc;
-      ctile[e] = l <= L && gc < C && !(kk && m == 0)
-                     ? (double)cf[((int64_t)l * l + l + (kk ? -m : m)) * C + gc] : 0.0;
-    }
-    __syncthreads();
-    if (tid < kJT) {
-      for (int t = 0; t < nl; ++t) {
-        if (l0 + t > m) {
-          const double p = ca[t] * (mu * p1 - cb[t] * p2);
-          p2 = p1;
-          p1 = p;
-        }
-        pt[t * kJT + ((tid + t) & (kJT - 1))] = p1;
-      }
-    }
-    __syncthreads();
-    for (int t = 0; t < nl; ++t) {
-      const double cc_ = ctile[(t * 2 + 0) * kCT + cl], cs = ctile[(t * 2 + 1) * kCT + cl];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const double p = pt[t * kJT + ((jg + 16 * r + t) & (kJT - 1))];
-        acc[r][0] = fma(p, cc_, acc[r][0]);
-        acc[r][1] = fma(p, cs, acc[r][1]);
-      }
-    }
-  }
-  if (c >= C) return;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int j = j0 + jg + 16 * r;
-    if (j >= nlat) continue;
-    double *o = ring + ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
-    o[(int64_t)m * C] = acc[r][0];
-    if (m > 0) o[-(int64_t)m * C] = acc[r][1];
-  }
-}
-
-// The longitude synthesis, the same way round: a lane owns one (ring, channel) row, a wave 16 longitudes (wave-uniform
-// table indices and twiddles), and every lane sums over the orders.
 template <typename TOut>
 __global__ __launch_bounds__(kThreads) void k_sht_lon_inv(const double *__restrict__ ring, const dpair *__restrict__ tw,
                                                           const double *__restrict__ lat_w, TOut *__restrict__ x,
@@ -291,28 +151,11 @@ __global__ __launch_bounds__(kThreads) void k_sht_lon_inv(const double *__restri
   const int c = (int)(rr - row * C);
   const int i0 = __builtin_amdgcn_readfirstlane((it * 4 + wave) * kLonK);
   if (i0 >= nlon) return;
-  int step[kLonK], idx[kLonK];
+  int step[kLonK];
   double acc[kLonK];
 #pragma unroll
-  for (int k = 0; k < kLonK; ++k) {
-    step[k] = i0 + k < nlon ? i0 + k : 0;
-    idx[k] = 0;
-    acc[k] = 0.0;
-  }
-  const double *gp = ring + (row * (int64_t)(2 * L + 1) + L) * C + c;
-#pragma unroll 2
-  for (int m = 0; m <= L; ++m) {
-    const double gc = gp[(int64_t)m * C];
-    const double gs = m ? gp[-(int64_t)m * C] : 0.0;
-#pragma unroll
-    for (int k = 0; k < kLonK; ++k) {
-      const dpair w = tw[idx[k]];
-      acc[k] = fma(gc, w.x, acc[k]);
-      acc[k] = fma(gs, w.y, acc[k]);
-      idx[k] += step[k];
-      if (idx[k] >= nlon) idx[k] -= nlon;
-    }
-  }
+  for (int k = 0; k < kLonK; ++k) step[k] = i0 + k < nlon ? i0 + k : 0;
+  lon_synthesis(ring + (row * (int64_t)(2 * L + 1) + L) * C + c, tw, nlon, L, C, step, acc);
   if (r >= rows) return;
   const double w = lat_w ? lat_w[row % nlat] : 1.0;
   TOut *xo = x + row * (int64_t)nlon * C + c;
@@ -324,12 +167,11 @@ __global__ __launch_bounds__(kThreads) void k_sht_lon_inv(const double *__restri
 // ---- reduced grids: rings of unequal length (gwen_sht_rings_transform) ----------------------------------------------
 // Ring j holds ring_nlon[j] longitudes 2 pi i / ring_nlon[j], the rows ring_start[j] ... of an item's P points, and
 // carries the orders m <= M_j = min(lmax, (ring_nlon[j] - 1) / 2); tw is one table a ring, end to end, tw[ring_start[j] +
-// i] = (cos, sin)(2 pi i / ring_nlon[j]).  The sums are those of k_sht_lon_fwd and k_sht_lon_inv term for term -- one
-// thread's fma chain in ascending i or m, the table index stepping by (idx += m) mod ring_nlon[j] -- so rings of one
-// length give the bits of the regular grid.  What changes is who shares a wave: a block owns one ring, 64 (item, channel)
-// lanes and 64 orders (longitudes), so the ring's length, start and M_j are block-uniform and the table indices and
-// twiddles stay in scalar registers.  The forward kernel stores zeros in the columns of the orders above M_j (the
-// latitude kernels read every column, and the workspace arrives uninitialised); the inverse kernel does not read them.
+// i] = (cos, sin)(2 pi i / ring_nlon[j]).  The sums are lon_sums() and lon_synthesis().  What changes is who shares a
+// wave: a block owns one ring, 64 (item, channel) lanes and 64 orders (longitudes), so the ring's length, start and M_j
+// are block-uniform and the table indices and twiddles stay in scalar registers.  The forward kernel stores zeros in the
+// columns of the orders above M_j (the latitude kernels read every column, and the workspace arrives uninitialised); the
+// inverse kernel does not read them.
 
 // The ring of the b-th row of blocks: from the equator outwards, nlat / 2, nlat / 2 - 1, nlat / 2 + 1, ...  On a reduced
 // Gaussian grid that is the longest rings first, so the short polar rings fill the tail of the launch.
@@ -370,30 +212,12 @@ __global__ __launch_bounds__(kThreads) void k_sht_rings_lon_fwd(const TIn *__res
     }
     return;
   }
-  int mk[kLonK], idx[kLonK];
+  int mk[kLonK];
   double ac[kLonK], as[kLonK];
 #pragma unroll
-  for (int k = 0; k < kLonK; ++k) {
-    mk[k] = m0 + k <= M ? m0 + k : 0;                     // an order past M_j walks order 0 and is stored as zero
-    idx[k] = 0;
-    ac[k] = 0.0;
-    as[k] = 0.0;
-  }
+  for (int k = 0; k < kLonK; ++k) mk[k] = m0 + k <= M ? m0 + k : 0;   // past M_j: walks order 0, is stored as zero
   const int64_t start = ring_start[j];
-  const dpair *twj = tw + start;
-  const TIn *xp = x + (item * P + start) * C + c;
-#pragma unroll 2
-  for (int i = 0; i < nlon; ++i) {
-    const double xv = (double)xp[(int64_t)i * C];
-#pragma unroll
-    for (int k = 0; k < kLonK; ++k) {
-      const dpair t = twj[idx[k]];
-      ac[k] = fma(xv, t.x, ac[k]);
-      as[k] = fma(xv, t.y, as[k]);
-      idx[k] += mk[k];
-      if (idx[k] >= nlon) idx[k] -= nlon;
-    }
-  }
+  lon_sums(x + (item * P + start) * C + c, tw + start, nlon, C, mk, ac, as);
   if (q >= lanes) return;
 #pragma unroll
   for (int k = 0; k < kLonK; ++k) {
@@ -426,30 +250,12 @@ __global__ __launch_bounds__(kThreads) void k_sht_rings_lon_inv(const double *__
   const int64_t qq = q < lanes ? q : lanes - 1;
   const int64_t item = qq / C;
   const int c = (int)(qq - item * C);
-  int step[kLonK], idx[kLonK];
+  int step[kLonK];
   double acc[kLonK];
 #pragma unroll
-  for (int k = 0; k < kLonK; ++k) {
-    step[k] = i0 + k < nlon ? i0 + k : 0;
-    idx[k] = 0;
-    acc[k] = 0.0;
-  }
+  for (int k = 0; k < kLonK; ++k) step[k] = i0 + k < nlon ? i0 + k : 0;
   const int64_t start = ring_start[j];
-  const dpair *twj = tw + start;
-  const double *gp = ring + ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
-#pragma unroll 2
-  for (int m = 0; m <= M; ++m) {
-    const double gc = gp[(int64_t)m * C];
-    const double gs = m ? gp[-(int64_t)m * C] : 0.0;
-#pragma unroll
-    for (int k = 0; k < kLonK; ++k) {
-      const dpair w = twj[idx[k]];
-      acc[k] = fma(gc, w.x, acc[k]);
-      acc[k] = fma(gs, w.y, acc[k]);
-      idx[k] += step[k];
-      if (idx[k] >= nlon) idx[k] -= nlon;
-    }
-  }
+  lon_synthesis(ring + ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c, tw + start, nlon, M, C, step, acc);
   if (q >= lanes) return;
   const double w = lat_w ? lat_w[j] : 1.0;
   TOut *xo = x + (item * P + start) * C + c;
@@ -476,24 +282,73 @@ __global__ __launch_bounds__(kThreads) void k_sht_power(const double *__restrict
   power[e] = s;
 }
 
-// ---- vector harmonics: (u, v) <-> (vort, div) -------------------------------------------------------------------------
-// grad Y of the cos row (l, m >= 0) is (east, north) = (-m Q sin m lon, D cos m lon), of the sin row (l, -m) it is
-// (m Q cos m lon, D sin m lon), with Q = Pbar_l^m / cos lat and D = d Pbar_l^m / d lat; k x grad Y = (-north, east).
-// Neither table divides by cos lat.  For m >= 1 the block walks Q_l^m, the recurrence of Pbar_l^m seeded one cosine short
-// (seed[m] cos^(m-1) lat), and D_l^m = c_d Q_{l-1}^m - l sin lat Q_l^m.  For m = 0 the Q term carries the factor m = 0
-// and D_l^0 = c_d Pbar_l^1, so the block walks the order-1 recurrence from l = 1.  Either way one recurrence a latitude.
+// ---- the latitude stage, scalar (V = false) or vector (V = true) -----------------------------------------------------
+// Scalar: the table is Pbar_l^m, the columns are the cos and the sin sums (coefficients) of order m.
+//
+// Vector, (u, v) <-> (vort, div): grad Y of the cos row (l, m >= 0) is (east, north) = (-m Q sin m lon, D cos m lon), of
+// the sin row (l, -m) it is (m Q cos m lon, D sin m lon), with Q = Pbar_l^m / cos lat and D = d Pbar_l^m / d lat; k x grad
+// Y = (-north, east).  Neither table divides by cos lat.  For m >= 1 the block walks Q_l^m, the recurrence of Pbar_l^m
+// seeded one cosine short (seed[m] cos^(m-1) lat), and D_l^m = c_d Q_{l-1}^m - l sin lat Q_l^m.  For m = 0 the Q term
+// carries the factor m = 0 and D_l^0 = c_d Pbar_l^1, so the block walks the order-1 recurrence from l = 1.  Either way one
+// recurrence a latitude, two tables (m Q, D) and four columns: (u cos, u sin, v cos, v sin) or those of (vort, div).
 
-// c_d of the line above: sqrt((2l + 1)(l^2 - m^2) / (2l - 1)) for m >= 1, sqrt(l (l + 1) / 2) for m = 0
+// a, b of Pbar_l^m = a (mu Pbar_{l-1}^m - b Pbar_{l-2}^m), l > m (l = m + 1: a = sqrt(2m + 3), b = 0)
+__device__ __forceinline__ void recurrence_coefficients(int l, int m, double &a, double &b) {
+  const double dl = (double)l, dm = (double)m, dl1 = (double)(l - 1);
+  a = sqrt((4.0 * dl * dl - 1.0) / (dl * dl - dm * dm));
+  b = sqrt((dl1 * dl1 - dm * dm) / (4.0 * dl1 * dl1 - 1.0));
+}
+
+// c_d of D above: sqrt((2l + 1)(l^2 - m^2) / (2l - 1)) for m >= 1, sqrt(l (l + 1) / 2) for m = 0
 __device__ __forceinline__ double derivative_coefficient(int l, int m) {
   const double dl = (double)l, dm = (double)m;
   return m ? sqrt((2.0 * dl + 1.0) * (dl * dl - dm * dm) / (2.0 * dl - 1.0)) : sqrt(dl * (dl + 1.0) / 2.0);
 }
 
-// One degree of the walk: p1 = the recurrence value of degree l (p2 of l - 1) on the way out, (q, d) = (m Q_l^m, D_l^m).
-// mm = max(m, 1) is the order of the recurrence; a, b, cd belong to (l, mm) and to derivative_coefficient(l, m).
-__device__ __forceinline__ void vector_step(int l, int m, int mm, double mu, double a, double b, double cd, double &p1,
+// the order of the recurrence that a block of order m walks
+template <bool V>
+__device__ __forceinline__ int walk_order(int m) {
+  return V && m == 0 ? 1 : m;
+}
+
+// The walk's first value at a latitude of cosine cl.  lmax = 0, vector: seed has one entry, and nothing reads the walk.
+template <bool V>
+__device__ __forceinline__ double walk_seed(const double *__restrict__ seed, int m, int L, double cl) {
+  const int mm = walk_order<V>(m);
+  return seed[mm < L ? mm : L] * powi(cl, V ? (m ? m - 1 : 1) : m);
+}
+
+// The recurrence coefficients of the nl degrees from l0 on, one degree a thread: co [2 + V][kLT] holds a, b and, when V,
+// c_d.  The scalar kernels have no third row.
+template <bool V>
+__device__ __forceinline__ void stage_coefficients(double *co, int l0, int nl, int m) {
+  const int t = threadIdx.x, mm = walk_order<V>(m);
+  if (t >= nl) return;
+  double a = 0.0, b = 0.0;
+  if (l0 + t > mm) recurrence_coefficients(l0 + t, mm, a, b);
+  co[t] = a;
+  co[kLT + t] = b;
+  if constexpr (V) co[2 * kLT + t] = derivative_coefficient(l0 + t, m);
+}
+
+// One degree l of the walk, scalar: p1 = Pbar_l^m (p2 = Pbar_{l-1}^m) on the way out; c points at the staged a of l, b is
+// kLT further on.
+__device__ __forceinline__ void scalar_step(int l, int m, double mu, const double *c, double &p1, double &p2, double &p) {
+  if (l > m) {
+    const double n = c[0] * (mu * p1 - c[kLT] * p2);
+    p2 = p1;
+    p1 = n;
+  }
+  p = p1;
+}
+
+// One degree l of the walk, vector: p1 = the recurrence value of degree l (p2 of l - 1) on the way out, (q, d) =
+// (m Q_l^m, D_l^m); a, b and cd are the staged coefficients of l.  The walk is one wave's serial chain while the block's
+// other three wait, and how it reads the coefficients shows in the time: the kernels read these three by value ahead of
+// the call (a select a degree), the scalar step reads its two where it needs them.  Measure before merging the two.
+__device__ __forceinline__ void vector_step(int l, int m, double mu, double a, double b, double cd, double &p1,
                                             double &p2, double &q, double &d) {
-  if (l > mm) {
+  if (l > walk_order<true>(m)) {
     const double p = a * (mu * p1 - b * p2);
     p2 = p1;
     p1 = p;
@@ -504,6 +359,132 @@ __device__ __forceinline__ void vector_step(int l, int m, int mm, double mu, dou
   } else {
     q = 0.0;
     d = l ? cd * p1 : 0.0;
+  }
+}
+
+// Degree t, latitude j of a Legendre tile [kLT][kJT]: column (j + t) & 63, conflict-free for the writer's 64 latitudes
+// and for the readers' 4 degrees a wave.
+__device__ __forceinline__ int tile_at(int t, int j) { return t * kJT + ((j + t) & (kJT - 1)); }
+
+// One table entry against one latitude's (degree's) columns.  Scalar, either direction: (cos, sin) += Pbar (cos, sin).
+__device__ __forceinline__ void contract(const double (&p)[1], const double (&f)[2], double (&acc)[2]) {
+  acc[0] = fma(p[0], f[0], acc[0]);
+  acc[1] = fma(p[0], f[1], acc[1]);
+}
+
+// Vector synthesis: f = (psi cos, psi sin, chi cos, chi sin), acc = (u cos, u sin, v cos, v sin), (u, v) = sum psi k x
+// grad Y + chi grad Y.  (The vector analysis has its four lines in k_vsht_lat_fwd.)
+__device__ __forceinline__ void contract(const double (&p)[2], const double (&f)[4], double (&acc)[4]) {
+  const double q = p[0], d = p[1];
+  acc[0] = fma(q, f[3], fma(-d, f[0], acc[0]));        // u, cos column: -D psi_cos + m Q chi_sin
+  acc[1] = fma(-q, f[2], fma(-d, f[1], acc[1]));       // u, sin column: -D psi_sin - m Q chi_cos
+  acc[2] = fma(d, f[2], fma(q, f[1], acc[2]));         // v, cos column:  m Q psi_sin + D chi_cos
+  acc[3] = fma(d, f[3], fma(-q, f[0], acc[3]));        // v, sin column: -m Q psi_cos + D chi_sin
+}
+
+// What the inverse kernels make of a coefficient of degree l: the scalar one takes it as it is; the vector one reads a
+// NULL tensor and row 0 as 0 and takes the potentials psi = -vort / L and chi = -div / L (unit_L = 0) or -vort, -div
+// (unit_L = 1, the adjoint of the analysis, whose factor L cancels).
+template <bool V, typename TIn>
+__device__ __forceinline__ double loaded_coefficient(const TIn *tensor, int64_t at, int l, int unit_L) {
+  if constexpr (!V) return (double)tensor[at];
+  if (!tensor || l == 0) return 0.0;
+  const double raw = (double)tensor[at];
+  return unit_L ? -raw : -raw / ((double)l * (double)(l + 1));
+}
+
+// Blocks run over (item, channel tile, order m, latitude tile), the last the fastest; the forward kernels have one
+// latitude tile.
+struct LatBlock {
+  int jt, m, ct;
+  int64_t item;
+};
+__device__ __forceinline__ LatBlock lat_block(int L, int ctiles, int jtiles) {
+  LatBlock b;
+  int64_t blk = blockIdx.x;
+  b.jt = (int)(blk % jtiles);
+  blk /= jtiles;
+  b.m = (int)(blk % (L + 1));
+  blk /= (L + 1);
+  b.ct = (int)(blk % ctiles);
+  b.item = blk / ctiles;
+  return b;
+}
+
+// Forward, scalar.  Block (item, channel tile, order m): all latitudes, all degrees l >= m.  Dynamic LDS (lat_fwd_lds):
+// two recurrence values per latitude, the Legendre tile with the latitude weight in it, the ring tile and the recurrence
+// coefficients of the tile's degrees.  Thread (channel, 2 degrees) sums over the latitudes.
+template <typename TOut>
+__global__ __launch_bounds__(kThreads) void k_sht_lat_fwd(const double *__restrict__ ring, const dpair *__restrict__ nodes,
+                                                          const double *__restrict__ lat_w,
+                                                          const double *__restrict__ seed, TOut *__restrict__ coef,
+                                                          int nlat, int L, int C, int ctiles) {
+  extern __shared__ double smem[];
+  double *st1 = smem;                                     // [nlat]  Pbar_{l-1}^m at the start of a degree tile
+  double *st2 = st1 + nlat;                               // [nlat]  Pbar_{l-2}^m
+  double *pt = st2 + nlat;                                // [kLT][kJT]  Pbar w
+  double *ft = pt + kLT * kJT;                            // [kJT][2][kCT]
+  double *co = ft + kJT * 2 * kCT;                        // [2][kLT]
+  const int tid = threadIdx.x, cl = tid & (kCT - 1), lg = tid >> 4;
+  const LatBlock b = lat_block(L, ctiles, 1);
+  const int m = b.m, c = b.ct * kCT + cl;
+  const int64_t T = (int64_t)(L + 1) * (L + 1);
+  for (int j = tid; j < nlat; j += kThreads) {
+    st1[j] = walk_seed<false>(seed, m, L, nodes[j].y);
+    st2[j] = 0.0;
+  }
+  const double *fr = ring + b.item * (int64_t)nlat * (2 * L + 1) * C;
+  for (int l0 = m; l0 <= L; l0 += kLT) {
+    const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
+    __syncthreads();                                      // the tile before is done with co (and st1, st2 are set)
+    stage_coefficients<false>(co, l0, nl, m);
+    double acc[2][2] = {};
+    for (int j0 = 0; j0 < nlat; j0 += kJT) {
+      __syncthreads();
+      if (tid < kJT) {
+        const int j = j0 + tid;
+        if (j < nlat) {
+          double p1 = st1[j], p2 = st2[j];
+          const double mu = nodes[j].x, w = lat_w ? lat_w[j] : 1.0;
+          for (int t = 0; t < nl; ++t) {
+            double p;
+            scalar_step(l0 + t, m, mu, co + t, p1, p2, p);
+            pt[tile_at(t, tid)] = p * w;
+          }
+          st1[j] = p1;
+          st2[j] = p2;
+        } else {
+          for (int t = 0; t < nl; ++t) pt[tile_at(t, tid)] = 0.0;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < kJT * 2 * kCT / kThreads; ++r) {
+        const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 1, jj = e >> 5;
+        const int j = j0 + jj, gc = b.ct * kCT + cc;
+        ft[e] = j < nlat && gc < C ? fr[((int64_t)j * (2 * L + 1) + (kk ? L - m : L + m)) * C + gc] : 0.0;
+      }
+      __syncthreads();
+      const int nj = nlat - j0 < kJT ? nlat - j0 : kJT;
+      for (int jj = 0; jj < nj; ++jj) {
+        const double f[2] = {ft[(jj * 2 + 0) * kCT + cl], ft[(jj * 2 + 1) * kCT + cl]};
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const int t = lg + 16 * r;
+          const double p[1] = {t < nl ? pt[tile_at(t, jj)] : 0.0};
+          contract(p, f, acc[r]);
+        }
+      }
+    }
+    if (c < C) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int l = l0 + lg + 16 * r;
+        if (l > L) continue;
+        TOut *o = coef + (b.item * T + (int64_t)l * l + l) * C + c;
+        o[(int64_t)m * C] = (TOut)acc[r][0];
+        if (m > 0) o[-(int64_t)m * C] = (TOut)acc[r][1];
+      }
+    }
   }
 }
 
@@ -524,37 +505,23 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_fwd(const double *__restr
   double *qt = st2 + nlat;                                // [kLT][kJT]  m Q w
   double *dt = qt + kLT * kJT;                            // [kLT][kJT]  D w
   double *ft = dt + kLT * kJT;                            // [kJT][4][kCT]
-  double *ca = ft + kJT * 4 * kCT;                        // [kLT]
-  double *cb = ca + kLT;                                  // [kLT]
-  double *cd = cb + kLT;                                  // [kLT]
+  double *ca = ft + kJT * 4 * kCT;                        // [3][kLT]: a, b, c_d (stage_coefficients)
+  double *cb = ca + kLT;
+  double *cd = cb + kLT;
   const int tid = threadIdx.x, cl = tid & (kCT - 1), lg = tid >> 4;
-  int64_t blk = blockIdx.x;
-  const int m = (int)(blk % (L + 1));
-  blk /= (L + 1);
-  const int ct = (int)(blk % ctiles);
-  const int64_t item = blk / ctiles;
-  const int c = ct * kCT + cl;
+  const LatBlock b = lat_block(L, ctiles, 1);
+  const int m = b.m, c = b.ct * kCT + cl;
   const int64_t T = (int64_t)(L + 1) * (L + 1);
-  const int mm = m ? m : 1;
-  const double sm = seed[mm < L ? mm : L];                // lmax = 0: seed has one entry, and nothing reads the walk
   for (int j = tid; j < nlat; j += kThreads) {
-    st1[j] = sm * powi(nodes[j].y, m ? m - 1 : 1);
+    st1[j] = walk_seed<true>(seed, m, L, nodes[j].y);
     st2[j] = 0.0;
   }
-  const int64_t item_off = item * (int64_t)nlat * (2 * L + 1) * C;
+  const int64_t item_off = b.item * (int64_t)nlat * (2 * L + 1) * C;
   for (int l0 = m; l0 <= L; l0 += kLT) {
     const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
     __syncthreads();                                      // the tile before is done with ca, cb, cd
-    if (tid < nl) {
-      double a = 0.0, b = 0.0;
-      if (l0 + tid > mm) recurrence_coefficients(l0 + tid, mm, a, b);
-      ca[tid] = a;
-      cb[tid] = b;
-      cd[tid] = derivative_coefficient(l0 + tid, m);
-    }
-    double acc[2][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+    stage_coefficients<true>(ca, l0, nl, m);
+    double acc[2][4] = {};
     for (int j0 = 0; j0 < nlat; j0 += kJT) {
       __syncthreads();
       if (tid < kJT) {
@@ -564,23 +531,23 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_fwd(const double *__restr
           const double mu = nodes[j].x, w = lat_w ? lat_w[j] : 1.0;
           for (int t = 0; t < nl; ++t) {
             double q, d;
-            vector_step(l0 + t, m, mm, mu, ca[t], cb[t], cd[t], p1, p2, q, d);
-            qt[t * kJT + ((tid + t) & (kJT - 1))] = q * w;
-            dt[t * kJT + ((tid + t) & (kJT - 1))] = d * w;
+            vector_step(l0 + t, m, mu, ca[t], cb[t], cd[t], p1, p2, q, d);
+            qt[tile_at(t, tid)] = q * w;
+            dt[tile_at(t, tid)] = d * w;
           }
           st1[j] = p1;
           st2[j] = p2;
         } else {
           for (int t = 0; t < nl; ++t) {
-            qt[t * kJT + ((tid + t) & (kJT - 1))] = 0.0;
-            dt[t * kJT + ((tid + t) & (kJT - 1))] = 0.0;
+            qt[tile_at(t, tid)] = 0.0;
+            dt[tile_at(t, tid)] = 0.0;
           }
         }
       }
 #pragma unroll
       for (int r = 0; r < kJT * 4 * kCT / kThreads; ++r) {
         const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 3, jj = e >> 6;
-        const int j = j0 + jj, gc = ct * kCT + cc;
+        const int j = j0 + jj, gc = b.ct * kCT + cc;
         const double *fr = (kk & 2 ? ring_v : ring_u) + item_off;
         ft[e] = j < nlat && gc < C ? fr[((int64_t)j * (2 * L + 1) + (kk & 1 ? L - m : L + m)) * C + gc] : 0.0;
       }
@@ -592,8 +559,8 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_fwd(const double *__restr
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
           const int t = lg + 16 * r;
-          const double q = t < nl ? qt[t * kJT + ((jj + t) & (kJT - 1))] : 0.0;
-          const double d = t < nl ? dt[t * kJT + ((jj + t) & (kJT - 1))] : 0.0;
+          const double q = t < nl ? qt[tile_at(t, jj)] : 0.0;
+          const double d = t < nl ? dt[tile_at(t, jj)] : 0.0;
           acc[r][0] = fma(q, vs, fma(d, uc, acc[r][0]));     // vort, cos row:  D u_cos + m Q v_sin
           acc[r][1] = fma(-q, vc, fma(d, us, acc[r][1]));    // vort, sin row:  D u_sin - m Q v_cos
           acc[r][2] = fma(-d, vc, fma(q, us, acc[r][2]));    // div, cos row:   m Q u_sin - D v_cos
@@ -607,7 +574,7 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_fwd(const double *__restr
         const int l = l0 + lg + 16 * r;
         if (l > L) continue;
         const double big = (double)l * (double)(l + 1);
-        const int64_t o = (item * T + (int64_t)l * l + l) * C + c;
+        const int64_t o = (b.item * T + (int64_t)l * l + l) * C + c;
         double out[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) out[k] = l == 0 ? 0.0 : inv_L ? acc[r][k] / big : acc[r][k];
@@ -622,83 +589,65 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_fwd(const double *__restr
   }
 }
 
-// Block (item, channel tile, order m, 64 latitudes) as k_sht_lat_inv: the coefficient tile holds the potentials
-// psi = -vort / L and chi = -div / L (unit_L = 0) or -vort, -div (unit_L = 1, the adjoint of the analysis, whose factor L
-// cancels); row 0, a NULL pointer and the sin row of order 0 read as 0.  (u, v) = sum psi k x grad Y + chi grad Y.
-template <typename TIn>
-__global__ __launch_bounds__(kThreads) void k_vsht_lat_inv(const TIn *__restrict__ vort, const TIn *__restrict__ div,
-                                                           const dpair *__restrict__ nodes,
-                                                           const double *__restrict__ seed, double *__restrict__ ring_u,
-                                                           double *__restrict__ ring_v, int nlat, int L, int C,
-                                                           int ctiles, int jtiles, int unit_L) {
-  __shared__ double qt[kLT * kJT];
-  __shared__ double dt[kLT * kJT];
-  __shared__ double ctile[kLT * 4 * kCT];
-  __shared__ double ca[kLT], cb[kLT], cd[kLT];
+// Inverse.  Block (item, channel tile, order m, 64 latitudes): the recurrence lives in the registers of the block's
+// first 64 threads; thread (channel, 4 latitudes) sums over the degrees.  The sin row of order 0 reads as 0.  in1, out1:
+// the vector kernel's div and v ring.
+template <bool V, typename TIn>
+__device__ __forceinline__ void lat_inv(const TIn *__restrict__ in0, const TIn *__restrict__ in1,
+                                        const dpair *__restrict__ nodes, const double *__restrict__ seed,
+                                        double *__restrict__ out0, double *__restrict__ out1, int nlat, int L, int C,
+                                        int ctiles, int jtiles, int unit_L) {
+  constexpr int NT = V ? 2 : 1, NC = 2 * NT;
+  __shared__ double tab[NT * kLT * kJT];
+  __shared__ double ctile[kLT * NC * kCT];
+  __shared__ double co[(2 + V) * kLT];
   const int tid = threadIdx.x, cl = tid & (kCT - 1), jg = tid >> 4;
-  int64_t blk = blockIdx.x;
-  const int jt = (int)(blk % jtiles);
-  blk /= jtiles;
-  const int m = (int)(blk % (L + 1));
-  blk /= (L + 1);
-  const int ct = (int)(blk % ctiles);
-  const int64_t item = blk / ctiles;
-  const int c = ct * kCT + cl;
+  const LatBlock b = lat_block(L, ctiles, jtiles);
+  const int m = b.m, c = b.ct * kCT + cl;
   const int64_t T = (int64_t)(L + 1) * (L + 1);
-  const int mm = m ? m : 1;
-  const int j0 = jt * kJT;
+  const int j0 = b.jt * kJT;
   const int jmine = j0 + tid;
   double p1 = 0.0, p2 = 0.0, mu = 0.0;
   if (tid < kJT && jmine < nlat) {
-    p1 = seed[mm < L ? mm : L] * powi(nodes[jmine].y, m ? m - 1 : 1);
+    p1 = walk_seed<V>(seed, m, L, nodes[jmine].y);
     mu = nodes[jmine].x;
   }
-  double acc[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = 0.0;
+  double acc[4][NC] = {};
   for (int l0 = m; l0 <= L; l0 += kLT) {
     const int nl = L - l0 + 1 < kLT ? L - l0 + 1 : kLT;
     __syncthreads();
-    if (tid < nl) {
-      double a = 0.0, b = 0.0;
-      if (l0 + tid > mm) recurrence_coefficients(l0 + tid, mm, a, b);
-      ca[tid] = a;
-      cb[tid] = b;
-      cd[tid] = derivative_coefficient(l0 + tid, m);
-    }
+    stage_coefficients<V>(co, l0, nl, m);
 #pragma unroll
-    for (int r = 0; r < kLT * 4 * kCT / kThreads; ++r) {
-      const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & 3, t = e >> 6;
-      const int l = l0 + t, gc = ct * kCT + cc;
-      const TIn *cf = kk & 2 ? div : vort;
-      double val = 0.0;
-      if (cf && l > 0 && l <= L && gc < C && !((kk & 1) && m == 0)) {
-        const double raw = (double)cf[(item * T + (int64_t)l * l + l + (kk & 1 ? -m : m)) * C + gc];
-        val = unit_L ? -raw : -raw / ((double)l * (double)(l + 1));
-      }
-      ctile[e] = val;
+    for (int r = 0; r < kLT * NC * kCT / kThreads; ++r) {
+      const int e = tid + kThreads * r, cc = e & (kCT - 1), kk = (e >> 4) & (NC - 1), t = e / (NC * kCT);
+      const int l = l0 + t, gc = b.ct * kCT + cc;
+      const int64_t at = (b.item * T + (int64_t)l * l + l + (kk & 1 ? -m : m)) * C + gc;
+      const bool there = l <= L && gc < C && !((kk & 1) && m == 0);
+      ctile[e] = there ? loaded_coefficient<V>(kk & 2 ? in1 : in0, at, l, unit_L) : 0.0;
     }
     __syncthreads();
     if (tid < kJT) {
       for (int t = 0; t < nl; ++t) {
-        double q, d;
-        vector_step(l0 + t, m, mm, mu, ca[t], cb[t], cd[t], p1, p2, q, d);
-        qt[t * kJT + ((tid + t) & (kJT - 1))] = q;
-        dt[t * kJT + ((tid + t) & (kJT - 1))] = d;
+        double val[NT];
+        if constexpr (V)
+          vector_step(l0 + t, m, mu, co[t], co[kLT + t], co[2 * kLT + t], p1, p2, val[0], val[NT - 1]);
+        else
+          scalar_step(l0 + t, m, mu, co + t, p1, p2, val[0]);
+#pragma unroll
+        for (int k = 0; k < NT; ++k) tab[k * kLT * kJT + tile_at(t, tid)] = val[k];
       }
     }
     __syncthreads();
     for (int t = 0; t < nl; ++t) {
-      const double pc = ctile[(t * 4 + 0) * kCT + cl], ps = ctile[(t * 4 + 1) * kCT + cl];
-      const double xc = ctile[(t * 4 + 2) * kCT + cl], xs = ctile[(t * 4 + 3) * kCT + cl];
+      double f[NC];
+#pragma unroll
+      for (int k = 0; k < NC; ++k) f[k] = ctile[(t * NC + k) * kCT + cl];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const double q = qt[t * kJT + ((jg + 16 * r + t) & (kJT - 1))];
-        const double d = dt[t * kJT + ((jg + 16 * r + t) & (kJT - 1))];
-        acc[r][0] = fma(q, xs, fma(-d, pc, acc[r][0]));      // u, cos column: -D psi_cos + m Q chi_sin
-        acc[r][1] = fma(-q, xc, fma(-d, ps, acc[r][1]));     // u, sin column: -D psi_sin - m Q chi_cos
-        acc[r][2] = fma(d, xc, fma(q, ps, acc[r][2]));       // v, cos column:  m Q psi_sin + D chi_cos
-        acc[r][3] = fma(d, xs, fma(-q, pc, acc[r][3]));      // v, sin column: -m Q psi_cos + D chi_sin
+        double p[NT];
+#pragma unroll
+        for (int k = 0; k < NT; ++k) p[k] = tab[k * kLT * kJT + tile_at(t, jg + 16 * r)];
+        contract(p, f, acc[r]);
       }
     }
   }
@@ -707,14 +656,30 @@ __global__ __launch_bounds__(kThreads) void k_vsht_lat_inv(const TIn *__restrict
   for (int r = 0; r < 4; ++r) {
     const int j = j0 + jg + 16 * r;
     if (j >= nlat) continue;
-    const int64_t o = ((item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
-    ring_u[o + (int64_t)m * C] = acc[r][0];
-    ring_v[o + (int64_t)m * C] = acc[r][2];
-    if (m > 0) {
-      ring_u[o - (int64_t)m * C] = acc[r][1];
-      ring_v[o - (int64_t)m * C] = acc[r][3];
+    const int64_t o = ((b.item * nlat + j) * (int64_t)(2 * L + 1) + L) * C + c;
+#pragma unroll
+    for (int k = 0; k < NT; ++k) {
+      double *out = k ? out1 : out0;
+      out[o + (int64_t)m * C] = acc[r][2 * k];
+      if (m > 0) out[o - (int64_t)m * C] = acc[r][2 * k + 1];
     }
   }
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(kThreads) void k_sht_lat_inv(const TIn *__restrict__ coef, const dpair *__restrict__ nodes,
+                                                          const double *__restrict__ seed, double *__restrict__ ring,
+                                                          int nlat, int L, int C, int ctiles, int jtiles) {
+  lat_inv<false, TIn>(coef, nullptr, nodes, seed, ring, nullptr, nlat, L, C, ctiles, jtiles, 0);
+}
+
+template <typename TIn>
+__global__ __launch_bounds__(kThreads) void k_vsht_lat_inv(const TIn *__restrict__ vort, const TIn *__restrict__ div,
+                                                           const dpair *__restrict__ nodes,
+                                                           const double *__restrict__ seed, double *__restrict__ ring_u,
+                                                           double *__restrict__ ring_v, int nlat, int L, int C,
+                                                           int ctiles, int jtiles, int unit_L) {
+  lat_inv<true, TIn>(vort, div, nodes, seed, ring_u, ring_v, nlat, L, C, ctiles, jtiles, unit_L);
 }
 
 struct Shape {
@@ -810,6 +775,58 @@ int chunk_items(const Shape &s, size_t workspace_bytes, int64_t batch, int64_t &
   return 0;
 }
 
+bool is_vector(int op) { return op == GWEN_SHT_OP_VECTOR_ANALYSIS || op == GWEN_SHT_OP_VECTOR_SYNTHESIS; }
+
+// Everything about a call of a valid op that is judged before a HIP call; 0 = fine, with the shape and the items of a
+// pass (0 for an empty batch).  The vector transforms have two inputs and two outputs, an adjoint flag and a ring of
+// twice the scalar's; the scalar ones do not read in1, out1 or adjoint.  One coefficient tensor of the vector synthesis
+// may be NULL.  rings: the tables of a reduced grid (k.nlon is then its longest ring, k.grid and k.longitude are not
+// read), or NULL.
+int check_call(const gwen_sht_call &k, const Rings *rings, Shape &s, int64_t &chunk) {
+  const bool vec = is_vector(k.op), in_optional = k.op == GWEN_SHT_OP_VECTOR_SYNTHESIS;
+  int rc = rings ? check_rings_shape(*rings, k.nlat, k.nlon, k.lmax, k.C, s)
+                 : check_shape(k.grid, k.nlat, k.nlon, k.lmax, k.C, s, k.longitude);
+  if (rc) return rc;
+  if (vec) s.item_bytes *= 2;
+  if (k.batch < 0 || (k.in_f64 != 0 && k.in_f64 != 1) || (k.out_f64 != 0 && k.out_f64 != 1)) return GWEN_EINVAL;
+  if (vec && k.adjoint != 0 && k.adjoint != 1) return GWEN_EINVAL;
+  chunk = 0;
+  if (k.batch == 0) return 0;
+  if (rings && !(rings->nlon && rings->start && gwen_aligned(rings->nlon, 4) && gwen_aligned(rings->start, 8)))
+    return GWEN_EINVAL;
+  const void *in1 = vec ? k.in1 : k.in0, *out1 = vec ? k.out1 : k.out0;
+  if (in_optional ? !k.in0 && !in1 : !k.in0 || !in1) return GWEN_EINVAL;
+  if (!k.out0 || !out1 || !k.nodes || !k.twiddle || !k.seed || !k.workspace) return GWEN_EINVAL;
+  const size_t in_size = k.in_f64 ? 8 : 4, out_size = k.out_f64 ? 8 : 4;
+  if (!gwen_aligned(k.in0, in_size) || !gwen_aligned(in1, in_size) || !gwen_aligned(k.out0, out_size) ||
+      !gwen_aligned(out1, out_size) || !gwen_aligned(k.nodes, 16) || !gwen_aligned(k.twiddle, 16) ||
+      !gwen_aligned(k.seed, 8) || !gwen_aligned(k.workspace, 8))
+    return GWEN_EINVAL;
+  // lat_w's alignment is judged before the workspace's size by the vector transforms and after it by the scalar ones, as
+  // each has done since it was written: a caller with both wrong gets the code it has always got.
+  const bool lat_w_ok = !k.lat_w || gwen_aligned(k.lat_w, 8);
+  if (vec && !lat_w_ok) return GWEN_EINVAL;
+  rc = chunk_items(s, k.workspace_bytes, k.batch, chunk);
+  return rc ? rc : lat_w_ok ? 0 : GWEN_EINVAL;
+}
+
+// A launch may ask for 64 KB of dynamic LDS as it is; above that the kernel's limit is raised first.
+template <typename Kernel>
+int allow_dynamic_lds(Kernel *kernel, size_t lds) {
+  if (lds > 64 * 1024)
+    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds));
+  return 0;
+}
+
+// the grid and the dynamic LDS of an FFT longitude kernel over `rings` rings
+template <typename Kernel>
+int fft_launch(const Shape &s, Kernel *kernel, int64_t rings, dim3 &grid, size_t &lds) {
+  grid = dim3((unsigned)sht_fft::grid_blocks(rings, s.fft_ctiles));
+  lds = sht_fft::lds_bytes(s.fft);
+  return allow_dynamic_lds(kernel, lds);
+}
+
 // The longitude stage of nb items: the direct sums or the FFT, as the shape says.
 template <typename TIn>
 int lon_fwd(const Shape &s, const TIn *x, const double *tw, double *ring, int64_t nb, hipStream_t st) {
@@ -819,22 +836,16 @@ int lon_fwd(const Shape &s, const TIn *x, const double *tw, double *ring, int64_
     k_sht_rings_lon_fwd<TIn><<<dim3((unsigned)(s.nlat * ltiles * s.mtiles)), dim3(kThreads), 0, st>>>(
         x, reinterpret_cast<const dpair *>(tw), s.ring_nlon, s.ring_start, ring, lanes, s.points, s.nlat, s.L, s.C,
         s.mtiles, (int)ltiles);
-    GWEN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s.longitude == GWEN_SHT_LON_DIRECT) {
+  } else if (s.longitude == GWEN_SHT_LON_DIRECT) {
     k_sht_lon_fwd<TIn><<<dim3((unsigned)((rows + 63) / 64 * s.mtiles)), dim3(kThreads), 0, st>>>(
         x, reinterpret_cast<const dpair *>(tw), ring, rows, s.nlon, s.L, s.C, s.mtiles);
-    GWEN_LAUNCH_CHECK();
-    return 0;
+  } else {
+    dim3 grid;
+    size_t lds;
+    if (const int rc = fft_launch(s, &sht_fft::k_sht_lon_fft_fwd<TIn>, nb * s.nlat, grid, lds)) return rc;
+    sht_fft::k_sht_lon_fft_fwd<TIn><<<grid, dim3(sht_fft::kThreads), lds, st>>>(
+        x, reinterpret_cast<const sht_fft::cpx *>(tw), ring, nb * s.nlat, s.nlon, s.L, s.C, s.fft_ctiles, s.fft);
   }
-  const size_t lds = sht_fft::lds_bytes(s.fft);
-  if (lds > 64 * 1024)
-    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sht_fft::k_sht_lon_fft_fwd<TIn>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  sht_fft::k_sht_lon_fft_fwd<TIn>
-      <<<dim3((unsigned)sht_fft::grid_blocks(nb * s.nlat, s.fft_ctiles)), dim3(sht_fft::kThreads), lds, st>>>(
-          x, reinterpret_cast<const sht_fft::cpx *>(tw), ring, nb * s.nlat, s.nlon, s.L, s.C, s.fft_ctiles, s.fft);
   GWEN_LAUNCH_CHECK();
   return 0;
 }
@@ -848,265 +859,102 @@ int lon_inv(const Shape &s, const double *ring, const double *tw, const double *
     k_sht_rings_lon_inv<TOut><<<dim3((unsigned)(s.nlat * ltiles * s.itiles)), dim3(kThreads), 0, st>>>(
         ring, reinterpret_cast<const dpair *>(tw), s.ring_nlon, s.ring_start, lat_w, x, lanes, s.points, s.nlat, s.L,
         s.C, s.itiles, (int)ltiles);
-    GWEN_LAUNCH_CHECK();
-    return 0;
-  }
-  if (s.longitude == GWEN_SHT_LON_DIRECT) {
+  } else if (s.longitude == GWEN_SHT_LON_DIRECT) {
     k_sht_lon_inv<TOut><<<dim3((unsigned)((rows + 63) / 64 * s.itiles)), dim3(kThreads), 0, st>>>(
         ring, reinterpret_cast<const dpair *>(tw), lat_w, x, rows, s.nlat, s.nlon, s.L, s.C, s.itiles);
-    GWEN_LAUNCH_CHECK();
-    return 0;
+  } else {
+    dim3 grid;
+    size_t lds;
+    if (const int rc = fft_launch(s, &sht_fft::k_sht_lon_fft_inv<TOut>, nb * s.nlat, grid, lds)) return rc;
+    sht_fft::k_sht_lon_fft_inv<TOut><<<grid, dim3(sht_fft::kThreads), lds, st>>>(
+        ring, reinterpret_cast<const sht_fft::cpx *>(tw), lat_w, x, nb * s.nlat, s.nlat, s.nlon, s.L, s.C, s.fft_ctiles,
+        s.fft);
   }
-  const size_t lds = sht_fft::lds_bytes(s.fft);
-  if (lds > 64 * 1024)
-    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&sht_fft::k_sht_lon_fft_inv<TOut>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  sht_fft::k_sht_lon_fft_inv<TOut>
-      <<<dim3((unsigned)sht_fft::grid_blocks(nb * s.nlat, s.fft_ctiles)), dim3(sht_fft::kThreads), lds, st>>>(
-          ring, reinterpret_cast<const sht_fft::cpx *>(tw), lat_w, x, nb * s.nlat, s.nlat, s.nlon, s.L, s.C,
-          s.fft_ctiles, s.fft);
   GWEN_LAUNCH_CHECK();
   return 0;
 }
 
-size_t lat_fwd_lds(int nlat) { return sizeof(double) * (2 * (size_t)nlat + kLT * kJT + kJT * 2 * kCT + 2 * kLT); }
+// the dynamic LDS of k_sht_lat_fwd (V = false) and of k_vsht_lat_fwd
+size_t lat_fwd_lds(bool V, int nlat) {
+  const size_t NT = V ? 2 : 1;
+  return sizeof(double) * (2 * (size_t)nlat + NT * kLT * kJT + kJT * 2 * NT * kCT + (2 + V) * kLT);
+}
 
-template <typename TIn, typename TOut>
-int analysis(const Shape &s, const TIn *x, TOut *coef, const double *nodes, const double *lat_w, const double *tw,
-             const double *seed, int64_t batch, int64_t chunk, double *ring, hipStream_t st) {
-  const size_t lds = lat_fwd_lds(s.nlat);
-  if (lds > 64 * 1024)
-    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sht_lat_fwd<TOut>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
-  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    if (const int rc = lon_fwd(s, x + b0 * s.points * s.C, tw, ring, nb, st)) return rc;
-    k_sht_lat_fwd<TOut><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1))), dim3(kThreads), lds, st>>>(
-        ring, reinterpret_cast<const dpair *>(nodes), lat_w, seed, coef + b0 * T * s.C, s.nlat, s.L, s.C, s.ctiles);
+// The transforms of a checked call, `chunk` items a pass: one field (V = false) or two.  The ring of a pass of nb items
+// is [1 + V, nb, nlat, 2 lmax + 1, C]: u's first, then v's.
+template <bool V, typename TIn, typename TOut>
+int analysis(const Shape &s, const gwen_sht_call &k, int64_t chunk) {
+  hipStream_t st = gwen_stream(k.stream);
+  const dpair *nodes = reinterpret_cast<const dpair *>(k.nodes);
+  const TIn *in[2] = {static_cast<const TIn *>(k.in0), static_cast<const TIn *>(k.in1)};
+  TOut *out0 = static_cast<TOut *>(k.out0), *out1 = static_cast<TOut *>(k.out1);
+  double *ring = static_cast<double *>(k.workspace);
+  const size_t lds = lat_fwd_lds(V, s.nlat);
+  if (const int rc = V ? allow_dynamic_lds(&k_vsht_lat_fwd<TOut>, lds) : allow_dynamic_lds(&k_sht_lat_fwd<TOut>, lds))
+    return rc;
+  const int64_t TC = (int64_t)(s.L + 1) * (s.L + 1) * s.C, item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
+  for (int64_t b0 = 0; b0 < k.batch; b0 += chunk) {
+    const int64_t nb = k.batch - b0 < chunk ? k.batch - b0 : chunk;
+    for (int f = 0; f <= V; ++f)
+      if (const int rc = lon_fwd(s, in[f] + b0 * s.points * s.C, k.twiddle, ring + f * nb * item, nb, st)) return rc;
+    const dim3 grid((unsigned)(nb * s.ctiles * (s.L + 1)));
+    if constexpr (V)
+      k_vsht_lat_fwd<TOut><<<grid, dim3(kThreads), lds, st>>>(ring, ring + nb * item, nodes, k.lat_w, k.seed,
+                                                              out0 + b0 * TC, out1 + b0 * TC, s.nlat, s.L, s.C, s.ctiles,
+                                                              k.adjoint);
+    else
+      k_sht_lat_fwd<TOut><<<grid, dim3(kThreads), lds, st>>>(ring, nodes, k.lat_w, k.seed, out0 + b0 * TC, s.nlat, s.L,
+                                                             s.C, s.ctiles);
     GWEN_LAUNCH_CHECK();
   }
   return 0;
 }
 
-template <typename TIn, typename TOut>
-int synthesis(const Shape &s, const TIn *coef, TOut *x, const double *nodes, const double *lat_w, const double *tw,
-              const double *seed, int64_t batch, int64_t chunk, double *ring, hipStream_t st) {
-  const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
-  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    k_sht_lat_inv<TIn><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1) * s.jtiles)), dim3(kThreads), 0, st>>>(
-        coef + b0 * T * s.C, reinterpret_cast<const dpair *>(nodes), seed, ring, s.nlat, s.L, s.C, s.ctiles, s.jtiles);
+template <bool V, typename TIn, typename TOut>
+int synthesis(const Shape &s, const gwen_sht_call &k, int64_t chunk) {
+  hipStream_t st = gwen_stream(k.stream);
+  const dpair *nodes = reinterpret_cast<const dpair *>(k.nodes);
+  const TIn *in0 = static_cast<const TIn *>(k.in0), *in1 = static_cast<const TIn *>(k.in1);
+  TOut *out[2] = {static_cast<TOut *>(k.out0), static_cast<TOut *>(k.out1)};
+  double *ring = static_cast<double *>(k.workspace);
+  const int64_t TC = (int64_t)(s.L + 1) * (s.L + 1) * s.C, item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
+  for (int64_t b0 = 0; b0 < k.batch; b0 += chunk) {
+    const int64_t nb = k.batch - b0 < chunk ? k.batch - b0 : chunk;
+    const dim3 grid((unsigned)(nb * s.ctiles * (s.L + 1) * s.jtiles));
+    if constexpr (V)
+      k_vsht_lat_inv<TIn><<<grid, dim3(kThreads), 0, st>>>(in0 ? in0 + b0 * TC : nullptr, in1 ? in1 + b0 * TC : nullptr,
+                                                           nodes, k.seed, ring, ring + nb * item, s.nlat, s.L, s.C,
+                                                           s.ctiles, s.jtiles, k.adjoint);
+    else
+      k_sht_lat_inv<TIn><<<grid, dim3(kThreads), 0, st>>>(in0 + b0 * TC, nodes, k.seed, ring, s.nlat, s.L, s.C, s.ctiles,
+                                                          s.jtiles);
     GWEN_LAUNCH_CHECK();
-    if (const int rc = lon_inv(s, ring, tw, lat_w, x + b0 * s.points * s.C, nb, st)) return rc;
+    for (int f = 0; f <= V; ++f)
+      if (const int rc = lon_inv(s, ring + f * nb * item, k.twiddle, k.lat_w, out[f] + b0 * s.points * s.C, nb, st))
+        return rc;
   }
   return 0;
 }
 
-bool rings_tables_ok(const Rings &r) { return r.nlon && r.start && gwen_aligned(r.nlon, 4) && gwen_aligned(r.start, 8); }
-
-int check_call(const void *a, int a_f64, const void *b, int b_f64, const double *nodes, const double *tw,
-               const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C,
-               int longitude, const void *workspace, size_t workspace_bytes, const Rings *rings, Shape &s,
-               int64_t &chunk) {
-  const int rc = rings ? check_rings_shape(*rings, nlat, nlon, lmax, C, s)
-                       : check_shape(grid, nlat, nlon, lmax, C, s, longitude);
-  if (rc) return rc;
-  if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1)) return GWEN_EINVAL;
-  chunk = 0;
-  if (batch == 0) return 0;
-  if (rings && !rings_tables_ok(*rings)) return GWEN_EINVAL;
-  if (!a || !b || !nodes || !tw || !seed || !workspace) return GWEN_EINVAL;
-  if (!gwen_aligned(a, a_f64 ? 8 : 4) || !gwen_aligned(b, b_f64 ? 8 : 4) || !gwen_aligned(nodes, 16) ||
-      !gwen_aligned(tw, 16) || !gwen_aligned(seed, 8) || !gwen_aligned(workspace, 8))
-    return GWEN_EINVAL;
-  return chunk_items(s, workspace_bytes, batch, chunk);
-}
-
-size_t vector_lat_fwd_lds(int nlat) {
-  return sizeof(double) * (2 * (size_t)nlat + 2 * kLT * kJT + kJT * 4 * kCT + 3 * kLT);
-}
-
-// The ring of a pass is [2, nb, nlat, 2 lmax + 1, C]: u's first, then v's.
-template <typename TIn, typename TOut>
-int vector_analysis(const Shape &s, const TIn *u, const TIn *v, TOut *vort, TOut *div, const double *nodes,
-                    const double *lat_w, const double *tw, const double *seed, int adjoint, int64_t batch, int64_t chunk,
-                    double *ring, hipStream_t st) {
-  const size_t lds = vector_lat_fwd_lds(s.nlat);
-  if (lds > 64 * 1024)
-    GWEN_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vsht_lat_fwd<TOut>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
-  const int64_t item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
-  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    const int64_t xo = b0 * s.points * s.C;
-    double *ring_v = ring + nb * item;
-    if (const int rc = lon_fwd(s, u + xo, tw, ring, nb, st)) return rc;
-    if (const int rc = lon_fwd(s, v + xo, tw, ring_v, nb, st)) return rc;
-    k_vsht_lat_fwd<TOut><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1))), dim3(kThreads), lds, st>>>(
-        ring, ring_v, reinterpret_cast<const dpair *>(nodes), lat_w, seed, vort + b0 * T * s.C, div + b0 * T * s.C,
-        s.nlat, s.L, s.C, s.ctiles, adjoint);
-    GWEN_LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-template <typename TIn, typename TOut>
-int vector_synthesis(const Shape &s, const TIn *vort, const TIn *div, TOut *u, TOut *v, const double *nodes,
-                     const double *lat_w, const double *tw, const double *seed, int adjoint, int64_t batch, int64_t chunk,
-                     double *ring, hipStream_t st) {
-  const int64_t T = (int64_t)(s.L + 1) * (s.L + 1);
-  const int64_t item = (int64_t)s.nlat * (2 * s.L + 1) * s.C;
-  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
-    const int64_t nb = batch - b0 < chunk ? batch - b0 : chunk;
-    double *ring_v = ring + nb * item;
-    k_vsht_lat_inv<TIn><<<dim3((unsigned)(nb * s.ctiles * (s.L + 1) * s.jtiles)), dim3(kThreads), 0, st>>>(
-        vort ? vort + b0 * T * s.C : nullptr, div ? div + b0 * T * s.C : nullptr,
-        reinterpret_cast<const dpair *>(nodes), seed, ring, ring_v, s.nlat, s.L, s.C, s.ctiles, s.jtiles, adjoint);
-    GWEN_LAUNCH_CHECK();
-    const int64_t xo = b0 * s.points * s.C;
-    if (const int rc = lon_inv(s, ring, tw, lat_w, u + xo, nb, st)) return rc;
-    if (const int rc = lon_inv(s, ring_v, tw, lat_w, v + xo, nb, st)) return rc;
-  }
-  return 0;
-}
-
-// check_call for two inputs and two outputs; the ring of an item is twice the scalar's.  a1 may be NULL when
-// a_optional (a0 likewise): a missing coefficient tensor of the synthesis.
-int check_vector_call(const void *a0, const void *a1, int a_optional, int a_f64, const void *b0, const void *b1, int b_f64,
-                      const double *nodes, const double *lat_w, const double *tw, const double *seed, int grid,
-                      int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint, int longitude,
-                      const void *workspace, size_t workspace_bytes, const Rings *rings, Shape &s, int64_t &chunk) {
-  const int rc = rings ? check_rings_shape(*rings, nlat, nlon, lmax, C, s)
-                       : check_shape(grid, nlat, nlon, lmax, C, s, longitude);
-  if (rc) return rc;
-  s.item_bytes *= 2;
-  if (batch < 0 || (a_f64 != 0 && a_f64 != 1) || (b_f64 != 0 && b_f64 != 1) || (adjoint != 0 && adjoint != 1))
-    return GWEN_EINVAL;
-  chunk = 0;
-  if (batch == 0) return 0;
-  if (rings && !rings_tables_ok(*rings)) return GWEN_EINVAL;
-  if (a_optional ? !a0 && !a1 : !a0 || !a1) return GWEN_EINVAL;
-  if (!b0 || !b1 || !nodes || !tw || !seed || !workspace) return GWEN_EINVAL;
-  if (!gwen_aligned(a0, a_f64 ? 8 : 4) || !gwen_aligned(a1, a_f64 ? 8 : 4) || !gwen_aligned(b0, b_f64 ? 8 : 4) ||
-      !gwen_aligned(b1, b_f64 ? 8 : 4) || !gwen_aligned(nodes, 16) || !gwen_aligned(tw, 16) || !gwen_aligned(seed, 8) ||
-      !gwen_aligned(workspace, 8) || (lat_w && !gwen_aligned(lat_w, 8)))
-    return GWEN_EINVAL;
-  return chunk_items(s, workspace_bytes, batch, chunk);
-}
-
-// The four transforms behind gwen_sht_transform and gwen_sht_rings_transform, each after its checks.  rings: the tables of
-// a reduced grid (k.nlon is then its longest ring, k.grid and k.longitude are not read), or NULL.
-int scalar_analysis(const gwen_sht_call &k, const Rings *rings) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_call(k.in0, k.in_f64, k.out0, k.out_f64, k.nodes, k.twiddle, k.seed, k.grid, k.batch, k.nlat,
-                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, rings, s, chunk);
-  if (rc || k.batch == 0) return rc;
-  if (k.lat_w && !gwen_aligned(k.lat_w, 8)) return GWEN_EINVAL;
-  hipStream_t st = gwen_stream(k.stream);
-  double *ring = static_cast<double *>(k.workspace);
-  const auto run = [&](auto *x, auto *coef) {
-    return analysis(s, x, coef, k.nodes, k.lat_w, k.twiddle, k.seed, k.batch, chunk, ring, st);
-  };
-  if (k.in_f64) return k.out_f64 ? run((const double *)k.in0, (double *)k.out0) : run((const double *)k.in0, (float *)k.out0);
-  return k.out_f64 ? run((const float *)k.in0, (double *)k.out0) : run((const float *)k.in0, (float *)k.out0);
-}
-
-int scalar_synthesis(const gwen_sht_call &k, const Rings *rings) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_call(k.in0, k.in_f64, k.out0, k.out_f64, k.nodes, k.twiddle, k.seed, k.grid, k.batch, k.nlat,
-                            k.nlon, k.lmax, k.C, k.longitude, k.workspace, k.workspace_bytes, rings, s, chunk);
-  if (rc || k.batch == 0) return rc;
-  if (k.lat_w && !gwen_aligned(k.lat_w, 8)) return GWEN_EINVAL;
-  hipStream_t st = gwen_stream(k.stream);
-  double *ring = static_cast<double *>(k.workspace);
-  const auto run = [&](auto *coef, auto *x) {
-    return synthesis(s, coef, x, k.nodes, k.lat_w, k.twiddle, k.seed, k.batch, chunk, ring, st);
-  };
-  if (k.in_f64) return k.out_f64 ? run((const double *)k.in0, (double *)k.out0) : run((const double *)k.in0, (float *)k.out0);
-  return k.out_f64 ? run((const float *)k.in0, (double *)k.out0) : run((const float *)k.in0, (float *)k.out0);
-}
-
-int vector_analysis_call(const gwen_sht_call &k, const Rings *rings) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_vector_call(k.in0, k.in1, 0, k.in_f64, k.out0, k.out1, k.out_f64, k.nodes, k.lat_w, k.twiddle,
-                                   k.seed, k.grid, k.batch, k.nlat, k.nlon, k.lmax, k.C, k.adjoint, k.longitude,
-                                   k.workspace, k.workspace_bytes, rings, s, chunk);
-  if (rc || k.batch == 0) return rc;
-  hipStream_t st = gwen_stream(k.stream);
-  double *ring = static_cast<double *>(k.workspace);
-  const auto run = [&](auto *u, auto *v, auto *vort, auto *div) {
-    return vector_analysis(s, u, v, vort, div, k.nodes, k.lat_w, k.twiddle, k.seed, k.adjoint, k.batch, chunk, ring, st);
-  };
-  if (k.in_f64)
-    return k.out_f64 ? run((const double *)k.in0, (const double *)k.in1, (double *)k.out0, (double *)k.out1)
-                     : run((const double *)k.in0, (const double *)k.in1, (float *)k.out0, (float *)k.out1);
-  return k.out_f64 ? run((const float *)k.in0, (const float *)k.in1, (double *)k.out0, (double *)k.out1)
-                   : run((const float *)k.in0, (const float *)k.in1, (float *)k.out0, (float *)k.out1);
-}
-
-int vector_synthesis_call(const gwen_sht_call &k, const Rings *rings) {
-  Shape s;
-  int64_t chunk;
-  const int rc = check_vector_call(k.in0, k.in1, 1, k.in_f64, k.out0, k.out1, k.out_f64, k.nodes, k.lat_w, k.twiddle,
-                                   k.seed, k.grid, k.batch, k.nlat, k.nlon, k.lmax, k.C, k.adjoint, k.longitude,
-                                   k.workspace, k.workspace_bytes, rings, s, chunk);
-  if (rc || k.batch == 0) return rc;
-  hipStream_t st = gwen_stream(k.stream);
-  double *ring = static_cast<double *>(k.workspace);
-  const auto run = [&](auto *vort, auto *div, auto *u, auto *v) {
-    return vector_synthesis(s, vort, div, u, v, k.nodes, k.lat_w, k.twiddle, k.seed, k.adjoint, k.batch, chunk, ring, st);
-  };
-  if (k.in_f64)
-    return k.out_f64 ? run((const double *)k.in0, (const double *)k.in1, (double *)k.out0, (double *)k.out1)
-                     : run((const double *)k.in0, (const double *)k.in1, (float *)k.out0, (float *)k.out1);
-  return k.out_f64 ? run((const float *)k.in0, (const float *)k.in1, (double *)k.out0, (double *)k.out1)
-                   : run((const float *)k.in0, (const float *)k.in1, (float *)k.out0, (float *)k.out1);
-}
-
-// the argument lists of the four older entries as a direct-sum call
-gwen_sht_call direct_call(int op, const void *in0, const void *in1, int in_f64, void *out0, void *out1, int out_f64,
-                          const double *nodes, const double *lat_w, const double *twiddle, const double *seed, int grid,
-                          int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
-                          void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  gwen_sht_call k;
-  k.op = op;
-  k.longitude = GWEN_SHT_LON_DIRECT;
-  k.in0 = in0;
-  k.in1 = in1;
-  k.in_f64 = in_f64;
-  k.out0 = out0;
-  k.out1 = out1;
-  k.out_f64 = out_f64;
-  k.nodes = nodes;
-  k.lat_w = lat_w;
-  k.twiddle = twiddle;
-  k.seed = seed;
-  k.grid = grid;
-  k.adjoint = adjoint;
-  k.batch = batch;
-  k.nlat = nlat;
-  k.nlon = nlon;
-  k.lmax = lmax;
-  k.C = C;
-  k.workspace = workspace;
-  k.workspace_bytes = workspace_bytes;
-  k.stream = stream;
-  return k;
-}
-
+// gwen_sht_transform and gwen_sht_rings_transform: the checks, then the op in the call's two dtypes
 int transform(const gwen_sht_call &k, const Rings *rings) {
-  switch (k.op) {
-    case GWEN_SHT_OP_ANALYSIS: return scalar_analysis(k, rings);
-    case GWEN_SHT_OP_SYNTHESIS: return scalar_synthesis(k, rings);
-    case GWEN_SHT_OP_VECTOR_ANALYSIS: return vector_analysis_call(k, rings);
-    case GWEN_SHT_OP_VECTOR_SYNTHESIS: return vector_synthesis_call(k, rings);
-  }
-  return GWEN_EINVAL;
+  if (k.op < GWEN_SHT_OP_ANALYSIS || k.op > GWEN_SHT_OP_VECTOR_SYNTHESIS) return GWEN_EINVAL;
+  Shape s;
+  int64_t chunk;
+  const int rc = check_call(k, rings, s, chunk);
+  if (rc || k.batch == 0) return rc;
+  const auto run = [&](auto in, auto out) {
+    using TIn = decltype(in);
+    using TOut = decltype(out);
+    switch (k.op) {
+      case GWEN_SHT_OP_ANALYSIS: return analysis<false, TIn, TOut>(s, k, chunk);
+      case GWEN_SHT_OP_SYNTHESIS: return synthesis<false, TIn, TOut>(s, k, chunk);
+      case GWEN_SHT_OP_VECTOR_ANALYSIS: return analysis<true, TIn, TOut>(s, k, chunk);
+      default: return synthesis<true, TIn, TOut>(s, k, chunk);
+    }
+  };
+  if (k.in_f64) return k.out_f64 ? run(double(), double()) : run(double(), float());
+  return k.out_f64 ? run(float(), double()) : run(float(), float());
 }
 
 }  // namespace
@@ -1122,10 +970,29 @@ int gwen_sht_transform(const gwen_sht_call *call) {
 
 int gwen_sht_rings_transform(const gwen_sht_rings_call *call) {
   if (!call) return GWEN_EINVAL;
-  const gwen_sht_call k = direct_call(call->op, call->in0, call->in1, call->in_f64, call->out0, call->out1, call->out_f64,
-                                      call->nodes, call->lat_w, call->twiddle, call->seed, GWEN_SHT_GAUSS, call->batch,
-                                      call->nlat, call->max_nlon, call->lmax, call->C, call->adjoint, call->workspace,
-                                      call->workspace_bytes, call->stream);
+  gwen_sht_call k = {};
+  k.op = call->op;
+  k.longitude = GWEN_SHT_LON_DIRECT;
+  k.in0 = call->in0;
+  k.in1 = call->in1;
+  k.in_f64 = call->in_f64;
+  k.out0 = call->out0;
+  k.out1 = call->out1;
+  k.out_f64 = call->out_f64;
+  k.nodes = call->nodes;
+  k.lat_w = call->lat_w;
+  k.twiddle = call->twiddle;
+  k.seed = call->seed;
+  k.grid = GWEN_SHT_GAUSS;
+  k.adjoint = call->adjoint;
+  k.batch = call->batch;
+  k.nlat = call->nlat;
+  k.nlon = call->max_nlon;
+  k.lmax = call->lmax;
+  k.C = call->C;
+  k.workspace = call->workspace;
+  k.workspace_bytes = call->workspace_bytes;
+  k.stream = call->stream;
   const Rings rings = {call->ring_nlon, call->ring_start, call->points};
   return transform(k, &rings);
 }
@@ -1147,18 +1014,60 @@ int gwen_sht_vector_analysis(const void *u, const void *v, int x_f64, void *vort
                              const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
                              int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
                              void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  const gwen_sht_call k = direct_call(GWEN_SHT_OP_VECTOR_ANALYSIS, u, v, x_f64, vort, div, coef_f64, nodes, lat_w, twiddle,
-                                      seed, grid, batch, nlat, nlon, lmax, C, adjoint, workspace, workspace_bytes, stream);
-  return gwen_sht_transform(&k);
+  gwen_sht_call k = {};
+  k.op = GWEN_SHT_OP_VECTOR_ANALYSIS;
+  k.longitude = GWEN_SHT_LON_DIRECT;
+  k.in0 = u;
+  k.in1 = v;
+  k.in_f64 = x_f64;
+  k.out0 = vort;
+  k.out1 = div;
+  k.out_f64 = coef_f64;
+  k.nodes = nodes;
+  k.lat_w = lat_w;
+  k.twiddle = twiddle;
+  k.seed = seed;
+  k.grid = grid;
+  k.adjoint = adjoint;
+  k.batch = batch;
+  k.nlat = nlat;
+  k.nlon = nlon;
+  k.lmax = lmax;
+  k.C = C;
+  k.workspace = workspace;
+  k.workspace_bytes = workspace_bytes;
+  k.stream = stream;
+  return transform(k, nullptr);
 }
 
 int gwen_sht_vector_synthesis(const void *vort, const void *div, int coef_f64, void *u, void *v, int x_f64,
                               const double *nodes, const double *lat_w, const double *twiddle, const double *seed,
                               int grid, int64_t batch, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, int adjoint,
                               void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  const gwen_sht_call k = direct_call(GWEN_SHT_OP_VECTOR_SYNTHESIS, vort, div, coef_f64, u, v, x_f64, nodes, lat_w, twiddle,
-                                      seed, grid, batch, nlat, nlon, lmax, C, adjoint, workspace, workspace_bytes, stream);
-  return gwen_sht_transform(&k);
+  gwen_sht_call k = {};
+  k.op = GWEN_SHT_OP_VECTOR_SYNTHESIS;
+  k.longitude = GWEN_SHT_LON_DIRECT;
+  k.in0 = vort;
+  k.in1 = div;
+  k.in_f64 = coef_f64;
+  k.out0 = u;
+  k.out1 = v;
+  k.out_f64 = x_f64;
+  k.nodes = nodes;
+  k.lat_w = lat_w;
+  k.twiddle = twiddle;
+  k.seed = seed;
+  k.grid = grid;
+  k.adjoint = adjoint;
+  k.batch = batch;
+  k.nlat = nlat;
+  k.nlon = nlon;
+  k.lmax = lmax;
+  k.C = C;
+  k.workspace = workspace;
+  k.workspace_bytes = workspace_bytes;
+  k.stream = stream;
+  return transform(k, nullptr);
 }
 
 int64_t gwen_sht_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C) {
@@ -1169,19 +1078,53 @@ int64_t gwen_sht_workspace_bytes(int grid, int64_t nlat, int64_t nlon, int64_t l
 int gwen_sht_analysis(const void *x, int x_f64, void *coef, int coef_f64, const double *nodes, const double *lat_w,
                       const double *twiddle, const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon,
                       int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  const gwen_sht_call k = direct_call(GWEN_SHT_OP_ANALYSIS, x, nullptr, x_f64, coef, nullptr, coef_f64, nodes, lat_w,
-                                      twiddle, seed, grid, batch, nlat, nlon, lmax, C, 0, workspace, workspace_bytes,
-                                      stream);
-  return gwen_sht_transform(&k);
+  gwen_sht_call k = {};                                   // in1, out1 and adjoint are not the scalar transforms'
+  k.op = GWEN_SHT_OP_ANALYSIS;
+  k.longitude = GWEN_SHT_LON_DIRECT;
+  k.in0 = x;
+  k.in_f64 = x_f64;
+  k.out0 = coef;
+  k.out_f64 = coef_f64;
+  k.nodes = nodes;
+  k.lat_w = lat_w;
+  k.twiddle = twiddle;
+  k.seed = seed;
+  k.grid = grid;
+  k.batch = batch;
+  k.nlat = nlat;
+  k.nlon = nlon;
+  k.lmax = lmax;
+  k.C = C;
+  k.workspace = workspace;
+  k.workspace_bytes = workspace_bytes;
+  k.stream = stream;
+  return transform(k, nullptr);
 }
 
 int gwen_sht_synthesis(const void *coef, int coef_f64, void *x, int x_f64, const double *nodes, const double *lat_w,
                        const double *twiddle, const double *seed, int grid, int64_t batch, int64_t nlat, int64_t nlon,
                        int64_t lmax, int64_t C, void *workspace, size_t workspace_bytes, gwen_stream_t stream) {
-  const gwen_sht_call k = direct_call(GWEN_SHT_OP_SYNTHESIS, coef, nullptr, coef_f64, x, nullptr, x_f64, nodes, lat_w,
-                                      twiddle, seed, grid, batch, nlat, nlon, lmax, C, 0, workspace, workspace_bytes,
-                                      stream);
-  return gwen_sht_transform(&k);
+  gwen_sht_call k = {};
+  k.op = GWEN_SHT_OP_SYNTHESIS;
+  k.longitude = GWEN_SHT_LON_DIRECT;
+  k.in0 = coef;
+  k.in_f64 = coef_f64;
+  k.out0 = x;
+  k.out_f64 = x_f64;
+  k.nodes = nodes;
+  k.lat_w = lat_w;
+  k.twiddle = twiddle;
+  k.seed = seed;
+  k.grid = grid;
+  k.batch = batch;
+  k.nlat = nlat;
+  k.nlon = nlon;
+  k.lmax = lmax;
+  k.C = C;
+  k.workspace = workspace;
+  k.workspace_bytes = workspace_bytes;
+  k.stream = stream;
+  return transform(k, nullptr);
 }
 
 int gwen_sht_power_f64(const double *coef, double *power, int64_t batch, int64_t lmax, int64_t C,
