@@ -21,7 +21,7 @@ from .products import ensemble_products, ensemble_quantiles, exceedance_probabil
 from .gridgraph import containing_faces, grid_graphs, latlon_grid, radius_edges, sphere_points
 from .regrid import (Regridder, cell_areas, cell_overlaps, latlon_cells, mesh_cells, mesh_dual_cells,
                      nearest_neighbours)
-from .spectral import SphericalHarmonics, check_rings, octahedral_nlon
+from .spectral import SphericalHarmonics, check_rings, octahedral_nlon, ring_fft_plan
 from .sfno import SFNO, SFNOBlock, SpectralConv, spectral_conv, spectral_conv_supported
 from .graph import GraphCSR, GraphCache, default_cache, prepare_graph
 from .mesh import Mesh, complete_graph, geodesic_mesh
@@ -37,7 +37,7 @@ __all__ = [
     "ensemble_products", "ensemble_quantiles", "exceedance_probability", "rank_histogram",
     "sphere_points", "latlon_grid", "radius_edges", "containing_faces", "grid_graphs", "ForcingClock",
     "Regridder", "nearest_neighbours", "mesh_cells", "mesh_dual_cells", "latlon_cells", "cell_areas", "cell_overlaps", "checkpointed_step", "CRPSLoss", "EnsembleVarRegLoss", "MaskedLoss",
-    "SphericalHarmonics", "octahedral_nlon", "check_rings", "SFNO", "SFNOBlock", "SpectralConv", "spectral_conv", "spectral_conv_supported",
+    "SphericalHarmonics", "octahedral_nlon", "check_rings", "ring_fft_plan", "SFNO", "SFNOBlock", "SpectralConv", "spectral_conv", "spectral_conv_supported",
     "BaseNet", "Encoder", "Decoder", "UNet",
 ]
 __version__ = "0.1.0"

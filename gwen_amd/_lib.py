@@ -86,6 +86,12 @@ class ShtRingsCall(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+class ShtRingsFftCall(C.Structure):
+    """gwen_sht_rings_fft_call (include/gwen_hip.h)."""
+    _fields_ = [("rings", ShtRingsCall), ("ring_plan", C.c_void_p), ("chirp", C.c_void_p), ("filter", C.c_void_p),
+                ("conv_twiddle", C.c_void_p), ("max_points", C.c_int64)]
+
+
 ORDER_AUTO, ORDER_TRANSFORM_FIRST, ORDER_AGGREGATE_FIRST, ORDER_FUSED, ORDER_FUSED_EXACT = -1, 0, 1, 2, 3
 CONTRACT_BF16X3, CONTRACT_F32, CONTRACT_BF16X6, CONTRACT_F16X3 = 0, 1, 2, 3          # GWEN_CONTRACT_* (include/gwen_hip.h)
 CONTRACT_NAMES = {"3xbf16": CONTRACT_BF16X3, "bf16x3": CONTRACT_BF16X3, "fp32": CONTRACT_F32, "bf16x6": CONTRACT_BF16X6,
@@ -114,6 +120,7 @@ CONSERVE_COVERED, CONSERVE_CELL = 0, 1               # GWEN_CONSERVE_*
 SHT_GRIDS = {"equiangular": 0, "equiangular-centred": 1, "gauss": 2}     # GWEN_SHT_* (include/gwen_hip.h)
 SHT_OP_ANALYSIS, SHT_OP_SYNTHESIS, SHT_OP_VECTOR_ANALYSIS, SHT_OP_VECTOR_SYNTHESIS = 0, 1, 2, 3     # GWEN_SHT_OP_*
 SHT_LONGITUDE = {"direct": 0, "fft": 1}                                   # GWEN_SHT_LON_*
+SHT_RING_KINDS = {0: None, 1: "mixed", 2: "bluestein"}                    # what gwen_sht_ring_fft_plan returns
 CONV_AFFINE, CONV_RELU, CONV_POOL = 1, 2, 4                               # GWEN_CONV_*
 KIND_NAMES = {KIND_PROPAGATE: "propagate", KIND_LINEAR: "linear", KIND_LAYER: "layer",
               KIND_CHAIN: "chain", KIND_SMALL: "small", KIND_WIDE: "wide"}
@@ -317,6 +324,8 @@ SIGNATURES = {
     "gwen_sht_fft_supported": (_int, [_i64]),
     "gwen_sht_rings_transform": (_int, [C.POINTER(ShtRingsCall)]),
     "gwen_sht_rings_workspace_bytes": (_i64, [_int, _i64, _i64, _i64, _i64, _i64]),
+    "gwen_sht_rings_fft_transform": (_int, [C.POINTER(ShtRingsFftCall)]),
+    "gwen_sht_ring_fft_plan": (_int, [_i64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "gwen_spectral_conv_supported": (_int, [_i64, _i64, _int]),
     "gwen_spectral_conv_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp]),
     "gwen_spectral_conv_grad_weight_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _vp]),

@@ -20,7 +20,9 @@
 //
 // On a reduced Gaussian grid (gwen_sht_rings_transform: a ring length of its own on every latitude) they are
 // k_sht_rings_lon_fwd and k_sht_rings_lon_inv ("reduced grids" below): the direct sums of the regular grid -- lon_sums()
-// and lon_synthesis(), the one copy of either loop -- one ring a block.
+// and lon_synthesis(), the one copy of either loop -- one ring a block; or, on request (gwen_sht_rings_fft_transform),
+// k_sht_rings_lon_fft_fwd and k_sht_rings_lon_fft_inv of sht_fft.h, one FFT a ring, item and channel whatever the ring's
+// length.
 //
 // The vector transforms, (u, v) <-> (vort, div), run the same longitude kernels on u and on v (ring [2, chunk, ...]) and
 // the latitude kernels k_vsht_lat_fwd and k_vsht_lat_inv, with two Legendre tables and four columns where the scalar
@@ -173,12 +175,8 @@ __global__ __launch_bounds__(kThreads) void k_sht_lon_inv(const double *__restri
 // columns of the orders above M_j (the latitude kernels read every column, and the workspace arrives uninitialised); the
 // inverse kernel does not read them.
 
-// The ring of the b-th row of blocks: from the equator outwards, nlat / 2, nlat / 2 - 1, nlat / 2 + 1, ...  On a reduced
-// Gaussian grid that is the longest rings first, so the short polar rings fill the tail of the launch.
-__device__ __forceinline__ int ring_of(int b, int nlat) {
-  const int h = nlat >> 1;
-  return b & 1 ? h - ((b + 1) >> 1) : h + (b >> 1);
-}
+// Rows of blocks take the rings from the equator outwards (ring_of(), sht_fft.h).
+using sht_fft::ring_of;
 
 template <typename TIn>
 __global__ __launch_bounds__(kThreads) void k_sht_rings_lon_fwd(const TIn *__restrict__ x, const dpair *__restrict__ tw,
@@ -691,6 +689,8 @@ struct Shape {
   int64_t points;                // grid points of an item: nlat nlon, or the sum of the ring lengths
   const int *ring_nlon;          // a reduced grid (check_rings_shape): the device tables of the ring lengths [nlat] and
   const int64_t *ring_start;     // starts [nlat + 1]; nlon is then the longest ring.  NULL on a regular grid
+  sht_fft::RingTables ring_fft;  // a reduced grid with one FFT a ring (gwen_sht_rings_fft_transform); plan NULL without
+  int ring_lds_slots;            // the complex LDS slots of a block of its kernels
 };
 
 // The device tables and the point count of a reduced grid, the fields of gwen_sht_rings_call that gwen_sht_call lacks.
@@ -698,6 +698,7 @@ struct Rings {
   const int *nlon;
   const int64_t *start;
   int64_t points;
+  const gwen_sht_rings_fft_call *fft;      // the call that asks for one FFT a ring, for its plan records and tables, or NULL
 };
 
 // the sizes and tile counts of checked arguments; nlon is the longest ring of a reduced grid
@@ -731,6 +732,8 @@ int check_shape(int grid, int64_t nlat, int64_t nlon, int64_t lmax, int64_t C, S
   s.points = nlat * nlon;
   s.ring_nlon = nullptr;
   s.ring_start = nullptr;
+  s.ring_fft = {};
+  s.ring_lds_slots = 0;
   if (longitude == GWEN_SHT_LON_FFT) {
     if (!sht_fft::supported(nlon)) return GWEN_EINVAL;
     s.fft = sht_fft::make_plan(s.nlon, s.C);
@@ -761,6 +764,23 @@ int check_rings_shape(const Rings &r, int64_t nlat, int64_t max_nlon, int64_t lm
   s.points = r.points;
   s.ring_nlon = r.nlon;
   s.ring_start = r.start;
+  s.ring_fft = {};
+  s.ring_lds_slots = 0;
+  if (r.fft) {
+    // blocks (ring, item, channel tile) with the tile of the ring that has the most points in LDS, the rows rounded up to
+    // the XCD count
+    const int64_t most = r.fft->max_points;
+    if (most < 1 || most > sht_fft::kPoints) return GWEN_EINVAL;
+    const int tile = 1 << sht_fft::tile_log2_of((int)most, s.C);
+    s.fft_ctiles = (s.C + tile - 1) / tile;
+    s.ring_lds_slots = sht_fft::ring_lds_slots((int)most, s.C);
+    s.item_blocks = (nlat + sht_fft::kXcds - 1) * (int64_t)s.fft_ctiles;
+    if (lat > s.item_blocks) s.item_blocks = lat;
+    s.ring_fft = {reinterpret_cast<const sht_fft::RingPlan *>(r.fft->ring_plan),
+                  reinterpret_cast<const sht_fft::cpx *>(r.fft->chirp),
+                  reinterpret_cast<const sht_fft::cpx *>(r.fft->filter),
+                  reinterpret_cast<const sht_fft::cpx *>(r.fft->conv_twiddle)};
+  }
   return 0;
 }
 
@@ -794,6 +814,13 @@ int check_call(const gwen_sht_call &k, const Rings *rings, Shape &s, int64_t &ch
   if (k.batch == 0) return 0;
   if (rings && !(rings->nlon && rings->start && gwen_aligned(rings->nlon, 4) && gwen_aligned(rings->start, 8)))
     return GWEN_EINVAL;
+  if (rings && rings->fft) {
+    const gwen_sht_rings_fft_call &f = *rings->fft;
+    if (!f.ring_plan || !f.chirp || !f.filter || !f.conv_twiddle) return GWEN_EINVAL;
+    if (!gwen_aligned(f.ring_plan, 16) || !gwen_aligned(f.chirp, 16) || !gwen_aligned(f.filter, 16) ||
+        !gwen_aligned(f.conv_twiddle, 16))
+      return GWEN_EINVAL;
+  }
   const void *in1 = vec ? k.in1 : k.in0, *out1 = vec ? k.out1 : k.out0;
   if (in_optional ? !k.in0 && !in1 : !k.in0 || !in1) return GWEN_EINVAL;
   if (!k.out0 || !out1 || !k.nodes || !k.twiddle || !k.seed || !k.workspace) return GWEN_EINVAL;
@@ -827,11 +854,26 @@ int fft_launch(const Shape &s, Kernel *kernel, int64_t rings, dim3 &grid, size_t
   return allow_dynamic_lds(kernel, lds);
 }
 
+// the grid and the dynamic LDS of a ragged FFT longitude kernel over nb items
+template <typename Kernel>
+int rings_fft_launch(const Shape &s, Kernel *kernel, int64_t nb, dim3 &grid, size_t &lds) {
+  grid = dim3((unsigned)sht_fft::grid_blocks(nb * s.nlat, s.fft_ctiles));      // <= nb item_blocks
+  lds = sizeof(sht_fft::cpx) * (size_t)s.ring_lds_slots;
+  return allow_dynamic_lds(kernel, lds);
+}
+
 // The longitude stage of nb items: the direct sums or the FFT, as the shape says.
 template <typename TIn>
 int lon_fwd(const Shape &s, const TIn *x, const double *tw, double *ring, int64_t nb, hipStream_t st) {
   const int64_t rows = nb * s.nlat * s.C;
-  if (s.ring_nlon) {
+  if (s.ring_fft.plan) {
+    dim3 grid;
+    size_t lds;
+    if (const int rc = rings_fft_launch(s, &sht_fft::k_sht_rings_lon_fft_fwd<TIn>, nb, grid, lds)) return rc;
+    sht_fft::k_sht_rings_lon_fft_fwd<TIn><<<grid, dim3(sht_fft::kThreads), lds, st>>>(
+        x, reinterpret_cast<const sht_fft::cpx *>(tw), s.ring_nlon, s.ring_start, s.ring_fft, ring, nb * s.nlat,
+        s.points, s.nlat, (int)nb, s.L, s.C, s.fft_ctiles, s.ring_lds_slots);
+  } else if (s.ring_nlon) {
     const int64_t lanes = nb * s.C, ltiles = (lanes + 63) / 64;      // nlat ltiles mtiles <= nb item_blocks
     k_sht_rings_lon_fwd<TIn><<<dim3((unsigned)(s.nlat * ltiles * s.mtiles)), dim3(kThreads), 0, st>>>(
         x, reinterpret_cast<const dpair *>(tw), s.ring_nlon, s.ring_start, ring, lanes, s.points, s.nlat, s.L, s.C,
@@ -854,7 +896,14 @@ template <typename TOut>
 int lon_inv(const Shape &s, const double *ring, const double *tw, const double *lat_w, TOut *x, int64_t nb,
             hipStream_t st) {
   const int64_t rows = nb * s.nlat * s.C;
-  if (s.ring_nlon) {
+  if (s.ring_fft.plan) {
+    dim3 grid;
+    size_t lds;
+    if (const int rc = rings_fft_launch(s, &sht_fft::k_sht_rings_lon_fft_inv<TOut>, nb, grid, lds)) return rc;
+    sht_fft::k_sht_rings_lon_fft_inv<TOut><<<grid, dim3(sht_fft::kThreads), lds, st>>>(
+        ring, reinterpret_cast<const sht_fft::cpx *>(tw), s.ring_nlon, s.ring_start, s.ring_fft, lat_w, x, nb * s.nlat,
+        s.points, s.nlat, (int)nb, s.L, s.C, s.fft_ctiles, s.ring_lds_slots);
+  } else if (s.ring_nlon) {
     const int64_t lanes = nb * s.C, ltiles = (lanes + 63) / 64;
     k_sht_rings_lon_inv<TOut><<<dim3((unsigned)(s.nlat * ltiles * s.itiles)), dim3(kThreads), 0, st>>>(
         ring, reinterpret_cast<const dpair *>(tw), s.ring_nlon, s.ring_start, lat_w, x, lanes, s.points, s.nlat, s.L,
@@ -957,19 +1006,8 @@ int transform(const gwen_sht_call &k, const Rings *rings) {
   return k.out_f64 ? run(float(), double()) : run(float(), float());
 }
 
-}  // namespace
-
-extern "C" {
-
-int gwen_sht_fft_supported(int64_t nlon) { return sht_fft::supported(nlon) ? 1 : 0; }
-
-int gwen_sht_transform(const gwen_sht_call *call) {
-  if (!call) return GWEN_EINVAL;
-  return transform(*call, nullptr);
-}
-
-int gwen_sht_rings_transform(const gwen_sht_rings_call *call) {
-  if (!call) return GWEN_EINVAL;
+// the fields that a reduced grid's call shares with gwen_sht_call; nlon is its longest ring
+gwen_sht_call rings_as_call(const gwen_sht_rings_call *call) {
   gwen_sht_call k = {};
   k.op = call->op;
   k.longitude = GWEN_SHT_LON_DIRECT;
@@ -993,14 +1031,48 @@ int gwen_sht_rings_transform(const gwen_sht_rings_call *call) {
   k.workspace = call->workspace;
   k.workspace_bytes = call->workspace_bytes;
   k.stream = call->stream;
-  const Rings rings = {call->ring_nlon, call->ring_start, call->points};
-  return transform(k, &rings);
+  return k;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gwen_sht_fft_supported(int64_t nlon) { return sht_fft::supported(nlon) ? 1 : 0; }
+
+int gwen_sht_transform(const gwen_sht_call *call) {
+  if (!call) return GWEN_EINVAL;
+  return transform(*call, nullptr);
+}
+
+int gwen_sht_rings_transform(const gwen_sht_rings_call *call) {
+  if (!call) return GWEN_EINVAL;
+  const Rings rings = {call->ring_nlon, call->ring_start, call->points, nullptr};
+  return transform(rings_as_call(call), &rings);
+}
+
+int gwen_sht_ring_fft_plan(int64_t nlon, int64_t *n, int64_t *M) {
+  if (!n || !M || nlon < 1 || nlon > 2 * (int64_t)sht_fft::kPoints) return 0;
+  *n = nlon % 2 == 0 ? nlon / 2 : nlon;
+  *M = 0;
+  if (sht_fft::supported(nlon)) return sht_fft::kRingMixed;
+  int64_t m = 2 * *n - 1;
+  while (m <= sht_fft::kPoints && !sht_fft::supported(m)) ++m;
+  if (m > sht_fft::kPoints) return 0;
+  *M = m;
+  return sht_fft::kRingBluestein;
+}
+
+int gwen_sht_rings_fft_transform(const gwen_sht_rings_fft_call *call) {
+  if (!call) return GWEN_EINVAL;
+  const Rings rings = {call->rings.ring_nlon, call->rings.ring_start, call->rings.points, call};
+  return transform(rings_as_call(&call->rings), &rings);
 }
 
 int64_t gwen_sht_rings_workspace_bytes(int vector, int64_t nlat, int64_t points, int64_t max_nlon, int64_t lmax,
                                        int64_t C) {
   Shape s;
-  const Rings rings = {nullptr, nullptr, points};
+  const Rings rings = {nullptr, nullptr, points, nullptr};
   if ((vector != 0 && vector != 1) || check_rings_shape(rings, nlat, max_nlon, lmax, C, s)) return 0;
   return vector ? 2 * s.item_bytes : s.item_bytes;
 }

@@ -56,7 +56,20 @@ O640`` and the classic ``N320`` grids of IFS, ERA5 and AIFS) keep everything abo
                   O8, lmax 7: 4e-15     O8, lmax 11 (M_j down to 9): 6e-15     O16, lmax 15: 4e-14
                   O16, lmax 23: 2e-8    O16, lmax 31: 6e-3
               -- round-off at the cubic pairing ``lmax = N - 1`` (the default of ``octahedral``), degrading beyond it.
-    longitude only ``"direct"``: octahedral ring lengths mostly have prime factors above 5, which the FFT does not take.
+    longitude ``longitude`` is ``"direct"`` only: octahedral ring lengths mostly have prime factors above 5, which the
+              mixed-radix FFT does not take.  The longitude stage of a reduced grid has a keyword of its own,
+              ``ring_longitude``: ``"direct"`` (the default) sums as above, ``"bluestein"`` makes every ring of every item
+              and channel one fp64 FFT in LDS whatever its length (csrc/sht_fft.h) -- the mixed-radix FFT of
+              ``longitude="fft"`` on a ring of ``2^a 3^b 5^c`` points (rings of one such length reproduce
+              ``SphericalHarmonics(nlat, nlon, grid="gauss", longitude="fft")`` bit for bit) and elsewhere Bluestein's
+              chirp-z convolution on the same stages: with ``n = nlon // 2`` (even rings, and a split step) or ``nlon``,
+              ``c_k = exp(-i pi k^2 / n)`` and ``M`` the smallest ``2^a 3^b 5^c >= 2 n - 1``, the ring's DFT is ``c_k``
+              times the cyclic convolution of length ``M`` of ``z c`` with ``conj c``, two FFTs of length ``M`` and three
+              pointwise products.  ``ring_fft_plan(nlon)`` tells how a ring runs; ``M <= 4096``, so even rings up to 4096
+              points and odd ones up to 2048 (any smooth length up to 4096) are taken, ``check_rings`` raising for others.
+              Same truncation, same numbers up to rounding, as reproducible and as NaN-tight as ``longitude="fft"``; no
+              automatic choice and no fallback.  A regular Gauss grid with an ``nlon`` that ``longitude="fft"`` does not
+              take is ``reduced([nlon] * nlat, ..., ring_longitude="bluestein")``.
 
 Everything is accumulated in fp64 by two HIP kernels a transform (csrc/sht.hip): the sums along every latitude ring
 against an ``nlon``-entry twiddle table, and a contraction over the latitudes with ``Pbar_l^m`` generated on the fly (the
@@ -81,6 +94,8 @@ MAX_LMAX = 1023
 MAX_NLAT = 2048
 LONGITUDE = ("direct", "fft")
 MAX_FFT_NLON = 4096
+RING_LONGITUDE = ("direct", "bluestein")
+MAX_RING_FFT_POINTS = 4096                 # complex points of a ring's FFT in LDS (kPoints of csrc/sht_fft.h)
 
 
 def fft_supported(nlon: int) -> bool:
@@ -93,6 +108,76 @@ def fft_supported(nlon: int) -> bool:
         while nlon % f == 0:
             nlon //= f
     return nlon == 1
+
+
+def ring_fft_plan(nlon: int) -> Tuple[Optional[str], int, int]:
+    """``(kind, n, M)``: how ``ring_longitude="bluestein"`` runs a ring of ``nlon`` longitudes (``gwen_sht_ring_fft_plan``).
+    ``n`` is the length of the ring's complex FFT, ``nlon // 2`` for an even ``nlon`` (with a split step) and ``nlon`` for
+    an odd one.  ``kind`` is ``"mixed"`` where ``fft_supported(nlon)`` -- the radix-4/2/3/5 FFT of ``longitude="fft"``,
+    ``M = 0`` -- and ``"bluestein"`` otherwise: a cyclic convolution of length ``M``, the smallest ``2^a 3^b 5^c >= 2 n -
+    1``.  ``kind`` is ``None`` where that ``M`` is above 4096: the ring is not supported."""
+    nlon = int(nlon)
+    if nlon < 1:
+        return None, 0, 0
+    n = nlon // 2 if nlon % 2 == 0 else nlon
+    if fft_supported(nlon):
+        return "mixed", n, 0
+    m = 2 * n - 1
+    while m <= MAX_RING_FFT_POINTS and not fft_supported(m):
+        m += 1
+    if m > MAX_RING_FFT_POINTS:
+        return None, n, 0
+    return "bluestein", n, m
+
+
+def ring_fft_tables(ring_nlon) -> dict:
+    """The host tables of ``ring_longitude="bluestein"`` for supported ring lengths, numpy, one set per distinct length
+    (include/gwen_hip.h, ``gwen_sht_rings_fft_call``):
+
+        ``plan [nlat, 8]`` int32   ``(kind, n, M, chirp_at, filter_at, conv_at, 0, 0)``, kind 1 mixed, 2 Bluestein
+        ``chirp [*, 2]`` fp64      ``c_k = exp(-i pi k^2 / n)``, ``k < n``, the phase index ``k^2 mod 2 n`` in integers
+        ``filter [*, 2]`` fp64     ``H = FFT_M(h) / M`` of ``h_k = conj c_k`` wrapped to ``|k| < n``
+        ``conv_twiddle [*, 2]``    ``(cos, sin)(2 pi k / M)``, ``k < M``, one table per distinct ``M``
+        ``max_points``             the largest ``n`` of a mixed and ``M`` of a Bluestein ring
+
+    Every table has at least one entry, so that its device copy has an address."""
+    rings = np.asarray(ring_nlon, dtype=np.int64)
+    plan = np.zeros((rings.size, 8), dtype=np.int32)
+    chirp, filt, conv = [], [], []
+    at = {"chirp": 0, "filter": 0, "conv": 0}
+    by_length, by_m = {}, {}
+    most = 1
+    for j, nlon in enumerate(rings.tolist()):
+        kind, n, m = ring_fft_plan(nlon)
+        if kind is None:
+            raise ValueError(f'ring_longitude="bluestein" does not take ring_nlon[{j}] = {nlon}')
+        if kind == "mixed":
+            plan[j, :3] = (1, n, 0)
+            most = max(most, n)
+            continue
+        most = max(most, m)
+        if nlon not in by_length:
+            k = np.arange(n, dtype=np.int64)
+            phase = np.pi * ((k * k) % (2 * n)).astype(np.float64) / n
+            c = np.cos(phase) - 1j * np.sin(phase)
+            h = np.zeros(m, dtype=np.complex128)
+            h[:n] = np.conj(c)
+            h[m - n + 1:] = np.conj(c[:0:-1])
+            if m not in by_m:
+                ang = 2.0 * np.pi * np.arange(m, dtype=np.float64) / m
+                conv.append(np.stack([np.cos(ang), np.sin(ang)], axis=1))
+                by_m[m] = at["conv"]
+                at["conv"] += m
+            by_length[nlon] = (at["chirp"], at["filter"], by_m[m])
+            chirp.append(np.stack([c.real, c.imag], axis=1))
+            big = np.fft.fft(h) / m
+            filt.append(np.stack([big.real, big.imag], axis=1))
+            at["chirp"] += n
+            at["filter"] += m
+        plan[j, :6] = (2, n, m) + by_length[nlon]
+    pad = [np.zeros((1, 2))]
+    return {"plan": plan, "chirp": np.concatenate(chirp or pad), "filter": np.concatenate(filt or pad),
+            "conv_twiddle": np.concatenate(conv or pad), "max_points": most}
 
 
 def quadrature(grid: str, nlat: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -182,14 +267,16 @@ def octahedral_nlon(N: int) -> np.ndarray:
     return np.concatenate([half, half[::-1]])
 
 
-def check_rings(ring_nlon, lmax: int, longitude: str = "direct") -> np.ndarray:
+def check_rings(ring_nlon, lmax: int, longitude: str = "direct", ring_longitude: str = "direct") -> np.ndarray:
     """The ring lengths of a reduced grid as an int64 array after every size check (module docstring, "limits");
     ValueError naming the offending value otherwise.  No device is touched."""
     if longitude not in LONGITUDE:
         raise ValueError(f"longitude must be one of {LONGITUDE} (got {longitude!r})")
     if longitude != "direct":
         raise ValueError(f'a reduced grid takes longitude="direct" only: the FFT needs ring lengths 2^a 3^b 5^c '
-                         f"(got longitude = {longitude!r})")
+                         f'(got longitude = {longitude!r}); ring_longitude="bluestein" is the FFT of any ring length')
+    if ring_longitude not in RING_LONGITUDE:
+        raise ValueError(f"ring_longitude must be one of {RING_LONGITUDE} (got {ring_longitude!r})")
     rings = np.asarray(ring_nlon)
     if rings.ndim != 1 or rings.size < 1:
         raise ValueError(f"ring_nlon must be a list of at least one ring length (got shape {rings.shape})")
@@ -217,6 +304,11 @@ def check_rings(ring_nlon, lmax: int, longitude: str = "direct") -> np.ndarray:
         raise ValueError(f"the gauss quadrature on {nlat} latitudes is exact up to lmax = {nlat - 1} (got {lmax})")
     if most < 2 * lmax + 1:
         raise ValueError(f"max(ring_nlon) >= 2 lmax + 1 = {2 * lmax + 1} (got {most})")
+    if ring_longitude == "bluestein":
+        for j, n in enumerate(rings.tolist()):
+            if ring_fft_plan(n)[0] is None:
+                raise ValueError(f'ring_longitude="bluestein" needs a convolution length 2^a 3^b 5^c >= 2 n - 1 of at most '
+                                 f"{MAX_RING_FFT_POINTS} (n = nlon / 2 for an even ring): ring_nlon[{j}] = {n} has none")
     return rings
 
 
@@ -261,33 +353,39 @@ class SphericalHarmonics:
     ``SphericalHarmonics.reduced(ring_nlon, ...)`` and ``SphericalHarmonics.octahedral(N, ...)`` make the object of a
     reduced Gaussian grid (module docstring): ``grid == "reduced-gauss"``, ``nlon is None``, ``rows`` is the number of
     points and every method below works as it does on a regular grid.  ``ring_nlon`` and ``ring_start`` (numpy int64,
-    ``[nlat]`` and ``[nlat + 1]``) are there on every object, constant ``nlon`` on a regular grid."""
+    ``[nlat]`` and ``[nlat + 1]``) are there on every object, constant ``nlon`` on a regular grid; ``ring_longitude`` is
+    the longitude stage of a reduced grid (``RING_LONGITUDE``) and ``None`` on a regular one."""
 
     def __init__(self, nlat: int, nlon: int, device, lmax: Optional[int] = None, grid: str = "equiangular",
                  workspace_bytes: int = 1 << 30, longitude: str = "direct"):
         self.lmax = check_sizes(grid, nlat, nlon, lmax, longitude)
         self.nlat, self.nlon, self.grid, self.longitude = int(nlat), int(nlon), grid, longitude
+        self.ring_longitude = None
         self._setup(np.full(self.nlat, self.nlon, dtype=np.int64), device, workspace_bytes)
 
     @classmethod
     def reduced(cls, ring_nlon, device, lmax: int, workspace_bytes: int = 1 << 30,
-                longitude: str = "direct") -> "SphericalHarmonics":
+                longitude: str = "direct", ring_longitude: str = "direct") -> "SphericalHarmonics":
         """The transforms of the reduced Gaussian grid with ``ring_nlon[j]`` longitudes on Gauss latitude ``j``, south to
-        north, truncated at ``lmax`` (module docstring, "Reduced Gaussian grids"; ``check_rings`` has the limits)."""
-        rings = check_rings(ring_nlon, lmax, longitude)
+        north, truncated at ``lmax`` (module docstring, "Reduced Gaussian grids"; ``check_rings`` has the limits).
+        ``ring_longitude`` chooses the longitude stage of every transform of the object: the ``"direct"`` sums or, with
+        ``"bluestein"``, one FFT a ring (``ring_fft_plan``)."""
+        rings = check_rings(ring_nlon, lmax, longitude, ring_longitude)
         self = cls.__new__(cls)
         self.lmax = int(lmax)
         self.nlat, self.nlon, self.grid, self.longitude = int(rings.size), None, "reduced-gauss", longitude
+        self.ring_longitude = ring_longitude
         self._setup(rings, device, workspace_bytes)
         return self
 
     @classmethod
     def octahedral(cls, N: int, device, lmax: Optional[int] = None, workspace_bytes: int = 1 << 30,
-                   longitude: str = "direct") -> "SphericalHarmonics":
+                   longitude: str = "direct", ring_longitude: str = "direct") -> "SphericalHarmonics":
         """``reduced(octahedral_nlon(N), ...)``: the octahedral grid ``O<N>``.  ``lmax`` defaults to ``N - 1``, the cubic
         pairing, at which the round trip of a band-limited field is at round-off."""
         rings = octahedral_nlon(N)
-        return cls.reduced(rings, device, int(N) - 1 if lmax is None else lmax, workspace_bytes, longitude)
+        return cls.reduced(rings, device, int(N) - 1 if lmax is None else lmax, workspace_bytes, longitude,
+                           ring_longitude)
 
     def _setup(self, rings: np.ndarray, device, workspace_bytes: int) -> None:
         """The tables of ``nlat`` rings of ``rings[j]`` longitudes; a regular grid keeps one ring's twiddle table, a
@@ -321,6 +419,10 @@ class SphericalHarmonics:
         if reduced:
             self._ring_nlon = torch.from_numpy(rings.astype(np.int32)).to(dev)
             self._ring_start = torch.from_numpy(self.ring_start).to(dev)
+        if self.ring_longitude == "bluestein":
+            tables = ring_fft_tables(rings)
+            self._ring_fft_points = int(tables.pop("max_points"))
+            self._ring_fft = {name: torch.from_numpy(np.ascontiguousarray(t)).to(dev) for name, t in tables.items()}
         self._degrees = torch.from_numpy(degree_index(self.lmax)).to(dev)
         big = (self._degrees * (self._degrees + 1)).to(torch.float64)
         self._lap = -big[:, None]                                # [T, 1]: the Laplacian's factor of every row
@@ -412,7 +514,7 @@ class SphericalHarmonics:
 
         src = ins[0] if ins[0] is not None else ins[1]
         if self.nlon is None:
-            call = _lib.ShtRingsCall(
+            rings = _lib.ShtRingsCall(
                 op=op, adjoint=int(adjoint), in0=ptr(ins[0]), in1=ptr(ins[1]), in_f64=int(src.dtype == torch.float64),
                 out0=ptr(outs[0]), out1=ptr(outs[1]), out_f64=int(outs[0].dtype == torch.float64),
                 nodes=ptr(self._nodes), lat_w=ptr(self._lat_w) if weighted else None, twiddle=ptr(self._twiddle),
@@ -420,8 +522,17 @@ class SphericalHarmonics:
                 nlat=self.nlat, points=self.rows, max_nlon=int(self.ring_nlon.max()), lmax=self.lmax, C=c,
                 workspace=ptr(ws), workspace_bytes=ws.numel() * 8,
                 stream=torch.cuda.current_stream(self.device).cuda_stream)
+            if self.ring_longitude == "bluestein":
+                t = self._ring_fft
+                call = _lib.ShtRingsFftCall(rings=rings, ring_plan=ptr(t["plan"]), chirp=ptr(t["chirp"]),
+                                            filter=ptr(t["filter"]), conv_twiddle=ptr(t["conv_twiddle"]),
+                                            max_points=self._ring_fft_points)
+                with torch.cuda.device(self.device):
+                    rc = _lib.lib().gwen_sht_rings_fft_transform(call)
+                _lib.check(rc, f"gwen_sht_rings_fft_transform(op={op})")
+                return
             with torch.cuda.device(self.device):
-                rc = _lib.lib().gwen_sht_rings_transform(call)
+                rc = _lib.lib().gwen_sht_rings_transform(rings)
             _lib.check(rc, f"gwen_sht_rings_transform(op={op})")
             return
         call = _lib.ShtCall(

@@ -1371,6 +1371,39 @@ int gwen_sht_rings_transform(const gwen_sht_rings_call *call);
 int64_t gwen_sht_rings_workspace_bytes(int vector, int64_t nlat, int64_t points, int64_t max_nlon, int64_t lmax,
                                        int64_t C);
 
+/* The same transforms with one fp64 FFT a ring, item and channel in LDS as the longitude stage, whatever the ring's length
+ * (csrc/sht_fft.h; gwen_amd.spectral, ring_longitude="bluestein").  `rings` is the call above, field for field: the
+ * tables, the truncation, the workspace (gwen_sht_rings_workspace_bytes) and the latitude kernels are the same, and the
+ * results agree with gwen_sht_rings_transform to rounding.
+ *
+ *   gwen_sht_ring_fft_plan(nlon, &n, &M): how a ring of nlon longitudes runs -- n = nlon / 2 for an even nlon (the FFT of
+ *         z[k] = x[2k] + i x[2k + 1] and a split step), n = nlon for an odd one.  1 (mixed): gwen_sht_fft_supported(nlon),
+ *         the radix-4/2/3/5 FFT of gwen_sht_transform(GWEN_SHT_LON_FFT) on the ring's own slice of `twiddle`, M = 0; rings
+ *         of one such length give the bits of that call on GWEN_SHT_GAUSS.  2 (Bluestein): any other nlon, as a cyclic
+ *         convolution of length M, the smallest 2^a 3^b 5^c >= 2 n - 1, where M <= 4096.  0: no such M (or nlon < 1, or a
+ *         NULL n or M), the ring is not supported.  No HIP call.
+ *   ring_plan [nlat, 8] int32, 16-byte aligned: (kind, n, M, chirp_at, filter_at, conv_at, 0, 0) of ring j -- the three
+ *         numbers above and, for a Bluestein ring, the complex entry at which its slices of the three tables start.
+ *   chirp [*, 2] fp64: a slice of n entries, c_k = exp(-i pi k^2 / n) as (re, im).
+ *   filter [*, 2] fp64: a slice of M entries, H = FFT_M(h) / M (forward, exp(-i ...)) of h_k = conj c_k at k = 0 ... n - 1
+ *         and at M - k, zero elsewhere.  The synthesis uses conj c and conj H.
+ *   conv_twiddle [*, 2] fp64: a slice of M entries, (cos, sin)(2 pi k / M).  All three 16-byte aligned, never NULL (a
+ *         grid of mixed rings alone passes tables that nothing reads).
+ *   max_points: the largest of n (mixed rings) and M (Bluestein rings), 1 ... 4096: it sizes the grid and the LDS.
+ *   Reproducibility and NaN containment as gwen_sht_transform(GWEN_SHT_LON_FFT): nothing is packed across channels, the
+ *   schedule of a ring is fixed by its length, no atomics.  Errors as gwen_sht_rings_transform, with GWEN_EINVAL for a
+ *   max_points out of range and for a missing or misaligned ring_plan or table, all before any HIP call.  The CONTENTS
+ *   of ring_plan are the caller's responsibility as those of the ring tables are; a block whose record does not fit
+ *   its ring's length or the launch's LDS stores nothing. */
+typedef struct gwen_sht_rings_fft_call {
+  gwen_sht_rings_call rings;
+  const int32_t *ring_plan;
+  const double *chirp, *filter, *conv_twiddle;
+  int64_t max_points;
+} gwen_sht_rings_fft_call;
+int gwen_sht_rings_fft_transform(const gwen_sht_rings_fft_call *call);
+int gwen_sht_ring_fft_plan(int64_t nlon, int64_t *n, int64_t *M);
+
 /* ---------------------------------------------------------------------------------------------
  * Spectral convolution (csrc/spectral_conv.hip, gwen_amd.sfno): the learned map of a spherical Fourier neural operator.
  *

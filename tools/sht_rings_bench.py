@@ -4,9 +4,10 @@ profiles/sht_rings_bench.jsonl.
 
     python tools/sht_rings_bench.py [N] [LMAX] [C] [MEMBERS] [--calls K] [--rounds R]
 
-Three transforms in one process, bracket after bracket in turn, the figure of each the median of its brackets:
+Four transforms in one process, bracket after bracket in turn, the figure of each the median of its brackets:
 
     reduced   ``SphericalHarmonics.octahedral(N, lmax=LMAX)``                                      (ragged direct sums)
+    bluestein the same grid with ``ring_longitude="bluestein"``                                    (one FFT a ring)
     direct    ``SphericalHarmonics(2 N, 4 N + 16, grid="gauss", lmax=LMAX, longitude="direct")``   (the longest ring everywhere)
     fft       the same regular grid with ``longitude="fft"`` (left out where ``4 N + 16`` is not ``2^a 3^b 5^c``)
 
@@ -14,7 +15,8 @@ Four operations, as tools/sht_bench.py: analysis (fp32 coefficients), synthesis,
 The default is O320, lmax 319, 64 channels, 4 members.  ``work_ratio`` is ``sum_j ring_nlon[j] (M_j + 1) / (nlat nlon
 (lmax + 1))``, the reduced grid's share of the regular grid's longitude fma, from the shapes alone;
 ``lon_kernel_ratio`` sets the two ragged longitude kernels' device times (one profiled call of analysis and of
-synthesis) against the regular direct-sum kernels'."""
+synthesis) against the regular direct-sum kernels', ``lon_fft_kernel_ratio`` those of the two ragged FFT kernels against
+the ragged direct sums' and, where the regular grid has an FFT, against the regular FFT kernels'."""
 from __future__ import annotations
 
 import argparse
@@ -93,6 +95,7 @@ def main() -> None:
     nlat, nlon = 2 * a.N, 4 * a.N + 16
     L = a.N - 1 if a.lmax is None else a.lmax
     shs = {"reduced": gwen_amd.SphericalHarmonics.octahedral(a.N, dev, lmax=L),
+           "bluestein": gwen_amd.SphericalHarmonics.octahedral(a.N, dev, lmax=L, ring_longitude="bluestein"),
            "direct": gwen_amd.SphericalHarmonics(nlat, nlon, dev, lmax=L, grid="gauss", longitude="direct")}
     if spectral.fft_supported(nlon):
         shs["fft"] = gwen_amd.SphericalHarmonics(nlat, nlon, dev, lmax=L, grid="gauss", longitude="fft")
@@ -120,22 +123,35 @@ def main() -> None:
     line = {"tool": "sht_rings_bench", "N": a.N, "nlat": nlat, "points": int(rings.sum()), "regular_nlon": nlon,
             "regular_points": nlat * nlon, "lmax": L, "C": C, "members": B, "calls": a.calls, "rounds": a.rounds,
             "truncated_rings": int((orders < L).sum()), "work_ratio": round(work_ratio, 4),
-            "point_ratio": round(float(rings.sum()) / (nlat * nlon), 4)}
+            "point_ratio": round(float(rings.sum()) / (nlat * nlon), 4),
+            "bluestein_rings": int(sum(spectral.ring_fft_plan(n)[0] == "bluestein" for n in rings))}
     for name in ("analysis", "synthesis", "power_spectrum", "analysis_backward"):
         times = alternate([ops[m][name] for m in modes], a.calls, a.rounds, a.warmup)
         us = dict(zip(modes, times))
         line[name] = {f"{m}_us": round(us[m], 1) for m in modes}
         line[name]["reduced_over_direct"] = round(us["reduced"] / us["direct"], 3)
+        line[name]["bluestein_over_reduced"] = round(us["bluestein"] / us["reduced"], 3)
         if "fft" in us:
             line[name]["reduced_over_fft"] = round(us["reduced"] / us["fft"], 3)
+            line[name]["bluestein_over_fft"] = round(us["bluestein"] / us["fft"], 3)
     kernels = {m: kernel_times([ops[m]["analysis"], ops[m]["synthesis"]]) for m in modes}
     line["kernel_us"] = kernels
     pairs = {"fwd": ("k_sht_rings_lon_fwd", "k_sht_lon_fwd"), "inv": ("k_sht_rings_lon_inv", "k_sht_lon_inv")}
     line["lon_kernel_ratio"] = {k: round(kernels["reduced"][r] / kernels["direct"][d], 4) for k, (r, d) in pairs.items()
                                 if kernels["reduced"].get(r) and kernels["direct"].get(d)}
+    ragged = {"fwd": ("k_sht_rings_lon_fft_fwd", "k_sht_rings_lon_fwd", "k_sht_lon_fft_fwd"),
+              "inv": ("k_sht_rings_lon_fft_inv", "k_sht_rings_lon_inv", "k_sht_lon_fft_inv")}
+    line["lon_fft_kernel_ratio"] = {}
+    for k, (b, r, f) in ragged.items():
+        own = kernels["bluestein"].get(b)
+        if own and kernels["reduced"].get(r):
+            line["lon_fft_kernel_ratio"][f"{k}_over_reduced"] = round(own / kernels["reduced"][r], 4)
+        if own and kernels.get("fft", {}).get(f):
+            line["lon_fft_kernel_ratio"][f"{k}_over_fft"] = round(own / kernels["fft"][f], 4)
     # the reduced transform of a band-limited field returns its coefficients
-    back = shs["reduced"].analysis(shs["reduced"].synthesis(coef))
-    line["round_trip_max_abs"] = float((back - coef).abs().max())
+    for m in ("reduced", "bluestein"):
+        back = shs[m].analysis(shs[m].synthesis(coef))
+        line["round_trip_max_abs" if m == "reduced" else "bluestein_round_trip_max_abs"] = float((back - coef).abs().max())
     text = json.dumps(line)
     print(text, flush=True)
     os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
