@@ -7,16 +7,15 @@
 // ~5 M log2(M)^2 / 4 vector instructions per point: 3x fewer at 32 members, 4x at 64).
 // Four launches, no atomics (bitwise reproducible): the weight sums, the pass (per-block per-channel partials), a
 // fixed-order per-channel finish, and the scalar loss.
-#include "common.h"
-
-#include <type_traits>
+// The member chains, the network, the block sums, the pass geometry and the bucket dispatch are csrc/members.h's.
+#include "members.h"
 
 namespace {
 
+using namespace gwen::ens;
+
 constexpr int kThreads = 256;
 constexpr int kMaxChunks = 2048;       // node chunks (blocks along N) of the pass: the partials' row count
-
-__device__ inline float sgnf(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
 
 // ws[0] = sum_n w_n (N without weights), ws[1] = sum_c v_c (C without weights); one block, fixed order
 __global__ __launch_bounds__(1024) void k_ens_weight_sums(const float *__restrict__ node_w, int64_t N,
@@ -28,16 +27,7 @@ __global__ __launch_bounds__(1024) void k_ens_weight_sums(const float *__restric
     for (int64_t i = threadIdx.x; i < N; i += 1024) a += node_w[i];
   if (chan_w)
     for (int64_t i = threadIdx.x; i < C; i += 1024) b += chan_w[i];
-  part[0][threadIdx.x] = a;
-  part[1][threadIdx.x] = b;
-  __syncthreads();
-  for (int s = 512; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) {
-      part[0][threadIdx.x] += part[0][threadIdx.x + s];
-      part[1][threadIdx.x] += part[1][threadIdx.x + s];
-    }
-    __syncthreads();
-  }
+  block_sum<1024>(part, {a, b});
   if (threadIdx.x == 0) {
     ws[0] = node_w ? part[0][0] : (float)N;
     ws[1] = chan_w ? part[1][0] : (float)C;
@@ -50,39 +40,15 @@ __device__ inline float sgn_diff(float a, float b) {
   return __builtin_amdgcn_fmed3f((a - b) * 0x1p126f * 0x1p126f, -1.0f, 1.0f);
 }
 
-// f(i) for the members i < M, i a compile-time index (registers): a chain of uniform branches that ends at M.  A
-// predicate per member instead is if-converted into selects whose MB conditions the compiler computes up front and keeps
-// in scalar registers (spilled from 16 members up), and a loop with a break at M is not fully unrolled past 8 (the
-// member arrays then go to scratch).
-template <int I, int MB, typename F>
-__device__ __forceinline__ void members(int M, F &&f) {
-  if constexpr (I < MB) {
-    if (I >= M) return;
-    f(std::integral_constant<int, I>());
-    members<I + 1, MB>(M, f);
-  }
-}
-
-// compare-exchange of a bitonic network.  Values only: min / max.  With member indices: one compare whose lane mask
-// feeds four selects at once -- the scheduling barrier keeps the compiler from hoisting a stage's compares (a mask
-// each, two scalar registers) ahead of their selects, which spills scalar registers at 32 and 64 members.
-template <bool IDX>
-__device__ inline void cex(float &a, float &b, int &ia, int &ib, bool up) {
-  if constexpr (IDX) {
-    const bool sw = up ? (b < a) : (a < b);
-    const float ta = a;
-    a = sw ? b : a;
-    b = sw ? ta : b;
-    const int t = ia;
-    ia = sw ? ib : ia;
-    ib = sw ? t : ib;
-    __builtin_amdgcn_sched_barrier(0);
-  } else {
-    const float lo = __builtin_fminf(a, b), hi = __builtin_fmaxf(a, b);
-    a = up ? lo : hi;
-    b = up ? hi : lo;
-  }
-}
+// A validated call of the pass, as gwen_ens_crps_f32 names its arguments: what the dispatch hands to launch_pass.  The
+// kernel itself keeps a parameter list: as one by-value struct the pointers lose __restrict__, and every instantiation
+// compiles to other code (DESIGN, "One copy of each helper").
+struct CrpsArgs {
+  const float *pred, *target, *node_w, *chan_w;
+  int64_t M, N, C;
+  float pair_coef;
+  float *grad_pred, *grad_target, *ws;
+};
 
 // The pass.  Thread (row, lc) of block (bx, by) owns VEC consecutive channels (vector column bx * CT + lc) and walks
 // the nodes n = by * R + row, += gridDim.y * R: a wave reads 64 consecutive columns of every member plane (the planes
@@ -118,14 +84,14 @@ __global__ __launch_bounds__(kThreads) void k_ens_crps(const float *__restrict__
   }
   if (active) {
     for (int64_t n = (int64_t)blockIdx.y * R + row; n < N; n += (int64_t)gridDim.y * R) {
-      // M and the plane stride pass an empty asm each node: otherwise the compiler hoists the MB member addresses
-      // (two scalar registers each) out of the loop, and they spill from 8 members up
       int M = M_;
       int64_t plane = plane_;
-      asm volatile("" : "+s"(M), "+s"(plane));
+      fresh(M, plane);
       const int64_t off = n * C + col * VEC;
       const float wn = node_w ? node_w[n] : 1.0f;
       float x[MB][VEC], y[VEC];
+      // the member loads: the POINTER passes the empty asm here, the offset in k_ens_products, whose loads must stay
+      // global loads -- two bodies on purpose
       if constexpr (VEC == 4) {
         const float4_t t = *reinterpret_cast<const float4_t *>(target + off);
 #pragma unroll
@@ -137,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_crps(const float *__restrict__
 #pragma unroll
           for (int v = 0; v < 4; ++v) x[i][v] = p[v];
           pp += plane;
-          asm volatile("" : "+v"(pp));         // a vector address: no scalar base per member
+          asm volatile("" : "+v"(pp));
         });
       } else {
         y[0] = target[off];
@@ -148,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_crps(const float *__restrict__
           constexpr int i = decltype(I_)::value;
           x[i][0] = *pp;
           pp += plane;
-          asm volatile("" : "+v"(pp));         // a vector address: no scalar base per member
+          asm volatile("" : "+v"(pp));
         });
       }
 #pragma unroll
@@ -156,6 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_crps(const float *__restrict__
         const float yv = y[v], r = x[0][v];
         const float scale = wn * vch[v] * inv;
         float skill = 0.0f, sgn_sum = 0.0f, dsum = 0.0f, var = 0.0f, pair = 0.0f;
+        // (dsum, dbar, var as in k_ens_products, but dsum shares the chain of skill and sgn_sum: two bodies)
         members<0, MB>(M, [&](auto I_) {
           constexpr int i = decltype(I_)::value;
           skill += __builtin_fabsf(x[i][v] - yv);
@@ -196,15 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_crps(const float *__restrict__
           int id[MB];
 #pragma unroll
           for (int i = 0; i < MB; ++i) id[i] = i;
-#pragma unroll
-          for (int k = 2; k <= MB; k <<= 1)
-#pragma unroll
-            for (int j = k >> 1; j > 0; j >>= 1)
-#pragma unroll
-              for (int i = 0; i < MB; ++i) {
-                const int l = i ^ j;
-                if (l > i) cex<GRAD>(s[i], s[l], id[i], id[l], (i & k) == 0);
-              }
+          bitonic_sort<MB, GRAD>(s, id);       // the indices travel only when the gradient needs them
           if constexpr (GRAD) {
             // mid-rank count difference of every sorted position: a tie run [a, b] has a + b - (M - 1) (a finite
             // member never ties the +inf pads, so no run crosses position M); the pads' own slots are scratch
@@ -298,12 +257,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_finish(float *__restrict__ ws,
   const float *p = ws + 2 + C + (int64_t)q * C + c;
   float acc = 0.0f;
   for (int g = threadIdx.x; g < G; g += kThreads) acc += p[(int64_t)g * 3 * C];
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum<kThreads>(&part, {acc});
   if (threadIdx.x == 0) {
     const float val = part[0] / ws[0];
     if (q == 0) ws[2 + c] = val;
@@ -317,52 +271,22 @@ __global__ __launch_bounds__(kThreads) void k_ens_loss(const float *__restrict__
   __shared__ float part[kThreads];
   float acc = 0.0f;
   for (int c = threadIdx.x; c < C; c += kThreads) acc += (chan_w ? chan_w[c] : 1.0f) * ws[2 + c];
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum<kThreads>(&part, {acc});
   if (threadIdx.x == 0) loss[0] = part[0] / ws[1];
 }
 
+// *chunks = the node chunks of the launch, the partials' row count
 template <int MB, int VEC, bool SORT, bool GRAD>
-int launch_pass(const float *pred, const float *target, const float *node_w, const float *chan_w, int64_t M, int64_t N,
-                int64_t C, float pair_coef, float *grad_pred, float *grad_target, float *ws, int32_t *chunks,
-                hipStream_t st) {
-  static int resident = 0;                      // blocks of this instantiation the device holds at once
-  if (resident == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    GWEN_HIP_CHECK(hipGetDevice(&dev));
-    GWEN_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, reinterpret_cast<const void *>(&k_ens_crps<MB, VEC, SORT, GRAD>), kThreads, 0));
-    resident = (cus < 8 ? 8 : cus) * (per_cu < 1 ? 1 : per_cu);
-  }
-  const int64_t Cv = VEC == 4 ? C / 4 : C;
-  const int64_t CT = Cv < kThreads ? Cv : kThreads;
-  const int64_t R = kThreads / CT;
-  const int64_t gx = (Cv + CT - 1) / CT;
-  int64_t cap = resident / gx;                  // one resident set of blocks walks the nodes: no tail round
-  cap = cap < 1 ? 1 : (cap > kMaxChunks ? kMaxChunks : cap);
-  int64_t G = (N + R - 1) / R;
-  G = G < cap ? G : cap;
-  *chunks = (int32_t)G;
-  k_ens_crps<MB, VEC, SORT, GRAD><<<dim3((unsigned)gx, (unsigned)G), kThreads, 0, st>>>(
-      pred, target, node_w, chan_w, (int32_t)M, N, (int32_t)C, (int32_t)CT, (int32_t)R, pair_coef, grad_pred,
-      grad_target, ws);
+int launch_pass(const CrpsArgs &a, int32_t *chunks, hipStream_t st) {
+  PassGeometry g;
+  const int rc = pass_geometry<&k_ens_crps<MB, VEC, SORT, GRAD>, kThreads>(VEC, a.C, a.N, kMaxChunks, g);
+  if (rc != GWEN_OK) return rc;
+  *chunks = (int32_t)g.G;
+  k_ens_crps<MB, VEC, SORT, GRAD><<<dim3((unsigned)g.gx, (unsigned)g.G), kThreads, 0, st>>>(
+      a.pred, a.target, a.node_w, a.chan_w, (int32_t)a.M, a.N, (int32_t)a.C, (int32_t)g.CT, (int32_t)g.R, a.pair_coef,
+      a.grad_pred, a.grad_target, a.ws);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
-}
-
-template <int VEC, bool GRAD>
-int dispatch_members(const float *pred, const float *target, const float *node_w, const float *chan_w, int64_t M,
-                     int64_t N, int64_t C, float k, float *gp, float *gt, float *ws, int32_t *G, hipStream_t st) {
-  if (M <= 4) return launch_pass<4, VEC, false, GRAD>(pred, target, node_w, chan_w, M, N, C, k, gp, gt, ws, G, st);
-  if (M <= 8) return launch_pass<8, VEC, false, GRAD>(pred, target, node_w, chan_w, M, N, C, k, gp, gt, ws, G, st);
-  if (M <= 16) return launch_pass<16, VEC, false, GRAD>(pred, target, node_w, chan_w, M, N, C, k, gp, gt, ws, G, st);
-  if (M <= 32) return launch_pass<32, 1, true, GRAD>(pred, target, node_w, chan_w, M, N, C, k, gp, gt, ws, G, st);
-  return launch_pass<64, 1, true, GRAD>(pred, target, node_w, chan_w, M, N, C, k, gp, gt, ws, G, st);
 }
 
 }  // namespace
@@ -376,30 +300,30 @@ extern "C" int gwen_ens_crps_f32(const float *pred, const float *target, const f
                                  int64_t M, int64_t N, int64_t C, float pair_coef, float *grad_pred,
                                  float *grad_target, float *loss, float *scores, float *workspace,
                                  int64_t workspace_floats, gwen_stream_t stream_) {
-  if (M < 1 || M > 64 || N < 1 || C < 1 || C > INT32_MAX / 4 || N > (int64_t(1) << 40) / C) return GWEN_EINVAL;
+  if (!shape_ok(M, N, C)) return GWEN_EINVAL;
   if (!pred || !target || !loss || !workspace || workspace_floats < gwen_ens_crps_workspace_floats(M, N, C))
     return GWEN_EINVAL;
-  const void *ptrs[] = {pred, target, node_w, chan_w, grad_pred, grad_target, loss, scores, workspace};
-  for (const void *p : ptrs)
-    if (p && !gwen_aligned(p, 4)) return GWEN_EINVAL;
-  // the 16-byte path: 4 channels per thread (member planes N*C floats apart stay aligned when C % 4 == 0)
-  const bool vec4 = C % 4 == 0 && gwen_aligned(pred, 16) && gwen_aligned(target, 16) &&
-                    (!grad_pred || gwen_aligned(grad_pred, 16)) && (!grad_target || gwen_aligned(grad_target, 16));
+  if (!aligned_all({pred, target, node_w, chan_w, grad_pred, grad_target, loss, scores, workspace}, 4))
+    return GWEN_EINVAL;
+  // the 16-byte path: 4 channels per thread (member planes N*C floats apart stay aligned when C % 4 == 0), up to 16
+  // members; above, the network holds one point per thread
+  const bool vec4 = C % 4 == 0 && aligned_all({pred, target, grad_pred, grad_target}, 16);
   hipStream_t st = gwen_stream(stream_);
   k_ens_weight_sums<<<1, 1024, 0, st>>>(node_w, N, chan_w, C, workspace);
   GWEN_LAUNCH_CHECK();
+  const CrpsArgs a{pred, target, node_w, chan_w, M, N, C, pair_coef, grad_pred, grad_target, workspace};
   int32_t G = 0;
-  int rc;
-  if (vec4)
-    rc = grad_pred ? dispatch_members<4, true>(pred, target, node_w, chan_w, M, N, C, pair_coef, grad_pred, grad_target,
-                                               workspace, &G, st)
-                   : dispatch_members<4, false>(pred, target, node_w, chan_w, M, N, C, pair_coef, grad_pred,
-                                                grad_target, workspace, &G, st);
-  else
-    rc = grad_pred ? dispatch_members<1, true>(pred, target, node_w, chan_w, M, N, C, pair_coef, grad_pred, grad_target,
-                                               workspace, &G, st)
-                   : dispatch_members<1, false>(pred, target, node_w, chan_w, M, N, C, pair_coef, grad_pred,
-                                                grad_target, workspace, &G, st);
+  auto pass = [&](auto vec, auto grad) {
+    return dispatch_bucket(gwen::ints<4, 8, 16, 32, 64>{}, M, [&](auto mb) {
+      constexpr int MB = decltype(mb)::value;
+      constexpr bool SORT = MB > 16;
+      return launch_pass<MB, SORT ? 1 : decltype(vec)::value, SORT, decltype(grad)::value>(a, &G, st);
+    });
+  };
+  using V4 = std::integral_constant<int, 4>;
+  using V1 = std::integral_constant<int, 1>;
+  const int rc = vec4 ? (grad_pred ? pass(V4(), std::true_type()) : pass(V4(), std::false_type()))
+                      : (grad_pred ? pass(V1(), std::true_type()) : pass(V1(), std::false_type()));
   if (rc != GWEN_OK) return rc;
   k_ens_finish<<<dim3((unsigned)C, 3), kThreads, 0, st>>>(workspace, (int32_t)C, G, scores);
   GWEN_LAUNCH_CHECK();

@@ -1,12 +1,15 @@
 // Masked L1 loss of the reference's training loop, forward value and gradient in one pass:
 //     loss = mean over the rows r with mask[r] (and all members, channels) of |out - target|
-// (/root/reference/src/gwen/models_gnn.py:261-265: F.l1_loss(output[mask], target[mask]); backward :372).
+// (the reference's src/gwen/models_gnn.py:261-265: F.l1_loss(output[mask], target[mask]); backward :372).
 // Written with tensor ops -- subtract, abs, mask, two reductions, and their autograd mirror -- it is 14 small
 // launches (~190 us of the 0.7 ms c2 training step, most of it launch gaps); here three: the row count, the
 // fused |diff| partial sums + gradient, and a fixed-order final reduction (no atomics: bitwise reproducible).
-#include "common.h"
+// The block sums, the sign and the alignment check are csrc/members.h's.
+#include "members.h"
 
 namespace {
+
+using namespace gwen::ens;
 
 constexpr int kThreads = 256;
 
@@ -31,12 +34,7 @@ __global__ __launch_bounds__(1024) void k_mask_count(const uint8_t *__restrict__
   }
   for (int64_t i = threadIdx.x; i < head; i += 1024) c += mask[i] != 0;
   for (int64_t i = head + nvec * 16 + threadIdx.x; i < N; i += 1024) c += mask[i] != 0;
-  part[threadIdx.x] = c;
-  __syncthreads();
-  for (int s = 512; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum<1024>(&part, {c});
   if (threadIdx.x == 0) ws[0] = (float)part[0];
 }
 
@@ -60,16 +58,11 @@ __global__ __launch_bounds__(kThreads) void k_masked_l1(const float *__restrict_
     for (int k = 0; k < 4; ++k) {
       const float d = o[k] - t[k];
       acc += m * __builtin_fabsf(d);
-      g[k] = (d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f)) * m * inv;     // 0 * inf = NaN with an empty mask, as torch
+      g[k] = sgnf(d) * m * inv;                 // 0 * inf = NaN with an empty mask, as torch
     }
     if (grad) reinterpret_cast<float4_t *>(grad)[i] = g;
   }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum<kThreads>(&part, {acc});
   if (threadIdx.x == 0) ws[1 + blockIdx.x] = part[0];
 }
 
@@ -78,12 +71,7 @@ __global__ __launch_bounds__(kThreads) void k_l1_final(const float *__restrict__
   __shared__ float part[kThreads];
   float acc = 0.0f;
   for (int i = threadIdx.x; i < nblocks; i += kThreads) acc += ws[1 + i];
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-    __syncthreads();
-  }
+  block_sum<kThreads>(&part, {acc});
   if (threadIdx.x == 0) loss[0] = part[0] / (ws[0] * scale_c);
 }
 
@@ -100,7 +88,7 @@ extern "C" int gwen_masked_l1_f32(const float *out, const float *target, const u
   if (!workspace || workspace_floats < gwen_masked_l1_workspace_floats()) return GWEN_ENOSPACE;
   const int64_t rows = members * N, total4 = rows * (C / 4);
   if ((total4 > 0 && (!out || !target || !mask)) || rows >= (int64_t(1) << 40)) return GWEN_EINVAL;
-  if (!gwen_aligned(out, 16) || !gwen_aligned(target, 16) || (grad && !gwen_aligned(grad, 16))) return GWEN_EINVAL;
+  if (!aligned_all({out, target, grad}, 16)) return GWEN_EINVAL;
   hipStream_t st = gwen_stream(stream_);
   k_mask_count<<<1, 1024, 0, st>>>(mask, N, workspace);
   GWEN_LAUNCH_CHECK();

@@ -11,43 +11,17 @@
 //   gwen_ens_rank_hist_f32: b = #{x_i < y}, t = #{x_i == y} from one sweep over the members (no member registers, no
 //   sort); every thread owns M + 1 LDS bins, adds w_n / (t + 1) to bins b..b+t in node order, the block sums its rows in
 //   a fixed order into a partial histogram per node chunk, and a finish kernel sums the chunks in a fixed order.
-#include "common.h"
-
-#include <type_traits>
+// The member chains, the network, the pass geometry and the bucket dispatch are csrc/members.h's.
+#include "members.h"
 
 namespace {
+
+using namespace gwen::ens;
 
 constexpr int kThreads = 256;
 constexpr int kMaxTable = 32;                   // quantiles, thresholds of one call
 constexpr int kHistMaxChunks = 1024;            // node chunks of the rank histogram, and
 constexpr int64_t kHistMaxFloats = 1 << 22;     // ... of its partials: chunks * C * (M + 1) floats, 16 MiB
-
-// f(i) for the members i < M, i a compile-time index (see ensemble.hip: a chain of uniform branches that ends at M)
-template <int I, int MB, typename F>
-__device__ __forceinline__ void members(int M, F &&f) {
-  if constexpr (I < MB) {
-    if (I >= M) return;
-    f(std::integral_constant<int, I>());
-    members<I + 1, MB>(M, f);
-  }
-}
-
-// f(i) for i = MB - 1 down to M
-template <int I, typename F>
-__device__ __forceinline__ void pads(int M, F &&f) {
-  if constexpr (I >= 0) {
-    if (I < M) return;
-    f(std::integral_constant<int, I>());
-    pads<I - 1>(M, f);
-  }
-}
-
-// M through an empty asm in front of every chain: otherwise the MB conditions of the first chain are kept in scalar
-// registers for the later ones, and spill from 32 members up
-__device__ __forceinline__ int fresh(int m) {
-  asm volatile("" : "+s"(m));
-  return m;
-}
 
 // a = s[lo], b = s[lo + 1] for a wave-uniform lo in [L, H): a binary tree of uniform branches over register indices
 template <int L, int H, int MB>
@@ -100,15 +74,14 @@ __global__ __launch_bounds__(kThreads) void k_ens_products(const float *__restri
   const float invM = 1.0f / fM;
   const float varDiv = (float)(M_ - 1);               // M = 1: 0 / 0 = NaN, torch's unbiased std of one value
   for (int64_t n = (int64_t)blockIdx.y * R + row; n < N; n += (int64_t)gridDim.y * R) {
-    // (M and the plane stride pass an empty asm each node, the member addresses are vector addresses: ensemble.hip)
     int M = M_;
     int64_t plane = plane_;
-    asm volatile("" : "+s"(M), "+s"(plane));
+    fresh(M, plane);
     const int64_t off = n * C + col * VEC;
     float x[VEC][MB];
     {
-      // the member's element offset is a vector register that passes an empty asm (no scalar base per member, and the
-      // loads stay global loads, which a laundered pointer does not)
+      // the member loads: the element OFFSET passes the empty asm here (the loads stay global loads, which a laundered
+      // pointer's do not), the pointer in k_ens_crps -- two bodies on purpose
       int64_t o = off;
       members<0, MB>(fresh(M), [&](auto I_) {
         constexpr int i = decltype(I_)::value;
@@ -122,8 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_products(const float *__restri
         o += plane;
         asm volatile("" : "+v"(o));
       });
-      // pads of +inf sort behind every member.  Set from the top down to M by a chain of their own: initialised in front
-      // of the loads, every exit of the load chain re-materialises all pads above it (MB^2 / 2 moves a point)
+      // pads of +inf sort behind every member
       if constexpr (SORT) pads<MB - 1>(fresh(M), [&](auto I_) { x[0][decltype(I_)::value] = __builtin_inff(); });
     }
     if (mean || stdv) {
@@ -131,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_products(const float *__restri
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
         const float r = x[v][0];
-        float dsum = 0.0f, var = 0.0f;
+        float dsum = 0.0f, var = 0.0f;          // (as in k_ens_crps, where dsum shares a chain with the skill: two bodies)
         members<0, MB>(fresh(M), [&](auto I_) {
           constexpr int i = decltype(I_)::value;
           dsum += x[v][i] - r;
@@ -183,20 +155,7 @@ __global__ __launch_bounds__(kThreads) void k_ens_products(const float *__restri
         top = mag > top ? mag : top;
       });
       const bool has_nan = top > 0x7f800000u;
-#pragma unroll
-      for (int k = 2; k <= MB; k <<= 1)
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1)
-#pragma unroll
-          for (int i = 0; i < MB; ++i) {
-            const int l = i ^ j;
-            if (l > i) {
-              const float lo = __builtin_fminf(s[i], s[l]), hi = __builtin_fmaxf(s[i], s[l]);
-              const bool up = (i & k) == 0;
-              s[i] = up ? lo : hi;
-              s[l] = up ? hi : lo;
-            }
-          }
+      bitonic_sort<MB, false>(s);
       int64_t o = off;
       for (int qi = 0; qi < Q; ++qi) {
         const int lo = __builtin_amdgcn_readfirstlane(s_lo[qi]);
@@ -213,60 +172,53 @@ __global__ __launch_bounds__(kThreads) void k_ens_products(const float *__restri
   }
 }
 
+// A validated call, as gwen_ens_products_f32 names its arguments: what the dispatch hands to launch_products.  (The kernel
+// keeps a parameter list, as k_ens_crps does: csrc/ensemble.hip.)
+struct ProductsArgs {
+  const float *pred;
+  int64_t M, N, C;
+  const float *q;
+  int64_t Q;
+  const float *thr;
+  int64_t T;
+  int thr_per_channel;
+  float *mean, *stdv, *quant, *prob;
+};
+
 template <int MB, int VEC, bool SORT>
-int launch_products(const float *pred, int64_t M, int64_t N, int64_t C, const float *q, int64_t Q, const float *thr,
-                    int64_t T, int thr_per_channel, float *mean, float *stdv, float *quant, float *prob,
-                    hipStream_t st) {
-  static int resident = 0;                      // blocks of this instantiation the device holds at once
-  if (resident == 0) {
-    int dev = 0, cus = 0, per_cu = 0;
-    GWEN_HIP_CHECK(hipGetDevice(&dev));
-    GWEN_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    GWEN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &per_cu, reinterpret_cast<const void *>(&k_ens_products<MB, VEC, SORT>), kThreads, 0));
-    resident = (cus < 8 ? 8 : cus) * (per_cu < 1 ? 1 : per_cu);
-  }
-  const int64_t Cv = VEC == 4 ? C / 4 : C;
-  const int64_t CT = Cv < kThreads ? Cv : kThreads;
-  const int64_t R = kThreads / CT;
-  const int64_t gx = (Cv + CT - 1) / CT;
-  int64_t cap = resident / gx;                  // one resident set of blocks walks the nodes: no tail round
-  cap = cap < 1 ? 1 : (cap > 65535 ? 65535 : cap);
-  int64_t G = (N + R - 1) / R;
-  G = G < cap ? G : cap;
-  k_ens_products<MB, VEC, SORT><<<dim3((unsigned)gx, (unsigned)G), kThreads, 0, st>>>(
-      pred, (int32_t)M, N, (int32_t)C, (int32_t)CT, (int32_t)R, q, (int32_t)Q, thr, (int32_t)T, thr_per_channel, mean,
-      stdv, quant, prob);
+int launch_products(const ProductsArgs &a, hipStream_t st) {
+  PassGeometry g;                               // nothing is summed over the chunks: up to the grid's own limit
+  const int rc = pass_geometry<&k_ens_products<MB, VEC, SORT>, kThreads>(VEC, a.C, a.N, 65535, g);
+  if (rc != GWEN_OK) return rc;
+  k_ens_products<MB, VEC, SORT><<<dim3((unsigned)g.gx, (unsigned)g.G), kThreads, 0, st>>>(
+      a.pred, (int32_t)a.M, a.N, (int32_t)a.C, (int32_t)g.CT, (int32_t)g.R, a.q, (int32_t)a.Q, a.thr, (int32_t)a.T,
+      a.thr_per_channel, a.mean, a.stdv, a.quant, a.prob);
   GWEN_LAUNCH_CHECK();
   return GWEN_OK;
 }
 
-#define GWEN_PRODUCTS_ARGS pred, M, N, C, q, Q, thr, T, thr_per_channel, mean, stdv, quant, prob, st
-
+// the member bucket; the 16-byte path (VEC == 4) holds up to 16 members
 template <int VEC, bool SORT>
-int dispatch_products(const float *pred, int64_t M, int64_t N, int64_t C, const float *q, int64_t Q, const float *thr,
-                      int64_t T, int thr_per_channel, float *mean, float *stdv, float *quant, float *prob,
-                      hipStream_t st) {
-  if (M <= 4) return launch_products<4, VEC, SORT>(GWEN_PRODUCTS_ARGS);
-  if (M <= 8) return launch_products<8, VEC, SORT>(GWEN_PRODUCTS_ARGS);
-  if (M <= 16) return launch_products<16, VEC, SORT>(GWEN_PRODUCTS_ARGS);
-  if (M <= 32) return launch_products<32, 1, SORT>(GWEN_PRODUCTS_ARGS);
-  return launch_products<64, 1, SORT>(GWEN_PRODUCTS_ARGS);
+int dispatch_products(const ProductsArgs &a, hipStream_t st) {
+  return dispatch_bucket(gwen::ints<4, 8, 16, 32, 64>{}, a.M, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    return launch_products<MB, (MB > 16 ? 1 : VEC), SORT>(a, st);
+  });
 }
 
 // Node chunks of the rank histogram: a function of the shapes alone (not of the device or of a pointer's alignment),
 // so that the order of every sum is too.
 struct HistShape {
-  int64_t threads, CT, R, gx, G;
+  int64_t threads;
+  ColumnTiles t;
+  int64_t G;
 };
 
 HistShape hist_shape(int64_t M, int64_t N, int64_t C) {
   HistShape h;
   h.threads = M <= 32 ? 256 : 128;              // (M + 1) LDS bins a thread: at most 33 KiB a block
-  h.CT = C < h.threads ? C : h.threads;
-  h.R = h.threads / h.CT;
-  h.gx = (C + h.CT - 1) / h.CT;
-  int64_t G = (N + h.R - 1) / h.R;
+  h.t = column_tiles(C, h.threads);
+  int64_t G = (N + h.t.R - 1) / h.t.R;
   const int64_t fit = kHistMaxFloats / (C * (M + 1));
   G = G < kHistMaxChunks ? G : kHistMaxChunks;
   G = G < fit ? G : (fit < 1 ? 1 : fit);
@@ -354,10 +306,6 @@ __global__ __launch_bounds__(kThreads) void k_ens_rank_hist_finish(const float *
   }
 }
 
-bool shape_ok(int64_t M, int64_t N, int64_t C) {
-  return M >= 1 && M <= 64 && N >= 1 && C >= 1 && C <= INT32_MAX / 4 && N <= (int64_t(1) << 40) / C;
-}
-
 }  // namespace
 
 extern "C" int gwen_ens_products_f32(const float *pred, int64_t M, int64_t N, int64_t C, const float *q, int64_t Q,
@@ -367,19 +315,17 @@ extern "C" int gwen_ens_products_f32(const float *pred, int64_t M, int64_t N, in
   if (!pred || (Q > 0 && (!q || !quant)) || (T > 0 && (!thr || !prob))) return GWEN_EINVAL;
   if (thr_per_channel != 0 && thr_per_channel != 1) return GWEN_EINVAL;
   if (!mean && !stdv && Q == 0 && T == 0) return GWEN_EINVAL;       // nothing asked for
-  const void *ptrs[] = {pred, q, thr, mean, stdv, quant, prob};
-  for (const void *p : ptrs)
-    if (p && !gwen_aligned(p, 4)) return GWEN_EINVAL;
+  if (!aligned_all({pred, q, thr, mean, stdv, quant, prob}, 4)) return GWEN_EINVAL;
   if (Q == 0) quant = nullptr;
   if (T == 0) prob = nullptr;
   // the 16-byte path: 4 channels per thread, for the work that needs no sort, while 4 points of members fit in
   // registers (16 members, as the CRPS)
-  const bool vec4 = Q == 0 && M <= 16 && C % 4 == 0 && gwen_aligned(pred, 16) && (!mean || gwen_aligned(mean, 16)) &&
-                    (!stdv || gwen_aligned(stdv, 16)) && (!prob || gwen_aligned(prob, 16));
+  const bool vec4 = Q == 0 && M <= 16 && C % 4 == 0 && aligned_all({pred, mean, stdv, prob}, 16);
+  const ProductsArgs a{pred, M, N, C, q, Q, thr, T, thr_per_channel, mean, stdv, quant, prob};
   hipStream_t st = gwen_stream(stream_);
-  if (Q > 0) return dispatch_products<1, true>(GWEN_PRODUCTS_ARGS);
-  if (vec4) return dispatch_products<4, false>(GWEN_PRODUCTS_ARGS);
-  return dispatch_products<1, false>(GWEN_PRODUCTS_ARGS);
+  if (Q > 0) return dispatch_products<1, true>(a, st);
+  if (vec4) return dispatch_products<4, false>(a, st);
+  return dispatch_products<1, false>(a, st);
 }
 
 extern "C" int64_t gwen_ens_rank_hist_workspace_floats(int64_t M, int64_t N, int64_t C) {
@@ -393,14 +339,12 @@ extern "C" int gwen_ens_rank_hist_f32(const float *pred, const float *target, co
   if (!shape_ok(M, N, C)) return GWEN_EINVAL;
   if (!pred || !target || !hist || !workspace || workspace_floats < gwen_ens_rank_hist_workspace_floats(M, N, C))
     return GWEN_EINVAL;
-  const void *ptrs[] = {pred, target, node_w, hist, workspace};
-  for (const void *p : ptrs)
-    if (p && !gwen_aligned(p, 4)) return GWEN_EINVAL;
+  if (!aligned_all({pred, target, node_w, hist, workspace}, 4)) return GWEN_EINVAL;
   const HistShape h = hist_shape(M, N, C);
   hipStream_t st = gwen_stream(stream_);
   const size_t lds_bytes = (size_t)h.threads * (size_t)(M + 1) * sizeof(float);
-  k_ens_rank_hist<<<dim3((unsigned)h.gx, (unsigned)h.G), (unsigned)h.threads, lds_bytes, st>>>(
-      pred, target, node_w, (int32_t)M, N, (int32_t)C, (int32_t)h.CT, (int32_t)h.R, workspace);
+  k_ens_rank_hist<<<dim3((unsigned)h.t.gx, (unsigned)h.G), (unsigned)h.threads, lds_bytes, st>>>(
+      pred, target, node_w, (int32_t)M, N, (int32_t)C, (int32_t)h.t.CT, (int32_t)h.t.R, workspace);
   GWEN_LAUNCH_CHECK();
   k_ens_rank_hist_finish<<<(unsigned)C, kThreads, 0, st>>>(workspace, (int32_t)M, (int32_t)C, (int32_t)h.G,
                                                            normalize, hist);

@@ -9,12 +9,12 @@
 // Every block owns the SAME kTile consecutive points on either path (4 bytes or 16 bytes per lane), leaves one value per
 // point in LDS and sums them in point order, so the bits depend on neither the path nor the alignment; per-block partial
 // sums go to the workspace and a second launch adds them in block order.  No atomics: two runs are bitwise equal.
-#include "common.h"
-
-#include <initializer_list>
-#include <type_traits>
+// The member chain, the block sum, the bucket dispatch and the alignment check are csrc/members.h's.
+#include "members.h"
 
 namespace {
+
+using namespace gwen::ens;
 
 constexpr int kThreads = 256;
 constexpr int kTile = 1024;                     // points (elements) of one block: 4 per thread
@@ -23,19 +23,7 @@ constexpr int64_t kMaxPoints = int64_t(1) << 33;   // of a launch: one block per
 constexpr float kSqrt2 = 1.41421356237309504880f;
 constexpr float kInvSqrtPi = 0.56418958354775628695f;
 
-__device__ inline float sgnf(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
-
-// f(i) for the members i < M, i a compile-time index: a chain of uniform branches that ends at M (csrc/ensemble.hip)
-template <int I, int MB, typename F>
-__device__ __forceinline__ void members(int M, F &&f) {
-  if constexpr (I < MB) {
-    if (I >= M) return;
-    f(std::integral_constant<int, I>());
-    members<I + 1, MB>(M, f);
-  }
-}
-
-// MB > 0: at most MB members, held in registers; MB == 0: any number, a runtime loop
+// MB > 0: at most MB members, held in registers (the chain of members.h); MB == 0: any number, a runtime loop
 template <int MB, typename F>
 __device__ __forceinline__ void for_members(int M, F &&f) {
   if constexpr (MB > 0) {
@@ -170,19 +158,6 @@ struct Trip {
   }
 };
 
-// the sum of this thread's four LDS entries over the block, in a fixed order
-__device__ __forceinline__ float block_sum(float acc, float *red) {
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // ---- Gaussian CRPS ----------------------------------------------------------------------------------------------------
 
 struct Gauss {
@@ -238,8 +213,8 @@ __global__ __launch_bounds__(kThreads) void k_gauss_crps(const float *__restrict
       h += head ? v[j] : 0.0f;
       t += head ? 0.0f : v[j];
     }
-    h = block_sum(h, red);
-    t = block_sum(t, red);
+    h = block_sum_all<kThreads>(h, &red);
+    t = block_sum_all<kThreads>(t, &red);
     if (tid == 0) {
       ws[2 * (int64_t)blockIdx.x] = h;
       ws[2 * (int64_t)blockIdx.x + 1] = t;
@@ -287,7 +262,7 @@ __global__ __launch_bounds__(kThreads) void k_crps_finish_block(const float *__r
   const int64_t b0 = (s * S) / kTile, b1 = ((s + 1) * S - 1) / kTile;
   float acc = 0.0f, c = 0.0f;
   for (int64_t b = b0 + threadIdx.x; b <= b1; b += kThreads) kadd(acc, c, crps_partial(ws, b, s, S));
-  acc = block_sum(acc, red);
+  acc = block_sum_all<kThreads>(acc, &red);
   if (threadIdx.x == 0) loss[s] = acc / (float)S;
 }
 
@@ -428,8 +403,8 @@ __global__ __launch_bounds__(kThreads) void k_varreg(const float *__restrict__ p
   __syncthreads();
   const float4_t u = *reinterpret_cast<const float4_t *>(l1s + 4 * tid);
   const float4_t w = *reinterpret_cast<const float4_t *>(vars + 4 * tid);
-  const float sl = block_sum(((u[0] + u[1]) + u[2]) + u[3], red);
-  const float sv = block_sum(((w[0] + w[1]) + w[2]) + w[3], red);
+  const float sl = block_sum_all<kThreads>(((u[0] + u[1]) + u[2]) + u[3], &red);
+  const float sv = block_sum_all<kThreads>(((w[0] + w[1]) + w[2]) + w[3], &red);
   if (tid == 0) {
     ws[2 * (int64_t)blockIdx.x] = sl;
     ws[2 * (int64_t)blockIdx.x + 1] = sv;
@@ -445,8 +420,8 @@ __global__ __launch_bounds__(kThreads) void k_varreg_final(const float *__restri
     kadd(sl, cl, ws[2 * b]);
     kadd(sv, cv, ws[2 * b + 1]);
   }
-  sl = block_sum(sl, red);
-  sv = block_sum(sv, red);
+  sl = block_sum_all<kThreads>(sl, &red);
+  sv = block_sum_all<kThreads>(sv, &red);
   if (threadIdx.x == 0) loss[0] = sl / (float)(M * P) + (-alpha * (sv / (float)P));
 }
 
@@ -475,7 +450,7 @@ __global__ __launch_bounds__(kThreads) void k_mask_sum(const float *__restrict__
       kadd(acc, c, v);
     }
   }
-  acc = block_sum(acc, red);
+  acc = block_sum_all<kThreads>(acc, &red);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
@@ -484,7 +459,7 @@ __global__ __launch_bounds__(kThreads) void k_mask_total(float *__restrict__ ws,
   __shared__ float red[kThreads];
   float acc = 0.0f;
   for (int i = threadIdx.x; i < nparts; i += kThreads) acc += ws[1 + i];
-  acc = block_sum(acc, red);
+  acc = block_sum_all<kThreads>(acc, &red);
   if (threadIdx.x == 0) ws[0] = acc;
 }
 
@@ -523,7 +498,7 @@ __global__ __launch_bounds__(kThreads) void k_masked_mean(const float *__restric
   }
   __syncthreads();
   const float4_t u = *reinterpret_cast<const float4_t *>(vals + 4 * tid);
-  const float s = block_sum(((u[0] + u[1]) + u[2]) + u[3], red);
+  const float s = block_sum_all<kThreads>(((u[0] + u[1]) + u[2]) + u[3], &red);
   if (tid == 0) ws[1 + kMaskBlocks + (int64_t)blockIdx.x] = s;
 }
 
@@ -532,7 +507,7 @@ __global__ __launch_bounds__(kThreads) void k_masked_final(const float *__restri
   __shared__ float red[kThreads];
   float acc = 0.0f, c = 0.0f;
   for (int64_t b = threadIdx.x; b < nblocks; b += kThreads) kadd(acc, c, ws[1 + kMaskBlocks + b]);
-  acc = block_sum(acc, red);
+  acc = block_sum_all<kThreads>(acc, &red);
   if (threadIdx.x == 0) loss[0] = acc / ws[0];
 }
 
@@ -547,24 +522,12 @@ int check_shape(int64_t A, int64_t M, int64_t R, int64_t min_m, int64_t max_m) {
 
 int64_t tiles(int64_t points) { return (points + kTile - 1) / kTile; }
 
-bool aligned_all(std::initializer_list<const void *> ptrs, size_t a) {
-  for (const void *p : ptrs)
-    if (p && !gwen_aligned(p, a)) return false;
-  return true;
-}
-
-// f(MB, VEC) as integral constants for the member bucket and the path
+// f(MB, VEC) as integral constants for the member bucket (8, 32, or 0: more, the run-time loop) and the path
 template <typename F>
 int dispatch(int64_t M, bool vec4, F &&f) {
-  using std::integral_constant;
-  if (vec4) {
-    if (M <= 8) return f(integral_constant<int, 8>(), integral_constant<int, 4>());
-    if (M <= 32) return f(integral_constant<int, 32>(), integral_constant<int, 4>());
-    return f(integral_constant<int, 0>(), integral_constant<int, 4>());
-  }
-  if (M <= 8) return f(integral_constant<int, 8>(), integral_constant<int, 1>());
-  if (M <= 32) return f(integral_constant<int, 32>(), integral_constant<int, 1>());
-  return f(integral_constant<int, 0>(), integral_constant<int, 1>());
+  return dispatch_bucket(gwen::ints<8, 32, 0>{}, M, [&](auto mb) {
+    return vec4 ? f(mb, std::integral_constant<int, 4>()) : f(mb, std::integral_constant<int, 1>());
+  });
 }
 
 int check_crps(int64_t A, int64_t M, int64_t R, int64_t S) {

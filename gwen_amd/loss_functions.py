@@ -21,6 +21,8 @@ import torch
 from torch import Tensor, nn
 from torch.autograd.function import once_differentiable
 
+from . import _checks
+
 MAX_MEMBERS = 256          # of the Gaussian CRPS kernel (include/gwen_hip.h)
 
 
@@ -29,23 +31,11 @@ def _lib():
     return L
 
 
-def _is_tensors(**named) -> None:
-    for name, t in named.items():
-        if not isinstance(t, Tensor):
-            raise ValueError(f"{name} must be a tensor")
-
-
-def _check_types(float_only, devices) -> None:
-    """dtypes (TypeError), then devices (RuntimeError): the order of ``losses._check``, after the shape errors."""
-    for name, t in float_only:
-        if t.dtype != torch.float32:
-            raise TypeError(f"gwen_amd: {name} must be float32 (got {t.dtype})")
-    first = devices[0][1]
-    for name, t in devices:
-        if not t.is_cuda:
-            raise RuntimeError(f"gwen_amd: {name} must live on a HIP device (no CPU fallback)")
-        if t.device != first.device:
-            raise RuntimeError(f"gwen_amd: {name} is on {t.device}, {devices[0][0]} on {first.device}")
+def _check_types(outputs: Tensor, target: Tensor, mask: Optional[Tensor] = None) -> None:
+    """After the shape errors: outputs and target are float32, and everything lives on outputs' HIP device."""
+    _checks.require_dtype("outputs", outputs)
+    _checks.require_dtype("target", target)
+    _checks.require_device(("outputs", outputs), ("target", target), ("mask", mask))
 
 
 # ---- launches on preallocated buffers (contiguous fp32 on one device; tools/ref_losses_bench.py times them) -------------
@@ -155,7 +145,7 @@ class CRPSLoss(nn.Module):
         super().__init__()
 
     def forward(self, outputs: Tensor, target: Tensor, dim: int = 0) -> Tensor:
-        _is_tensors(outputs=outputs, target=target)
+        _checks.require_tensors(outputs=outputs, target=target)
         if outputs.dim() != 5:
             raise ValueError(f"CRPSLoss takes 5-D outputs with the members on dim (got {outputs.dim()}-D): the mean "
                              "over the three trailing axes of the reduced tensor is defined for 4-D targets only")
@@ -172,7 +162,7 @@ class CRPSLoss(nn.Module):
             raise ValueError(f"at most {MAX_MEMBERS} members (got {m})")
         if outputs.numel() == 0:
             raise ValueError(f"outputs is empty: {tuple(outputs.shape)}")
-        _check_types((("outputs", outputs), ("target", target)), (("outputs", outputs), ("target", target)))
+        _check_types(outputs, target)
         return _GaussCRPS.apply(outputs, target, dim)
 
 
@@ -210,7 +200,7 @@ class EnsembleVarRegLoss(nn.Module):
         self.alpha = alpha
 
     def forward(self, outputs: Tensor, target: Tensor) -> Tensor:
-        _is_tensors(outputs=outputs, target=target)
+        _checks.require_tensors(outputs=outputs, target=target)
         if outputs.dim() < 2:
             raise ValueError(f"outputs needs at least 2 dims, the members on dim 1 (got {tuple(outputs.shape)})")
         if outputs.numel() == 0:
@@ -224,7 +214,7 @@ class EnsembleVarRegLoss(nn.Module):
             if not ok:
                 raise ValueError(f"target {tuple(target.shape)} does not broadcast to outputs {shape}")
             target = target.expand(shape)                # autograd sums the gradient back over the expanded axes
-        _check_types((("outputs", outputs), ("target", target)), (("outputs", outputs), ("target", target)))
+        _check_types(outputs, target)
         return _VarRegL1.apply(outputs, target, float(self.alpha))
 
     def extra_repr(self) -> str:
@@ -279,7 +269,7 @@ class MaskedLoss(nn.Module):
         self.loss_fn = loss_fn
 
     def forward(self, outputs: Tensor, target: Tensor, mask: Tensor) -> Tensor:
-        _is_tensors(outputs=outputs, target=target, mask=mask)
+        _checks.require_tensors(outputs=outputs, target=target, mask=mask)
         if outputs.numel() == 0 or mask.numel() == 0:
             raise ValueError(f"outputs {tuple(outputs.shape)} or mask {tuple(mask.shape)} is empty")
         if tuple(target.shape) != tuple(outputs.shape):
@@ -293,10 +283,9 @@ class MaskedLoss(nn.Module):
         if mask.requires_grad:
             raise ValueError("mask requires grad: the loss has no gradient for its mask (detach it)")
         kind = _fused_kind(self.loss_fn)
-        if kind is not None and mask.dtype not in (torch.float32, torch.bool):
-            raise TypeError(f"gwen_amd: mask must be float32 or bool (got {mask.dtype})")
-        _check_types((("outputs", outputs), ("target", target)),
-                     (("outputs", outputs), ("target", target), ("mask", mask)))
+        if kind is not None:
+            _checks.require_dtype("mask", mask, (torch.float32, torch.bool))
+        _check_types(outputs, target, mask)
         mshape = tuple(mask.shape)
         while len(mshape) > 1 and mshape[0] == 1:        # leading ones change neither the broadcast nor the sum
             mshape = mshape[1:]

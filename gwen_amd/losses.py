@@ -22,6 +22,8 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
+from . import _checks
+
 MAX_MEMBERS = 64
 
 
@@ -32,43 +34,27 @@ def pair_coef(members: int, alpha: float) -> float:
 
 
 def _check(pred, target, node_weights, channel_weights, alpha) -> None:
-    """Shape and argument errors (ValueError) first, then dtypes (TypeError), then devices (RuntimeError)."""
+    """Shape and argument errors, then dtypes, then devices (``_checks``)."""
     if not isinstance(pred, Tensor) or not isinstance(target, Tensor):
         raise ValueError("pred and target must be tensors")
-    if pred.dim() != 3:
-        raise ValueError(f"pred must be [members, N, C], got {tuple(pred.shape)}")
-    if target.dim() != 2 or tuple(target.shape) != tuple(pred.shape[1:]):
-        raise ValueError(f"target must be [N, C] = {tuple(pred.shape[1:])}, got {tuple(target.shape)}")
+    _checks.require_members_first(pred)
+    _checks.require_target_nc(pred, target)
+    _checks.require_sizes(pred, MAX_MEMBERS)
     m, n, c = pred.shape
-    if not 1 <= m <= MAX_MEMBERS:
-        raise ValueError(f"1 <= members <= {MAX_MEMBERS} (got {m})")
-    if n < 1 or c < 1:
-        raise ValueError(f"N and C must be >= 1 (got {n}, {c})")
     alpha = float(alpha)
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"alpha must lie in [0, 1] (got {alpha})")
     if alpha > 0 and m < 2:
         raise ValueError("alpha > 0 needs at least 2 members (alpha = 0 takes one)")
     for name, w, size in (("node_weights", node_weights, n), ("channel_weights", channel_weights, c)):
-        if w is None:
-            continue
-        if not isinstance(w, Tensor):
-            raise ValueError(f"{name} must be a tensor or None")
-        if w.dim() != 1 or w.numel() != size:
-            raise ValueError(f"{name} must be [{size}], got {tuple(w.shape)}")
-        if w.requires_grad:
+        _checks.require_weights(name, w, size)
+        if w is not None and w.requires_grad:
             raise ValueError(f"{name} requires grad: the loss has no gradient for its weights (detach them)")
     for name, t in (("pred", pred), ("target", target), ("channel_weights", channel_weights)):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"gwen_amd: {name} must be float32 (got {t.dtype})")
-    if node_weights is not None and node_weights.dtype not in (torch.float32, torch.bool):
-        raise TypeError(f"gwen_amd: node_weights must be float32 or bool (got {node_weights.dtype})")
-    for name, t in (("pred", pred), ("target", target), ("node_weights", node_weights),
-                    ("channel_weights", channel_weights)):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"gwen_amd: {name} must live on a HIP device (no CPU fallback)")
-        if t is not None and t.device != pred.device:
-            raise RuntimeError(f"gwen_amd: {name} is on {t.device}, pred on {pred.device}")
+        _checks.require_dtype(name, t)
+    _checks.require_dtype("node_weights", node_weights, (torch.float32, torch.bool))
+    _checks.require_device(("pred", pred), ("target", target), ("node_weights", node_weights),
+                           ("channel_weights", channel_weights))
 
 
 def crps_launch(pred: Tensor, target: Tensor, node_weights: Optional[Tensor], channel_weights: Optional[Tensor],

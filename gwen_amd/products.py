@@ -22,21 +22,17 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from . import _checks
+
 MAX_MEMBERS = 64
 MAX_QUANTILES = 32
 MAX_THRESHOLDS = 32
 
 
 def _check_pred(pred) -> None:
-    if not isinstance(pred, Tensor):
-        raise ValueError("pred must be a tensor")
-    if pred.dim() != 3:
-        raise ValueError(f"pred must be [members, N, C], got {tuple(pred.shape)}")
-    m, n, c = pred.shape
-    if not 1 <= m <= MAX_MEMBERS:
-        raise ValueError(f"1 <= members <= {MAX_MEMBERS} (got {m})")
-    if n < 1 or c < 1:
-        raise ValueError(f"N and C must be >= 1 (got {n}, {c})")
+    _checks.require_tensors(pred=pred)
+    _checks.require_members_first(pred)
+    _checks.require_sizes(pred, MAX_MEMBERS)
 
 
 def _is_device_table(t, pred: Tensor) -> bool:
@@ -80,21 +76,6 @@ def _threshold_table(thr, pred: Tensor) -> Tensor:
     if t.shape[0] > MAX_THRESHOLDS:
         raise ValueError(f"at most {MAX_THRESHOLDS} thresholds a call (got {t.shape[0]})")
     return t
-
-
-def _check_dtype_device(pred: Tensor, others=()) -> None:
-    """After the shapes: dtypes (TypeError), then devices (RuntimeError), as ``losses._check``."""
-    if pred.dtype != torch.float32:
-        raise TypeError(f"gwen_amd: pred must be float32 (got {pred.dtype})")
-    for name, t, dtypes in others:
-        if t is not None and t.dtype not in dtypes:
-            raise TypeError(f"gwen_amd: {name} must be {' or '.join(str(d).replace('torch.', '') for d in dtypes)} "
-                            f"(got {t.dtype})")
-    for name, t in (("pred", pred),) + tuple((name, t) for name, t, _ in others):
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"gwen_amd: {name} must live on a HIP device (no CPU fallback)")
-        if t is not None and t.device != pred.device:
-            raise RuntimeError(f"gwen_amd: {name} is on {t.device}, pred on {pred.device}")
 
 
 def products_launch(pred: Tensor, q: Optional[Tensor], thr: Optional[Tensor], mean: Optional[Tensor],
@@ -145,7 +126,8 @@ def ensemble_products(pred: Tensor, quantiles=None, thresholds=None, mean: bool 
     thr = None if thresholds is None else _threshold_table(thresholds, pred)
     if q is None and thr is None and not mean and not std:
         raise ValueError("ensemble_products: nothing asked for (quantiles, thresholds, mean or std)")
-    _check_dtype_device(pred)
+    _checks.require_dtype("pred", pred)
+    _checks.require_device(("pred", pred))
     p = pred.detach().contiguous()
     dev = p.device
     _, n, c = p.shape
@@ -182,18 +164,14 @@ def rank_histogram(pred: Tensor, target: Tensor, node_weights: Optional[Tensor] 
     counted.  ``normalize`` divides every channel's row by its own sum (a row that counted nothing is NaN).  Flat rows
     mean a calibrated ensemble, a U an under-dispersive one, a dome an over-dispersive one."""
     _check_pred(pred)
-    if not isinstance(target, Tensor):
-        raise ValueError("target must be a tensor")
-    if target.dim() != 2 or tuple(target.shape) != tuple(pred.shape[1:]):
-        raise ValueError(f"target must be [N, C] = {tuple(pred.shape[1:])}, got {tuple(target.shape)}")
+    _checks.require_tensors(target=target)
+    _checks.require_target_nc(pred, target)
     m, n, c = pred.shape
-    if node_weights is not None:
-        if not isinstance(node_weights, Tensor):
-            raise ValueError("node_weights must be a tensor or None")
-        if node_weights.dim() != 1 or node_weights.numel() != n:
-            raise ValueError(f"node_weights must be [{n}], got {tuple(node_weights.shape)}")
-    _check_dtype_device(pred, (("target", target, (torch.float32,)),
-                               ("node_weights", node_weights, (torch.float32, torch.bool))))
+    _checks.require_weights("node_weights", node_weights, n)
+    _checks.require_dtype("pred", pred)
+    _checks.require_dtype("target", target)
+    _checks.require_dtype("node_weights", node_weights, (torch.float32, torch.bool))
+    _checks.require_device(("pred", pred), ("target", target), ("node_weights", node_weights))
     p, t = pred.detach().contiguous(), target.detach().contiguous()
     w = None if node_weights is None else node_weights.detach().to(torch.float32).contiguous()
     hist = torch.empty(c, m + 1, dtype=torch.float32, device=p.device)
